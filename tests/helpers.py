@@ -1,9 +1,25 @@
 """Shared test helpers: scene -> boundary arguments, oracle frame, comparison utilities."""
+from pathlib import Path
+
+import numpy as np
 import torch
 
 from oracle import gsplat_oracle as O
 from tinysplat_amd.rasterizer import project_args, raster_args, sh_args, tile_bounds
 from tinysplat_amd.synthetic import make_scene
+
+
+GOLD = Path(__file__).resolve().parent / "golden"
+
+
+def load_golden(name):
+    """The arrays of tests/golden/<name>.npz, with those of <name>.post.npz (the expected state after the operation)
+    merged in where a fixture is stored in two files to keep every committed file below 1 MiB."""
+    z = dict(np.load(GOLD / f"{name}.npz"))
+    post = GOLD / f"{name}.post.npz"
+    if post.exists():
+        z.update(np.load(post))
+    return z
 
 
 def scene_args(n, sh_degree, width, height, seed=0, scale_mult=1.0, device="cpu", dtype=None):

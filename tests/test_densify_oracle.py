@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import load_golden
 from oracle import densify_oracle as D
 
 GOLD = Path(__file__).resolve().parent / "golden"
@@ -20,7 +21,7 @@ def _state(z, prefix):
 
 @pytest.mark.parametrize("name", ["densify_n1200_k15", "densify_n300_k0"])
 def test_densify_and_prune_matches_reference(name):
-    z = np.load(GOLD / f"{name}.npz")
+    z = load_golden(name)
     p, m, v, accum = _state(z, "pre")
     # update_grad_accum: the fixture's accumulator is two frames of xys gradients
     a = torch.zeros(int(z["n"]))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import load_golden
 from oracle import densify_oracle as D
 from tinysplat_amd.densify import DensifyConfig, Densifier
 from tinysplat_amd.synthetic import SplatModel
@@ -57,7 +58,7 @@ def _check_state(model, optim, dens, rp, rm, rv, ra, first_sampled=None):
 
 @pytest.mark.parametrize("name", ["densify_n1200_k15", "densify_n300_k0"])
 def test_densify_and_prune_matches_reference_fixture(name):
-    z = np.load(GOLD / f"{name}.npz")
+    z = load_golden(name)
     p, m, v, accum = _load(z, "pre")
     model, optim = _on_device(p, m, v)
     cfg = DensifyConfig(interval_densify=int(z["interval_densify"]), tau_means=float(z["tau_means"]),

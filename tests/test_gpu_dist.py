@@ -91,7 +91,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     JSON line; on this 1-GPU box both ranks share cuda:0 (--single-device, gloo)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--single-device", "--backend",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--full", "--single-device", "--backend",
                         "gloo", "--config", "2", "--depth", "--steps", "3", "--warmup", "1", "--profile-steps", "1",
                         "--no-cpu-baseline", "--no-pmc", "--no-bandwidth"],      # (no --shard-mode: N > 1 defaults to 'both')
                        env=env, capture_output=True, text=True, timeout=600)

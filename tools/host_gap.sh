@@ -9,7 +9,7 @@ lscpu | grep -E "Model name|^CPU\(s\)" >> "$out"
 for cfg in 3 2; do
   for cap in 0 1; do
     for rep in 1 2 3; do
-      TS_CAPACITY_ALLOC=$cap python bench.py --config $cfg --steps 50 --warmup 10 --no-pmc --no-cpu-baseline --no-bandwidth --no-rgbd-figure 2>/dev/null \
+      TS_CAPACITY_ALLOC=$cap python bench.py --full --config $cfg --steps 50 --warmup 10 --no-pmc --no-cpu-baseline --no-bandwidth --no-rgbd-figure 2>/dev/null \
         | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

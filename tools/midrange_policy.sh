@@ -4,7 +4,7 @@
 run() {   # G rank env...
   g=$1; r=$2; shift 2
   echo -n "G=$g [$*] "
-  env "$@" python bench.py --emulate-ranks $g --emulate-rank $r --shard-mode replicated --steps 30 --no-cpu-baseline --no-pmc --no-bandwidth --no-rgbd-figure 2>/dev/null | python -c "
+  env "$@" python bench.py --full --emulate-ranks $g --emulate-rank $r --shard-mode replicated --steps 30 --no-cpu-baseline --no-pmc --no-bandwidth --no-rgbd-figure 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); e=d['entries_ms']; print(round(d['ms_per_step'],3), 'fwd', round(e['ts_raster_fwd'],3), 'bwd', round(e['ts_raster_bwd'],3), 'reduce', round(e.get('ts_reduce_partials',0),3))"
 }

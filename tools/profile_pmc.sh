@@ -3,11 +3,11 @@
 # usage: tools/profile_pmc.sh <tag> "<counters...>" [bench args...]
 set -u
 TAG=$1; CNT=$2; shift 2
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $CNT --output-format csv -d "$OUT/raw" -o "$TAG" -- python "$REPO/bench.py" --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --no-pmc --no-bandwidth "$@" > "$OUT/bench.log" 2>&1
+rocprofv3 --pmc $CNT --output-format csv -d "$OUT/raw" -o "$TAG" -- python "$REPO/bench.py" --full --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --no-pmc --no-bandwidth "$@" > "$OUT/bench.log" 2>&1
 F=$(find "$OUT/raw" -name "*counter_collection.csv" | head -1)
 python - "$F" "$OUT/${TAG}_pmc_summary.csv" <<'PY'
 import csv, sys, collections

@@ -6,11 +6,11 @@
 # usage: tools/profile_round.sh <tag>
 set -u
 TAG=${1:-r01}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$REPO"
-python bench.py 2> "$OUT/bench.err" | tail -1 > "$OUT/bench.json"
+python bench.py --full 2> "$OUT/bench.err" | tail -1 > "$OUT/bench.json"
 bash tools/profile_stats.sh "$TAG" > /dev/null 2>&1
 cp gpurun_out/prof_$TAG/${TAG}_kernel_stats.csv "$OUT/" 2>/dev/null
 grep -o '^{.*' gpurun_out/prof_$TAG/bench.log > "$OUT/bench_under_rocprof.json"

@@ -23,7 +23,7 @@ for mode in args.modes.split(","):
     for r in range(args.ranks):
         cmd = [sys.executable, str(ROOT / "bench.py"), "--config", str(args.config), "--emulate-ranks", str(args.ranks),
                "--emulate-rank", str(r), "--shard-mode", args.shard_mode, "--steps", str(args.steps), "--warmup", "10",
-               "--no-cpu-baseline", "--no-pmc", "--no-bandwidth", "--no-rgbd-figure", "--profile-steps", "3"]
+               "--full", "--no-cpu-baseline", "--no-pmc", "--no-bandwidth", "--no-rgbd-figure", "--profile-steps", "3"]
         if args.top_third:
             cmd += ["--top-third", str(args.top_third)]
         if mode == "balanced":

@@ -34,10 +34,10 @@ run() {   # run <tag> <ranks> <bench args...>
   if [ $DRY = 1 ]; then extra="--backend gloo --single-device --no-pmc --no-bandwidth --prewarm-ms 0"; fi
   echo "== $tag: $n rank(s): bench.py --gpus $n $* $extra" >&2
   if [ "$n" = 1 ]; then
-    python bench.py --gpus 1 --steps $STEPS --warmup $WARMUP --no-cpu-baseline $extra "$@" > "$OUT/$tag.json" 2> "$OUT/$tag.log"
+    python bench.py --gpus 1 --full --steps $STEPS --warmup $WARMUP --no-cpu-baseline $extra "$@" > "$OUT/$tag.json" 2> "$OUT/$tag.log"
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $port \
-      bench.py --gpus "$n" --steps $STEPS --warmup $WARMUP --no-cpu-baseline $extra "$@" > "$OUT/$tag.json" 2> "$OUT/$tag.log"
+      bench.py --gpus "$n" --full --steps $STEPS --warmup $WARMUP --no-cpu-baseline $extra "$@" > "$OUT/$tag.json" 2> "$OUT/$tag.log"
   fi
   local rc=$?
   tail -n 1 "$OUT/$tag.json" | python -c "

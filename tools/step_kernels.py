@@ -2,7 +2,7 @@
 """Lists the GPU kernels of ONE step (between two project_fwd launches) of a rocprofv3 --kernel-trace csv: start,
 duration, gap to the previous kernel - which launches around the HIP entries does PyTorch add to a training step?
 
-usage: rocprofv3 --kernel-trace --output-format csv -d DIR -o NAME -- python bench.py --train-step ...
+usage: rocprofv3 --kernel-trace --output-format csv -d DIR -o NAME -- python bench.py --full --train-step ...
        python tools/step_kernels.py DIR        (developer tool)
 """
 import csv

@@ -1,10 +1,10 @@
 #!/bin/bash
 # Kernel timeline (start, duration, gap before) of the last frame of bench.py's timed loop under rocprofv3
 # --kernel-trace.  usage (GPU box): tools/timeline.sh <first-kernel-substring> <bench.py arguments...>
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 FIRST=$1; shift
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/tl
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -o tl -- python $REPO/bench.py "$@" --steps 4 --warmup 2 --profile-steps 0 --no-cpu-baseline --no-pmc --no-bandwidth --no-rgbd-figure > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -o tl -- python $REPO/bench.py --full "$@" --steps 4 --warmup 2 --profile-steps 0 --no-cpu-baseline --no-pmc --no-bandwidth --no-rgbd-figure > /dev/null 2>&1
 FIRST="$FIRST" python - <<'PY'
 import csv, glob, os
 kt = glob.glob("/tmp/tl/**/*kernel_trace.csv", recursive=True)
