@@ -658,6 +658,32 @@ int ts_ply_unpack_rows(int32_t n, int32_t k_rest, const float* rows, float* mean
                        float* colors_rest, float* opacities, float* scales, float* quats,
                        void* stream);
 
+/* ============== point-cloud initialisation (GaussianModel.from_pcd, model_gaussian.py:66-90) ===== */
+/* Exact k nearest neighbours: for each of the m queries (float32 [m,3]) the k <= TS_KNN_MAX_K nearest of
+ * the n points (float32 [n,3]), ascending in (distance, index), distances sqrt(dx*dx + dy*dy + dz*dz)
+ * evaluated in double and rounded to float32 -> dist float32 [m,k], idx int32 [m,k].  queries == points
+ * with m == n is the self-search (every point finds itself at distance 0).  The result is a fixed
+ * function of the input (bit-identical from run to run).  ws: >= ts_knn_ws_bytes(n, m, k) bytes, 256-byte
+ * aligned.  stats: NULL, or a device int32[2] <- {queries that took the brute-force fallback, rings of
+ * grid cells the longest ring search visited}.  TS_E_BADARG (device untouched): n < 1, k outside
+ * 1..TS_KNN_MAX_K, k > n, m < 0, NULL points / ws, NULL queries / dist / idx with m > 0. */
+#define TS_KNN_MAX_K 16
+int64_t ts_knn_ws_bytes(int32_t n, int32_t m, int32_t k);
+int ts_knn(int32_t n, const float* points, int32_t m, const float* queries, int32_t k, float* dist,
+           int32_t* idx, void* ws, int32_t* stats, void* stream);
+
+/* The six tensors of from_pcd in one launch: means = xyz; colors_dc = RGB2SH(colors / 255) (colors:
+ * float32 [n,3] holding 0..255); colors_rest [n, k_rest, 3] = 0; scales [n,3] = log(float32(mean of the
+ * double distances to neighbours 1..3)) from knn_idx, the int32 [n,4] k = 4 self-search (column 0, the
+ * point itself or a coincident one, is dropped); quats [n,4] = random_quat_tensor's formula of the
+ * uniforms u, v, w [n] (utils.py:15-27); opacities [n,1] = logit(0.1).  mean_dist: NULL, or float32 [n]
+ * <- the mean distance before the log.  TS_E_BADARG: n < 4, k_rest < 0, a NULL pointer
+ * (colors_rest may be NULL when k_rest == 0). */
+int ts_init_from_points(int32_t n, int32_t k_rest, const float* xyz, const float* colors, const float* u,
+                        const float* v, const float* w, const int32_t* knn_idx, float* means,
+                        float* colors_dc, float* colors_rest, float* scales, float* quats,
+                        float* opacities, float* mean_dist, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

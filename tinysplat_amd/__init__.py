@@ -5,9 +5,11 @@ model_gaussian.py:14) plus the render adapter.  ``tinysplat_amd.sh`` mirrors ``g
 """
 from .ops import (deg_from_sh, num_sh_bases, project_gaussians, rasterize_gaussians,
                   spherical_harmonics)
+from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
 from .rasterizer import GaussianRasterizer
 from .scene import Scene
 from .synthetic import RGB2SH, SH2RGB
 
 __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "num_sh_bases",
-           "deg_from_sh", "GaussianRasterizer", "Scene", "RGB2SH", "SH2RGB"]
+           "deg_from_sh", "GaussianRasterizer", "Scene", "RGB2SH", "SH2RGB", "PointCloud", "from_pcd", "knn_points",
+           "read_point_cloud_ply"]

@@ -23,6 +23,8 @@ SOURCES = [
     ("formats.hip", []),
     ("frame.hip", []),
     ("shard.hip", ["-ffp-contract=off"]),
+    # knn.hip: neighbour distances are compared bit-for-bit with a float64 oracle (sqrt of dx*dx + dy*dy + dz*dz)
+    ("knn.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -174,6 +174,9 @@ SIGNATURES = {
     "ts_frame_fwd_composite": (c_int32, [_FRAME, _P]),
     "ts_frame_bwd_composite": (c_int32, [_FRAME, _P]),
     "ts_frame_bwd_params": (c_int32, [_FRAME, _P]),
+    "ts_knn_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "ts_knn": (c_int32, [c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P, _P]),
+    "ts_init_from_points": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
