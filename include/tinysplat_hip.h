@@ -684,6 +684,15 @@ int ts_init_from_points(int32_t n, int32_t k_rest, const float* xyz, const float
                         float* colors_dc, float* colors_rest, float* scales, float* quats,
                         float* opacities, float* mean_dist, void* stream);
 
+/* ================= surface regularisers of the training loop (scripts/train.py:71-75) ============== */
+/* Opacity entropy: o = sigmoid(opacities[i]), loss[0] <- -mean(o log(o + 1e-10) + (1 - o) log(1 - o + 1e-10))
+ * over the n logits (float32 [n]; a [n,1] tensor is the same memory); v_opacities: NULL, or float32 [n] <-
+ * d loss / d opacities (autograd's chain of that expression).  Deterministic (no atomics; fixed-order sums in
+ * double).  ws: >= ts_opacity_entropy_ws_bytes(n) bytes, 8-byte aligned.  TS_E_BADARG: n < 1, a NULL pointer
+ * (v_opacities may be NULL). */
+int64_t ts_opacity_entropy_ws_bytes(int32_t n);
+int ts_opacity_entropy(int32_t n, const float* opacities, float* loss, float* v_opacities, void* ws, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

@@ -177,6 +177,8 @@ SIGNATURES = {
     "ts_knn_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ts_knn": (c_int32, [c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P, _P]),
     "ts_init_from_points": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_opacity_entropy_ws_bytes": (c_int64, [c_int32]),
+    "ts_opacity_entropy": (c_int32, [c_int32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -282,9 +282,18 @@ class TrainStep:
         _hold(model, "TrainStep")        # per-row state now exists outside the model: see SplatModel.spatial_sort_
 
     def __call__(self, camera, target_rgb: Tensor, target_depth: Optional[Tensor] = None,
-                 densifier=None, step: Optional[int] = None):
+                 densifier=None, step: Optional[int] = None, surface=None):
         """``densifier`` (densify.Densifier) + ``step`` add train.py:99-102 after the Adam update:
-        gradient accumulation and, on the policy's steps, clone / split / prune."""
+        gradient accumulation and, on the policy's steps, clone / split / prune.
+        ``surface`` (surface.SurfaceRegularizer) + ``step`` add the regularisers of train.py:71-75 that its schedule
+        makes active at ``step``: ``loss += lambda * term``, one backward for the whole loss, then the two-launch Adam
+        (the fused in-backward update only sees the frame's own gradients).  On a step where none is active the step
+        is exactly the one without ``surface``."""
+        terms = {}
+        if surface is not None:
+            if step is None:
+                raise ValueError("the surface regularisers need the 1-based step number")
+            terms = surface.terms(self.model, step)
         rgb, extras = self.scene.render(camera)
         frame = getattr(rgb, "_base", None)
         depth = extras["depth"]
@@ -307,9 +316,16 @@ class TrainStep:
             loss, l1, ssim = photometric_loss(rgb, target_rgb, self.lambda_dssim)
             if target_depth is not None:                          # train.py:65-69
                 loss = loss + self.lambda_depth * (extras["depth"] - target_depth).abs().mean()
+        if terms:                                              # train.py:71-75: loss += lambda * term
+            extra = None
+            for weight, term in terms.values():
+                extra = weight * term if extra is None else extra + weight * term
+            if direct is not None:
+                direct = (direct[0] + [extra], direct[1] + [None])
+            loss = loss + extra
         # `direct`: the loss launches already produced dloss / d(rgb, depth) - they go straight into the frame's backward
         run_backward = (lambda: torch.autograd.backward(*direct)) if direct is not None else loss.backward
-        if self.fused_adam:
+        if self.fused_adam and not terms:
             from .frame import fused_adam
             with fused_adam(self.optimizer):
                 run_backward()
@@ -325,8 +341,10 @@ class TrainStep:
             densifier.update_grad_accum(step, extras)         # train.py:101
             densifier.densify_and_prune(step, self.optimizer, extras)   # train.py:102
         self.optimizer.zero_grad()
-        return {"loss": loss.detach(), "l1": l1, "ssim": ssim, "radii": extras["radii"],
-                "xys_grad": xys_grad}
+        out = {"loss": loss.detach(), "l1": l1, "ssim": ssim, "radii": extras["radii"], "xys_grad": xys_grad}
+        for name, (_, term) in terms.items():
+            out[name] = term.detach()
+        return out
 
 
 class Scheduler:
@@ -363,15 +381,19 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
         sh_increment_interval: int = 500, max_sh_degree: int = 3, lambda_dssim: float = 0.2,
         lambda_depth: float = 0.2, depth_schedule: Optional[Scheduler] = None, densifier=None,
         lrs: Optional[Dict[str, float]] = None, rng=None, generator: Optional[torch.Generator] = None,
-        on_step=None):
+        on_step=None, surface=None):
     """The training loop of scripts/train.py:45-106 (steps 1-7) on in-memory cameras / targets:
     SH degree schedule (:49-50, model_gaussian.py:126-128), random background (:51), camera pick
-    (:54), render + loss (:55-69), backward + Adam (:93-97), gradient accumulation and
-    densification (:99-102).  Dataset loading, the opacity / density regularisers of the surface
-    extension (:71-90), metrics and checkpoints stay with the caller (``on_step(step, out)``)."""
+    (:54), render + loss (:55-69), the opacity-entropy regulariser (:71-75) when ``surface``
+    (surface.SurfaceConfig) enables it, backward + Adam (:93-97), gradient accumulation and
+    densification (:99-102).  Dataset loading, the SuGaR density regulariser of the surface
+    extension (:77-91), metrics and checkpoints stay with the caller (``on_step(step, out)``)."""
     dev = torch.device(device)
     scene = Scene(cameras, model, device=dev, rng=rng)
     step_fn = TrainStep(model, dev, lambda_dssim, lambda_depth, lrs, scene=scene)
+    if surface is not None:
+        from .surface import SurfaceRegularizer
+        surface = SurfaceRegularizer(surface)
     pick = scene._sampler
     out = None
     for step in range(1, int(max_iter) + 1):
@@ -382,7 +404,7 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
         i = pick(step)
         use_depth = depth_targets is not None and (depth_schedule is None or depth_schedule(step))
         out = step_fn(cameras[i], targets[i], depth_targets[i] if use_depth else None,
-                      densifier=densifier, step=step)
+                      densifier=densifier, step=step, surface=surface)
         if on_step is not None:
             on_step(step, out)
     return out
