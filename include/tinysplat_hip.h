@@ -693,6 +693,47 @@ int ts_init_from_points(int32_t n, int32_t k_rest, const float* xyz, const float
 int64_t ts_opacity_entropy_ws_bytes(int32_t n);
 int ts_opacity_entropy(int32_t n, const float* opacities, float* loss, float* v_opacities, void* ws, void* stream);
 
+/* SuGaR density regulariser (scripts/train.py:77-91, model_gaussian.py:244-326).
+ * ts_density_sample: m sample points of the n Gaussians.  Rows: rows_in (int32 [m], given), or the inverse CDF of
+ * uniforms (float32 [m] in [0, 1)) over the weights prod(exp(scales)) (TS_DENSITY_WEIGHTS_AREA) or their inclusive
+ * prefix sums (TS_DENSITY_WEIGHTS_REFERENCE, the reference's quirk), prefix sums in double by a fixed tree.
+ * points[i] = means[r] + R(quats[r] / |quats[r]|) (exp(scales[r]) * normals[i]); rows <- r (-1 and NaN points for a
+ * given row outside [0, n)); frozen float32 [m, TS_DENSITY_FROZEN] <- {normals, exp(scales[r]), quats[r]}.
+ * ws: >= ts_density_sample_ws_bytes(n) bytes, 256-byte aligned.
+ * ts_density_loss: with knn int32 [m, TS_DENSITY_K] (the points' neighbours among the means), depth float32 [H, W]
+ * and view_proj_host (host float[32]: the row-major 4x4 view, then projection matrix): out float32[3] <- {mean of
+ * |d - approx| over the masked points (NaN if none), 1 / count (0 if none), count}.  density / beta / approx /
+ * mask: all NULL or all float32 [m] (mask uint8) <- the per-point values.  grad_rows / tap_keys / tap_vals: all NULL
+ * (forward only) or float32 [m * (TS_DENSITY_K + 1), TS_DENSITY_ROW] <- the unscaled gradient rows {means, scales,
+ * quats, opacities} of every (point, neighbour) pair, then of every point's sampling source (through frozen), and
+ * int32 / float32 [m, 4] <- the bilinear depth taps (pixel y * W + x, or H * W for none; d loss / d depth there,
+ * unscaled).  ws: >= ts_density_loss_ws_bytes(m) bytes.  TS_E_BADARG: n < TS_DENSITY_K, m < 1, H * W >= 2^31.
+ * ts_segment_sum: out float32 [num_keys, width] <- scale[0] * the sum over e of vals[perm[e], :] for
+ * keys_sorted[e] == key (keys >= num_keys dropped), entries summed in their sorted order in double, in chunks;
+ * width 1 or TS_DENSITY_ROW.  ws: >= ts_segment_sum_ws_bytes(entries, width) bytes, 256-byte aligned.
+ * All three are deterministic (no atomics). */
+#define TS_DENSITY_K 16
+#define TS_DENSITY_ROW 11
+#define TS_DENSITY_FROZEN 10
+#define TS_DENSITY_PROJ_REFERENCE 0
+#define TS_DENSITY_PROJ_SCREEN 1
+#define TS_DENSITY_WEIGHTS_REFERENCE 0
+#define TS_DENSITY_WEIGHTS_AREA 1
+int64_t ts_density_sample_ws_bytes(int32_t n);
+int ts_density_sample(int32_t n, int32_t m, int32_t weights, const float* means, const float* scales, const float* quats,
+                      const float* uniforms, const int32_t* rows_in, const float* normals, int32_t* rows, float* points,
+                      float* frozen, void* ws, void* stream);
+int64_t ts_density_loss_ws_bytes(int32_t m);
+int ts_density_loss(int32_t n, int32_t m, const float* points, const int32_t* rows, const float* frozen,
+                    const int32_t* knn, const float* means, const float* scales, const float* quats,
+                    const float* opacities, int32_t height, int32_t width, const float* depth,
+                    const float* view_proj_host, int32_t projection, float znear, float* out, float* density,
+                    float* beta, float* approx, uint8_t* mask, float* grad_rows, int32_t* tap_keys, float* tap_vals,
+                    void* ws, void* stream);
+int64_t ts_segment_sum_ws_bytes(int64_t entries, int32_t width);
+int ts_segment_sum(int64_t entries, int32_t width, int32_t num_keys, const int32_t* keys_sorted, const int64_t* perm,
+                   const float* vals, const float* scale, float* out, void* ws, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

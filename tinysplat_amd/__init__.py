@@ -8,9 +8,11 @@ from .ops import (deg_from_sh, num_sh_bases, project_gaussians, rasterize_gaussi
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
 from .rasterizer import GaussianRasterizer
 from .scene import Scene
-from .surface import SurfaceConfig, SurfaceRegularizer, opacity_entropy
+from .surface import (DensitySamples, SurfaceConfig, SurfaceRegularizer, density_loss, density_parts, opacity_entropy,
+                      sample_points)
 from .synthetic import RGB2SH, SH2RGB
 
 __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "num_sh_bases",
            "deg_from_sh", "GaussianRasterizer", "Scene", "RGB2SH", "SH2RGB", "PointCloud", "from_pcd", "knn_points",
-           "read_point_cloud_ply", "SurfaceConfig", "SurfaceRegularizer", "opacity_entropy"]
+           "read_point_cloud_ply", "SurfaceConfig", "SurfaceRegularizer", "opacity_entropy", "DensitySamples",
+           "sample_points", "density_loss", "density_parts"]

@@ -179,6 +179,13 @@ SIGNATURES = {
     "ts_init_from_points": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ts_opacity_entropy_ws_bytes": (c_int64, [c_int32]),
     "ts_opacity_entropy": (c_int32, [c_int32, _P, _P, _P, _P, _P]),
+    "ts_density_sample_ws_bytes": (c_int64, [c_int32]),
+    "ts_density_sample": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_density_loss_ws_bytes": (c_int64, [c_int32]),
+    "ts_density_loss": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, c_int32,
+                                  c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_segment_sum_ws_bytes": (c_int64, [c_int64, c_int32]),
+    "ts_segment_sum": (c_int32, [c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -285,9 +285,10 @@ class TrainStep:
                  densifier=None, step: Optional[int] = None, surface=None):
         """``densifier`` (densify.Densifier) + ``step`` add train.py:99-102 after the Adam update:
         gradient accumulation and, on the policy's steps, clone / split / prune.
-        ``surface`` (surface.SurfaceRegularizer) + ``step`` add the regularisers of train.py:71-75 that its schedule
-        makes active at ``step``: ``loss += lambda * term``, one backward for the whole loss, then the two-launch Adam
-        (the fused in-backward update only sees the frame's own gradients).  On a step where none is active the step
+        ``surface`` (surface.SurfaceRegularizer) + ``step`` add the regularisers of train.py:71-91 that its schedule
+        makes active at ``step`` (the density term on the rendered depth): ``loss += lambda * term``, one backward for
+        the whole loss, then the two-launch Adam (the fused in-backward update only sees the frame's own gradients);
+        after densification, the prune of train.py:103-105 on its step.  On a step where nothing is active the step
         is exactly the one without ``surface``."""
         terms = {}
         if surface is not None:
@@ -295,6 +296,8 @@ class TrainStep:
                 raise ValueError("the surface regularisers need the 1-based step number")
             terms = surface.terms(self.model, step)
         rgb, extras = self.scene.render(camera)
+        if surface is not None:                                # train.py:77-91: the density term reads the render
+            terms.update(surface.frame_terms(self.model, step, camera, extras))
         frame = getattr(rgb, "_base", None)
         depth = extras["depth"]
         direct = None
@@ -340,6 +343,8 @@ class TrainStep:
                 raise ValueError("densification needs the 1-based step number")
             densifier.update_grad_accum(step, extras)         # train.py:101
             densifier.densify_and_prune(step, self.optimizer, extras)   # train.py:102
+        if surface is not None:
+            surface.after_step(self.model, step, self.optimizer, densifier)   # train.py:103-105
         self.optimizer.zero_grad()
         out = {"loss": loss.detach(), "l1": l1, "ssim": ssim, "radii": extras["radii"], "xys_grad": xys_grad}
         for name, (_, term) in terms.items():
@@ -384,16 +389,17 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
         on_step=None, surface=None):
     """The training loop of scripts/train.py:45-106 (steps 1-7) on in-memory cameras / targets:
     SH degree schedule (:49-50, model_gaussian.py:126-128), random background (:51), camera pick
-    (:54), render + loss (:55-69), the opacity-entropy regulariser (:71-75) when ``surface``
-    (surface.SurfaceConfig) enables it, backward + Adam (:93-97), gradient accumulation and
-    densification (:99-102).  Dataset loading, the SuGaR density regulariser of the surface
-    extension (:77-91), metrics and checkpoints stay with the caller (``on_step(step, out)``)."""
+    (:54), render + loss (:55-69), the opacity-entropy (:71-75) and SuGaR density (:77-91)
+    regularisers when ``surface`` (surface.SurfaceConfig) enables them, backward + Adam (:93-97),
+    gradient accumulation and densification (:99-102), the density window's opening prune
+    (:103-105).  ``generator`` also draws the density samples.  Dataset loading, metrics and
+    checkpoints stay with the caller (``on_step(step, out)``)."""
     dev = torch.device(device)
     scene = Scene(cameras, model, device=dev, rng=rng)
     step_fn = TrainStep(model, dev, lambda_dssim, lambda_depth, lrs, scene=scene)
     if surface is not None:
         from .surface import SurfaceRegularizer
-        surface = SurfaceRegularizer(surface)
+        surface = SurfaceRegularizer(surface, generator)
     pick = scene._sampler
     out = None
     for step in range(1, int(max_iter) + 1):
