@@ -352,6 +352,11 @@ int ts_reduce_partials(int32_t n, int32_t channels, int32_t flags, const int32_t
 #define TS_FRAME_SEPARATE_SORT 128     /* ts_sort_tiles + ts_raster_fwd_planes even where ts_raster_fwd_sort applies: A/B */
 #define TS_FRAME_STRIPE 16             /* one stripe of a multi-GPU frame: colour stage only for the Gaussians the
                                           stripe lists, clamp mask applied in reduce_partials (before the all-reduce) */
+#define TS_FRAME_SURVIVORS 512         /* SURVIVOR LISTS (csrc/raster.hip): the forward compositing pass hands the entries
+                                          it staged to the backward pass, which replays those instead of re-culling the
+                                          lists (same rows, same gradients).  Only with the in-kernel sort on 16x16 lists
+                                          without TS_FRAME_SPLIT / NARROW_WAVES / SEPARATE_SORT (ignored otherwise), and
+                                          `survivors` set; bucket_ids then holds the survivors' ids after the forward pass */
 typedef struct ts_frame {
     int32_t n, num_bases, sh_degree, channels, flags;
     int32_t flag_gen;                         /* row-flag generation of the backward pass (0: zero row_flags) */
@@ -383,6 +388,9 @@ typedef struct ts_frame {
     /* TS_FRAME_PLANES: the depth plane of the image and of its gradient */
     float* out_depth;
     const float* v_out_depth;
+    /* TS_FRAME_SURVIVORS: int32 workspace, 8 * num_tiles rounded up to 64, plus one word per list entry (the buffers'
+     * capacity) - written by ts_frame_fwd_composite, read by ts_frame_bwd_composite */
+    int32_t* survivors;
 } ts_frame;
 int32_t ts_frame_struct_bytes(void);       /* sizeof(ts_frame): bindings check their mirror against it */
 int ts_frame_fwd_project(const ts_frame* f, void* stream);

@@ -59,7 +59,7 @@ class TsFrame(ctypes.Structure):
                     "v_out_img", "partials", "row_flags",
                     "v_xy", "v_conic", "v_colors", "v_depth", "v_opacity",
                     "v_means", "v_scales", "v_quats", "v_colors_dc", "v_colors_rest",
-                    "out_depth", "v_out_depth")])
+                    "out_depth", "v_out_depth", "survivors")])
 
 
 _FRAME = POINTER(TsFrame)

@@ -3,7 +3,8 @@
 // [+ depth], and its backward) enqueued from native code.
 //
 // Nothing is computed here: every function below calls the per-stage C-ABI entries of this library
-// (project.hip, binning.hip, raster.hip) in the order frame.py used to call them one by one through
+// (project.hip, binning.hip, raster.hip; the compositing pair through raster_survivors.h, which adds the
+// survivor lists to the same launches) in the order frame.py used to call them one by one through
 // ctypes.  What it buys is host time: a frame is ~30 kernel launches, and issuing them from Python
 // costs ~0.45 ms per frame - more than the GPU needs for a 100 k-Gaussian scene or for one tile
 // stripe of a multi-GPU frame.  From here a launch costs ~2 us.  The one host round trip of the path
@@ -22,6 +23,7 @@
 #endif
 
 #include "../../include/tinysplat_hip.h"
+#include "raster_survivors.h"
 
 // roctx ranges around the five executor calls: `rocprofv3 --marker-trace --kernel-trace` shows which kernels a
 // call enqueued and the gaps between them (no cost without a tool attached)
@@ -78,6 +80,13 @@ inline int small_n_fused() {
         return e ? atoi(e) : 262144;
     }();
     return v;
+}
+// SURVIVOR LISTS (TS_FRAME_SURVIVORS): the compositing pair of a frame on 16x16 lists with the in-kernel sort.  Both
+// passes ask the same question of the same struct, so the backward pass reads lists only where the forward pass wrote them
+inline bool survivors(const ts_frame* f) {
+    return (f->flags & TS_FRAME_SURVIVORS) && f->survivors && f->final_Ts && f->num_intersects > 0 &&
+           f->cam.wide_tiles == 0 &&
+           !(f->flags & (TS_FRAME_SPLIT | TS_FRAME_NARROW_WAVES | TS_FRAME_SEPARATE_SORT));
 }
 inline int raster_flags(const ts_frame* f) {
     return TS_RASTER_CLAMP_RGB | ((f->flags & TS_FRAME_SPLIT) ? TS_RASTER_SPLIT_BLOCKS : 0) |
@@ -154,9 +163,10 @@ int ts_frame_fwd_composite(const ts_frame* f, void* stream) {
                                  f->bin_ws, counter, stream));
     }
     if (fused_sort)
-        return ts_raster_fwd_sort(f->channels, raster_flags(f), &f->cam, f->tile_bins, f->bucket_ids, f->depths,
-                                  f->gaussian_ids_sorted, f->splats, f->background, f->out_img,
-                                  planes ? f->out_depth : nullptr, f->final_Ts, f->final_index, f->clamp_mask, stream);
+        return ts_surv::raster_fwd_sort(f->channels, raster_flags(f), &f->cam, f->tile_bins, f->bucket_ids, f->depths,
+                                        f->gaussian_ids_sorted, f->splats, f->background, f->out_img,
+                                        planes ? f->out_depth : nullptr, f->final_Ts, f->final_index, f->clamp_mask,
+                                        survivors(f) ? f->survivors : nullptr, stream);
     return ts_raster_fwd_planes(f->channels, raster_flags(f), &f->cam, f->tile_bins, f->gaussian_ids_sorted, f->splats,
                                 f->background, f->out_img, planes ? f->out_depth : nullptr, f->final_Ts,
                                 f->final_index, f->clamp_mask, stream);
@@ -166,13 +176,14 @@ int ts_frame_bwd_composite(const ts_frame* f, void* stream) {
     TsRange range_("ts_frame_bwd_composite");
     if (bad(f) || f->num_intersects < 0) return TS_E_BADARG;
     const bool planes = (f->flags & TS_FRAME_PLANES) != 0;
-    TS_TRY(ts_raster_bwd_planes(f->channels,
-                                ((raster_flags(f) & ~(TS_RASTER_CLAMP_RGB | TS_RASTER_SPLIT_BLOCKS)) | bwd_split(f)) |
-                                    TS_RASTER_FLAG_GEN(f->flag_gen),
-                                f->num_intersects, &f->cam, f->tile_bins, f->gaussian_ids_sorted, f->splats,
-                                f->background, f->final_Ts, f->final_index, f->v_out_img,
-                                planes ? f->v_out_depth : nullptr, planes ? 1 : 0, nullptr, f->clamp_mask, f->partials,
-                                f->row_flags, stream));
+    const bool surv = survivors(f);
+    TS_TRY(ts_surv::raster_bwd(f->channels,
+                               ((raster_flags(f) & ~(TS_RASTER_CLAMP_RGB | TS_RASTER_SPLIT_BLOCKS)) | bwd_split(f)) |
+                                   TS_RASTER_FLAG_GEN(f->flag_gen),
+                               f->num_intersects, &f->cam, f->tile_bins, f->gaussian_ids_sorted, f->splats,
+                               f->background, f->final_Ts, f->final_index, f->v_out_img,
+                               planes ? f->v_out_depth : nullptr, planes ? 1 : 0, nullptr, f->clamp_mask, f->partials,
+                               f->row_flags, surv ? f->bucket_ids : nullptr, surv ? f->survivors : nullptr, stream));
     const bool stripe = (f->flags & TS_FRAME_STRIPE) != 0;
     return ts_reduce_partials(f->n, f->channels,
                               TS_RASTER_LOGIT_OPACITY | bwd_split(f) | TS_RASTER_FLAG_GEN(f->flag_gen),

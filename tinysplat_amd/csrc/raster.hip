@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "../../include/tinysplat_hip.h"
+#include "raster_survivors.h"
 #include "splat_math.h"
 
 namespace {
@@ -289,9 +290,9 @@ __device__ __forceinline__ bool mask_rect(unsigned long long m, int& xmin, int& 
 // the block at first; it shrinks as pixels saturate in the forward pass / covers only the pixels
 // whose lists have started in the backward pass), kept in LDS so that the rolled loop can index it.
 // blocks = bit mask of the blocks whose rectangle is non-empty.
-template <int NB>
-__device__ __forceinline__ Staged stage_splat(bool have, const float4 q0, const float4 q1,
-                                              const float4* __restrict__ rects, int blocks) {
+// the staged fields of a record (mask left 0): shared by stage_splat and the backward's survivor walk, so that both
+// derive bit-identical values
+__device__ __forceinline__ Staged stage_fields(const float4 q0, const float4 q1) {
     Staged s;
     s.gx = q0.x; s.gy = q0.y;
     const float A = q0.w, Bc = q1.x, Cc = q1.y, op = q0.z;
@@ -300,6 +301,13 @@ __device__ __forceinline__ Staged stage_splat(bool have, const float4 q0, const 
     s.hC = 0.5f * kLog2e * Cc;
     s.lo = __log2f(op);
     s.mask = 0;
+    return s;
+}
+template <int NB>
+__device__ __forceinline__ Staged stage_splat(bool have, const float4 q0, const float4 q1,
+                                              const float4* __restrict__ rects, int blocks) {
+    Staged s = stage_fields(q0, q1);
+    const float op = q0.z;
     // bit NB ("general"): the per-pixel code must test sigma >= 0 and apply the 0.999 clamp.  For a
     // positive-definite conic and opacity <= 0.99 neither can trigger (sigma >= 0 up to rounding,
     // alpha = opacity * exp(-sigma) <= opacity), and the kernels take a leaner wave-uniform path.
@@ -888,13 +896,14 @@ __device__ __forceinline__ void coop_sort_tile(const int* __restrict__ g, const 
 // One 16x16 tile composited by the four waves of a workgroup (see COOPERATIVE TILES).  rec: 256 x 3 float4 staged
 // records (the whole-tile waves' lds_all), also the key array of the shared sort; rect_sh[4]: rectangle of the
 // unfinished pixels of block k; cnt_sh[4]: entries wave s staged in this round; alive_sh[4]: block k has unfinished pixels.
-template <int CH, bool SORT, bool SEGS>
+template <int CH, bool SORT, bool SEGS, bool SURV>
 __device__ __forceinline__ void coop_fwd_tile(
     const ts_camera& cam, int tile, int num_tiles, const int* __restrict__ tile_bins, const int* __restrict__ ids_sorted,
     const int* __restrict__ bucket_ids, const float* __restrict__ depths, int* ids_rw,
     const float4* __restrict__ splats, const float* __restrict__ background, float* __restrict__ out_img,
     float* __restrict__ out_depth, float* __restrict__ final_Ts, int* __restrict__ final_index, int clamp_rgb,
-    unsigned char* __restrict__ clamp_mask, float4* rec, float4* rect_sh, int* cnt_sh, int* alive_sh, int clock_unit) {
+    unsigned char* __restrict__ clamp_mask, float4* rec, float4* rect_sh, int* cnt_sh, int* alive_sh, int clock_unit,
+    int* sv_id, int* sv_meta, int* sv_cnt) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int tbx = cam.tile_bounds_x;
     const int tx = tile % tbx, ty = tile / tbx + cam.tile_row0;
@@ -988,14 +997,17 @@ __device__ __forceinline__ void coop_fwd_tile(
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 n0 = zero4, n1 = zero4, n2 = zero4;
     int id_next = 0;
+    int g_n = 0;                             // (SURV) the id of the record in n0 .. n2
     {
         const int i0 = range.x + 64 * wave + lane;
         if (i0 < range.y) {
             const int g = from_lds ? idr[0] : ids[i0];
             n0 = splats[3 * (size_t)g]; n1 = splats[3 * (size_t)g + 1]; n2 = splats[3 * (size_t)g + 2];
+            g_n = g;
         }
         if (i0 + 256 < range.y) id_next = from_lds ? idr[1] : ids[i0 + 256];
     }
+    int nsv = 0;                             // (SURV) survivors listed so far (SURVIVOR LISTS)
     int round = 0;
     for (int base = range.x; base < range.y; base += 256) {
         TS_SEG_T0(tseg_w0);
@@ -1007,9 +1019,11 @@ __device__ __forceinline__ void coop_fwd_tile(
         const int i = base + 64 * wave + lane;
         const bool have = i < range.y;
         const float4 q0 = n0, q1 = n1, q2 = n2;
+        const int g_q = g_n;
         if (i + 256 < range.y) {
             const int g = id_next;
             n0 = splats[3 * (size_t)g]; n1 = splats[3 * (size_t)g + 1]; n2 = splats[3 * (size_t)g + 2];
+            g_n = g;
         }
         if (i + 512 < range.y) id_next = from_lds ? (round == 0 ? idr[2] : idr[3]) : ids[i + 512];
         ++round;
@@ -1028,15 +1042,28 @@ __device__ __forceinline__ void coop_fwd_tile(
         TS_LDS_BARRIER();
         TS_SEG_ADD(ts_wave_clock_.seg, 1, tseg_w1);
         TS_SEG_T0(tseg_b);
+        if constexpr (SURV) {
+            // this wave's survivors go behind those of the waves in front of it: the round's entries stay in list order
+            int before = 0;
+#pragma unroll
+            for (int w = 0; w < 3; ++w) before += w < wave ? cnt_sh[w] : 0;
+            if (keep) {
+                const size_t at = (size_t)range.x + nsv + before + __popcll(kmask & ((1ull << lane) - 1ull));
+                sv_id[at] = g_q;
+                sv_meta[at] = ((i - range.x) << 8) | s.mask;
+            }
+        }
         // block `wave`: the staged entries of the four source waves in list order
 #pragma unroll 1
         for (int src = 0; src < 4; ++src) {
             if (SEGS && base + 64 * src == next_ck) {     // a segment boundary (never the list's first entry)
+                if constexpr (SURV) if (wave == 0 && lane == 0) sv_cnt[8 * (size_t)tile + ck] = nsv;
                 store_ck(ck);
                 ++ck;
                 next_ck = ck < S_seg ? range.x + seg_bound(n, S_seg, ck) : 0x7fffffff;
             }
             const int c = cnt_sh[src];
+            if constexpr (SURV) nsv += c;
             const float4* rs = rec + 3 * 64 * src;
             const int m = lane < c ? __float_as_int(rs[3 * lane + 2].w) : 0;
             unsigned long long bits = __ballot(((m >> wave) & 1) != 0);
@@ -1076,6 +1103,13 @@ __device__ __forceinline__ void coop_fwd_tile(
         TS_SEG_ADD(ts_wave_clock_.seg, 2, tseg_b);
     }
 
+    if constexpr (SURV) {
+        if (wave == 0 && lane == 0) {
+            sv_cnt[8 * (size_t)tile] = nsv;
+            if (SEGS && seg_on)
+                for (int r = ck; r < S_seg; ++r) sv_cnt[8 * (size_t)tile + r] = nsv;      // boundaries never reached
+        }
+    }
     if (SEGS && seg_on) {
         // the pass ended in segment ck - 1: its colour goes into record ck; the records behind hold no colour (see the
         // whole-tile waves of the split launches)
@@ -1123,14 +1157,20 @@ __device__ __forceinline__ void coop_fwd_tile(
 // ids_rw, the network of sort_tiles_small_kernel - when the list has at most kWaveSortMax entries (longer lists were
 // sorted by ts_sort_tiles_above before this launch).  The per-tile sort on its own is latency-bound (VALU 40 %, LDS
 // 59 % busy on config 3); inside this VALU-bound kernel its stalls are filled by other tiles' compositing.
-template <int CH, bool SPLIT, int NBX, bool WL, bool SORT = false, bool SEGS = false>
+// SURV (SURVIVOR LISTS; one wave or one cooperative workgroup per 16x16 tile on 16x16 lists): the pass also writes, in list
+// order, every entry it staged - sv_id = its Gaussian id, sv_meta = (list index - tile start) << 8 | its staged block
+// mask (bit 4: the general per-pixel code) - at the tile's list offset, and sv_cnt[8 tile] = their number, sv_cnt[8 tile
+// + s] = the number in front of segment boundary s (cut tiles).  sv_id may be bucket_ids: a tile's own sort has read
+// its bucket before the first survivor is written.  raster_bwd_kernel<.., SURV> replays these lists.
+template <int CH, bool SPLIT, int NBX, bool WL, bool SORT = false, bool SEGS = false, bool SURV = false>
 __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_MIN_WAVES_RGB : TS_FWD_MIN_WAVES_RGBD) : TS_FWD_MIN_WAVES) void raster_fwd_kernel(
     const ts_camera cam, const int num_tiles, const int* __restrict__ tile_bins,
     const int* __restrict__ ids_sorted, const int* __restrict__ bucket_ids, const float* __restrict__ depths,
     int* ids_rw, const float4* __restrict__ splats,
     const float* __restrict__ background, float* __restrict__ out_img, float* __restrict__ out_depth,
     float* __restrict__ final_Ts, int* __restrict__ final_index, const int clamp_rgb,
-    unsigned char* __restrict__ clamp_mask) {
+    unsigned char* __restrict__ clamp_mask, int* sv_id, int* sv_meta, int* sv_cnt) {
+    static_assert(!SURV || (!SPLIT && NBX == 2 && !WL && TS_LDS_DMA && !kSegsCoop), "survivor lists: one wave per 16x16 tile");
     constexpr int NB = 2 * NBX;
     TS_LDS_PAD_DECL();
     __shared__ float4 lds_all[kWaves][64 * 3];
@@ -1154,10 +1194,10 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
             const int ctile = (xcd * pl.per_xcd + pl.coop_lo) * kWaves + (pl.descending ? kWaves * pl.coop - 1 - t : t);
             if (ctile >= num_tiles) return;
             __shared__ int coop_cnt[4], coop_alive[4];
-            coop_fwd_tile<CH, SORT, SEGS>(cam, ctile, num_tiles, tile_bins, ids_sorted, bucket_ids, depths, ids_rw, splats,
-                                          background, out_img, out_depth, final_Ts, final_index, clamp_rgb, clamp_mask,
-                                          &lds_all[0][0], &rect_all[0][0], coop_cnt, coop_alive,
-                                          num_tiles + kWaves * (xcd * kWaves * pl.coop + t));
+            coop_fwd_tile<CH, SORT, SEGS, SURV>(cam, ctile, num_tiles, tile_bins, ids_sorted, bucket_ids, depths, ids_rw,
+                                                splats, background, out_img, out_depth, final_Ts, final_index, clamp_rgb,
+                                                clamp_mask, &lds_all[0][0], &rect_all[0][0], coop_cnt, coop_alive,
+                                                num_tiles + kWaves * (xcd * kWaves * pl.coop + t), sv_id, sv_meta, sv_cnt);
             return;
         } else {
             return;
@@ -1285,6 +1325,7 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
         loc.zero();
     };
 
+    int nsv = 0;                                                     // (SURV) survivors listed so far
     // the walk over the list, with (LOCP) or without the per-segment colour sums - two instantiations, so that the
     // whole tiles of a hybrid launch run the loop they always ran
     auto walk = [&](auto& loc_) {
@@ -1298,6 +1339,8 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
         const float4 q0 = have ? raw[lane] : zero4, q1 = have ? raw[64 + lane] : zero4,
                      q2 = have ? raw[128 + lane] : zero4;
         TS_LDS_WAIT();                               // read out before the next chunk's records may overwrite them
+        int g_cur = 0;                               // (SURV) this chunk's ids, requested in front of the next chunk's
+        if constexpr (SURV) if (have) g_cur = ids[i];
         if (i + 64 < range.y) dma_record(splats, id_next, raw);
 #else
         // (LOCP: the per-segment sums need twelve registers more; there the next chunk's records are requested AFTER
@@ -1305,6 +1348,7 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
         // cover the round trip)
         constexpr bool kLate = LOCP && TS_FWD_LATE_PREFETCH;
         const float4 q0 = n0, q1 = n1, q2 = n2;
+        const int g_cur = 0;                         // (SURV needs TS_LDS_DMA)
         auto prefetch = [&]() {
             if (i + 64 < range.y) {
                 const int g = id_next;
@@ -1321,6 +1365,7 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
             // a segment boundary (wave-uniform; never the list's first entry).  The record's stores are issued BEHIND the
             // loads of the next chunk's records: the wait for those loads then leaves the stores in flight
             if (base == next_ck) {
+                if constexpr (SURV) if (lane == 0) sv_cnt[8 * (size_t)tile + ck] = nsv;
                 store_ck(ck);
                 ++ck;
                 next_ck = ck < S_seg ? range.x + seg_bound(range.y - range.x, S_seg, ck) : 0x7fffffff;
@@ -1345,7 +1390,12 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
             lds[3 * pos] = make_float4(s.gx, s.gy, s.hA, s.B);
             lds[3 * pos + 1] = make_float4(s.hC, s.lo, q1.z, q1.w);
             lds[3 * pos + 2] = make_float4(q2.x, q2.y, __int_as_float(i), __int_as_float(s.mask));
+            if constexpr (SURV) {
+                sv_id[(size_t)range.x + nsv + pos] = g_cur;
+                sv_meta[(size_t)range.x + nsv + pos] = ((i - range.x) << 8) | s.mask;
+            }
         }
+        if constexpr (SURV) nsv += cnt;
         TS_WAVE_SYNC();
         TS_STAT(0, cnt);
         const bool general = __ballot(keep && (s.mask & (1 << NB))) != 0ull;
@@ -1367,6 +1417,13 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     else if (seg_on) walk(loc);
     else walk(no_loc);
 
+    if constexpr (SURV) {
+        if (lane == 0) {
+            sv_cnt[8 * (size_t)tile] = nsv;
+            if constexpr (kSegsF)
+                if (seg_on) for (int r = ck; r < S_seg; ++r) sv_cnt[8 * (size_t)tile + r] = nsv;   // boundaries never reached
+        }
+    }
     if constexpr (kSegsF) if (seg_on) {
         // the pass ended in segment ck - 1: its colour goes into record ck; the records behind hold no colour (the
         // wave's pixels are finished there - no segment replays them, fidx lies in front - or the list is shorter),
@@ -1807,7 +1864,16 @@ __device__ __forceinline__ void bwd_chunk(const float4* __restrict__ lds, int cn
 #define TS_BWD_WAVES 1
 #endif
 constexpr int kBwdWaves = TS_BWD_WAVES;
-template <int CH, bool SPLIT, int NBX, bool WL>
+// SURVIVOR LISTS (SURV; one wave per 16x16 tile on 16x16 lists, whole tiles and list-segment items).  The forward pass
+// stages entry i against the rectangles of the pixels still unfinished at the start of i's chunk, and every pixel whose
+// final_index is >= i is among them: its block mask (raster_fwd_kernel<.., SURV>) covers every block in which entry i
+// has a pixel with alpha >= 1/255 and idx <= fidx - all this pass needs - and an entry it culled contributes to no
+// gradient.  So the walk here goes over the forward pass's survivors of the item's range ([sv_cnt[s], sv_cnt[s + 1])
+// of the tile's list), 64 per chunk: the records of survivors only, the block mask taken over with the `i > bmax[k]`
+// cull, and no rectangles, exact tests or tile-box masks of its own.  A block the forward mask adds beyond what the
+// rectangles of the started pixels would keep finds no valid lane (the body's per-pixel test), so the same rows are
+// written with the same values.
+template <int CH, bool SPLIT, int NBX, bool WL, bool SURV = false>
 __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS_BWD_MIN_WAVES) void raster_bwd_kernel(
     const ts_camera cam, const int num_tiles, const long long num_isects,
     const int* __restrict__ tile_bins, const int* __restrict__ ids_sorted,
@@ -1815,7 +1881,9 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
     const float* __restrict__ final_Ts, const int* __restrict__ final_index,
     const float* __restrict__ v_out_img, const float* __restrict__ v_out_depth, const int planes,
     const float* __restrict__ v_out_alpha, const unsigned char* __restrict__ clamp_mask,
-    float* __restrict__ partials, unsigned char* __restrict__ row_flags) {
+    float* __restrict__ partials, unsigned char* __restrict__ row_flags,
+    const int* __restrict__ sv_id, const int* __restrict__ sv_meta, const int* __restrict__ sv_cnt) {
+    static_assert(!SURV || (!SPLIT && NBX == 2 && !WL && TS_LDS_DMA), "survivor lists: one wave per 16x16 tile");
     constexpr int NB = 2 * NBX;
     TS_LDS_PAD_DECL();
     __shared__ float4 lds_all[kBwdWaves][64 * 4];
@@ -1862,7 +1930,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
     int sb = range.x, se = range.y;
     bool front = false;                           // entries lie behind this segment: it starts from a checkpoint
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 n0 = zero4, n1 = zero4, n2 = zero4;
+    [[maybe_unused]] float4 n0 = zero4, n1 = zero4, n2 = zero4;
     int id_next = 0;
     if (kSegs && S_seg > 1) {
         const int len = range.y - range.x;
@@ -1972,6 +2040,78 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
 
     // same software pipeline as the forward kernel, walking the list back to front
     float4* raw = raw_all[TS_LDS_DMA ? wave : 0];
+    if constexpr (SURV) {
+        // the item's survivors [pb, pe) (positions in the tile's survivor list; clamped to the list)
+        const int* cnt_t = sv_cnt + 8 * (size_t)tile;
+        const int len = range.y - range.x;
+        int pb = 0, pe = cnt_t[0];
+        if (kSegs && S_seg > 1 && len >= kSegMinList) {
+            if (seg > 0) pb = cnt_t[seg];
+            if (seg + 1 < S_seg) pe = cnt_t[seg + 1];
+        }
+        pe = min(pe, len);
+        pb = max(pb, 0);
+        __shared__ int meta_all[kBwdWaves][64];      // landing zone of the next chunk's survivor words
+        int* meta_l = meta_all[wave];
+        const int* sid = sv_id + range.x;
+        const int* smeta = sv_meta + range.x;
+        auto dma_meta = [&](int p) {
+            __builtin_amdgcn_global_load_lds((gbl_ptr_t)(smeta + p), (lds_ptr_t)meta_l, 4, 0, 0);
+        };
+        if (pe - 1 - lane >= pb) {
+            dma_record(splats, sid[pe - 1 - lane], raw);
+            dma_meta(pe - 1 - lane);
+        }
+        if (pe - 65 - lane >= pb) id_next = sid[pe - 65 - lane];
+        for (int hi = pe - 1; hi >= pb; hi -= 64) {
+            TS_SEG_T0(tseg_p);
+            const int p = hi - lane;
+            const bool have = p >= pb;
+            TS_DMA_WAIT();                           // this chunk's records and survivor words have landed
+            const float4 q0 = have ? raw[lane] : zero4, q1 = have ? raw[64 + lane] : zero4,
+                         q2 = have ? raw[128 + lane] : zero4;
+            const int meta = have ? meta_l[lane] : 0;
+            TS_LDS_WAIT();                           // read out before the next chunk's may overwrite them
+            if (p - 64 >= pb) {
+                dma_record(splats, id_next, raw);
+                dma_meta(p - 64);
+            }
+            if (p - 128 >= pb) id_next = sid[p - 128];
+            const int i = range.x + (meta >> 8);
+            int mask = meta & ((2 << NB) - 1);       // the forward pass's blocks and bit NB (general)
+#pragma unroll
+            for (int k = 0; k < NB; ++k)
+                if (i > bmax[k]) mask &= ~(1 << k);  // nothing in block k got this far in forward
+            const bool keep = have && (mask & ((1 << NB) - 1)) != 0;
+            const unsigned long long kmask = __ballot(keep);
+            const int cnt = __popcll(kmask);
+            if (keep) {
+                const int pos = __popcll(kmask & ((1ull << lane) - 1ull));
+                const Staged s = stage_fields(q0, q1);
+                const int wm = __float_as_int(q2.w);
+                const int slot = __float_as_int(q2.z) + ty * (wm & 0xffff) + tx;      // (see below)
+                constexpr int RS = CH == 3 ? 3 : 4;
+                lds[RS * pos] = make_float4(s.gx, s.gy, s.hA, s.B);
+                lds[RS * pos + 1] = make_float4(s.hC, s.lo, q1.z, q1.w);
+                lds[RS * pos + 2] = make_float4(q2.x, CH == 3 ? __int_as_float(mask) : q2.y, __int_as_float(i),
+                                                __int_as_float(slot));
+                if (CH == 4) lds[RS * pos + 3] = make_float4(__int_as_float(mask), 0.f, 0.f, 0.f);
+            }
+            TS_WAVE_SYNC();
+            TS_STAT(2, cnt);
+            TS_STAT(7, min(64, hi - pb + 1));
+            TS_SEG_ADD(ts_wave_clock_.seg, 0, tseg_p);
+            const bool general = __ballot(keep && (mask & (1 << NB))) != 0ull;
+            if (general)
+                bwd_chunk<CH, true, NBX>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
+                                         row_flags, lane TS_SEG_ARG);
+            else
+                bwd_chunk<CH, false, NBX>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
+                                          row_flags, lane TS_SEG_ARG);
+            TS_WAVE_SYNC();
+        }
+        return;
+    }
     if (last - lane >= sb) {
         const int g = ids_sorted[last - lane];
 #if TS_LDS_DMA
@@ -2279,7 +2419,7 @@ int ts_raster_fwd_planes(int32_t channels, int32_t flags, const ts_camera* cam, 
     hipLaunchKernelGGL((raster_fwd_kernel<C, S, X, L, false, G>), dim3(grid), dim3(kThreads), 0, s, kcam, nt, \
                        tile_bins, gaussian_ids_sorted, (const int*)nullptr, (const float*)nullptr,   \
                        (int*)nullptr, sp, background, out_img, out_depth, final_Ts,                  \
-                       final_index, clamp, clamp ? clamp_mask : nullptr)
+                       final_index, clamp, clamp ? clamp_mask : nullptr, (int*)nullptr, (int*)nullptr, (int*)nullptr)
 #define TS_LAUNCH_FWD_X(C, S)                                                                      \
     do {                                                                                           \
         if (wide) TS_LAUNCH_FWD(C, S, 4, false, false);                                            \
@@ -2298,45 +2438,8 @@ int ts_raster_fwd_sort(int32_t channels, int32_t flags, const ts_camera* cam, co
                        const int32_t* bucket_ids, const float* depths, int32_t* gaussian_ids_sorted,
                        const float* splats, const float* background, float* out_img, float* out_depth,
                        float* final_Ts, int32_t* final_index, uint8_t* clamp_mask, void* stream) {
-    if (!cam || (channels != 3 && channels != 4) || (out_depth && channels != 4)) return TS_E_BADARG;
-    // 16x16 lists, one wave (or, split, one workgroup) per tile: the mappings in which a list has one owner
-    if (cam->wide_tiles != 0 || (flags & TS_RASTER_NARROW_WAVES)) return TS_E_BADARG;
-    const int nt = ts_num_tiles(cam);
-    if (nt <= 0) return 0;
-    if (!tile_bins || !background || !out_img || (!final_Ts != !final_index) || !bucket_ids || !depths ||
-        !gaussian_ids_sorted)
-        return TS_E_BADARG;
-    bool split = (flags & TS_RASTER_SPLIT_BLOCKS) != 0;
-    ts_camera kcam = *cam;
-    kcam.hints &= ~kHintCoopAll;
-    if (split && TS_COOP && (cam->hints & TS_HINT_COOP_SPLIT)) {          // see ts_raster_fwd_planes
-        split = false;
-        kcam.hints |= kHintCoopAll;
-    }
-    const int units = split ? 4 * nt : nt;
-    int grid = 8 * (((units + kWaves - 1) / kWaves + 7) / 8);      // see xcd_tile_group
-    hipStream_t s = (hipStream_t)stream;
-    const float4* sp = reinterpret_cast<const float4*>(splats);
-    const int clamp = (flags & TS_RASTER_CLAMP_RGB) ? 1 : 0;
-    const bool segs = final_Ts && TS_CAM_SEGS(*cam) > 1;                // list segments: see ts_raster_fwd_planes
-    if (!split) grid = fwd_plan(nt, kcam.hints, segs, true).grid();     // COOPERATIVE TILES
-#define TS_LAUNCH_FWD_SORT(C, S, G)                                                                            \
-    hipLaunchKernelGGL((raster_fwd_kernel<C, S, 2, false, true, G>), dim3(grid), dim3(kThreads), 0, s, kcam, nt, \
-                       tile_bins, (const int*)nullptr, bucket_ids, depths, gaussian_ids_sorted, sp, background, \
-                       out_img, out_depth, final_Ts, final_index, clamp, clamp ? clamp_mask : nullptr)
-    if (channels == 3) {
-        if (split && segs) TS_LAUNCH_FWD_SORT(3, true, true);
-        else if (split) TS_LAUNCH_FWD_SORT(3, true, false);
-        else if (segs) TS_LAUNCH_FWD_SORT(3, false, true);
-        else TS_LAUNCH_FWD_SORT(3, false, false);
-    } else {
-        if (split && segs) TS_LAUNCH_FWD_SORT(4, true, true);
-        else if (split) TS_LAUNCH_FWD_SORT(4, true, false);
-        else if (segs) TS_LAUNCH_FWD_SORT(4, false, true);
-        else TS_LAUNCH_FWD_SORT(4, false, false);
-    }
-#undef TS_LAUNCH_FWD_SORT
-    return launch_status();
+    return ts_surv::raster_fwd_sort(channels, flags, cam, tile_bins, bucket_ids, depths, gaussian_ids_sorted, splats,
+                                    background, out_img, out_depth, final_Ts, final_index, clamp_mask, nullptr, stream);
 }
 
 int ts_raster_bwd(int32_t channels, int32_t flags, int64_t num_intersects, const ts_camera* cam,
@@ -2355,7 +2458,80 @@ int ts_raster_bwd_planes(int32_t channels, int32_t flags, int64_t num_intersects
                          const float* v_out_img, const float* v_out_depth, int32_t planes,
                          const float* v_out_alpha, const uint8_t* clamp_mask,
                          float* partials, uint8_t* row_flags, void* stream) {
+    return ts_surv::raster_bwd(channels, flags, num_intersects, cam, tile_bins, gaussian_ids_sorted, splats, background,
+                               final_Ts, final_index, v_out_img, v_out_depth, planes, v_out_alpha, clamp_mask, partials,
+                               row_flags, nullptr, nullptr, stream);
+}
+
+}  // extern "C"
+
+namespace ts_surv {
+
+int raster_fwd_sort(int32_t channels, int32_t flags, const ts_camera* cam, const int32_t* tile_bins,
+                    const int32_t* bucket_ids, const float* depths, int32_t* gaussian_ids_sorted,
+                    const float* splats, const float* background, float* out_img, float* out_depth,
+                    float* final_Ts, int32_t* final_index, uint8_t* clamp_mask, int32_t* survivors, void* stream) {
+    if (!cam || (channels != 3 && channels != 4) || (out_depth && channels != 4)) return TS_E_BADARG;
+    // 16x16 lists, one wave (or, split, one workgroup) per tile: the mappings in which a list has one owner
+    if (cam->wide_tiles != 0 || (flags & TS_RASTER_NARROW_WAVES)) return TS_E_BADARG;
+    const int nt = ts_num_tiles(cam);
+    if (nt <= 0) return 0;
+    if (!tile_bins || !background || !out_img || (!final_Ts != !final_index) || !bucket_ids || !depths ||
+        !gaussian_ids_sorted)
+        return TS_E_BADARG;
+    bool split = (flags & TS_RASTER_SPLIT_BLOCKS) != 0;
+    // survivor lists: one wave (or cooperative workgroup) per tile, and a backward pass to read them
+    if (survivors && (split || !final_Ts)) return TS_E_BADARG;
+    ts_camera kcam = *cam;
+    kcam.hints &= ~kHintCoopAll;
+    if (split && TS_COOP && (cam->hints & TS_HINT_COOP_SPLIT)) {          // see ts_raster_fwd_planes
+        split = false;
+        kcam.hints |= kHintCoopAll;
+    }
+    const int units = split ? 4 * nt : nt;
+    int grid = 8 * (((units + kWaves - 1) / kWaves + 7) / 8);      // see xcd_tile_group
+    hipStream_t s = (hipStream_t)stream;
+    const float4* sp = reinterpret_cast<const float4*>(splats);
+    const int clamp = (flags & TS_RASTER_CLAMP_RGB) ? 1 : 0;
+    const bool segs = final_Ts && TS_CAM_SEGS(*cam) > 1;                // list segments: see ts_raster_fwd_planes
+    if (!split) grid = fwd_plan(nt, kcam.hints, segs, true).grid();     // COOPERATIVE TILES
+    int* sv_id = survivors ? const_cast<int*>(bucket_ids) : nullptr;    // (a tile's bucket is dead once it is sorted)
+    int* sv_cnt = survivors;
+    int* sv_meta = survivors ? survivors + survivor_counts(nt) : nullptr;
+#define TS_LAUNCH_FWD_SORT(C, S, G, V)                                                                            \
+    hipLaunchKernelGGL((raster_fwd_kernel<C, S, 2, false, true, G, V>), dim3(grid), dim3(kThreads), 0, s, kcam, nt, \
+                       tile_bins, (const int*)nullptr, bucket_ids, depths, gaussian_ids_sorted, sp, background, \
+                       out_img, out_depth, final_Ts, final_index, clamp, clamp ? clamp_mask : nullptr, sv_id, sv_meta, \
+                       sv_cnt)
+    if (channels == 3) {
+        if (split && segs) TS_LAUNCH_FWD_SORT(3, true, true, false);
+        else if (split) TS_LAUNCH_FWD_SORT(3, true, false, false);
+        else if (segs && survivors) TS_LAUNCH_FWD_SORT(3, false, true, true);
+        else if (segs) TS_LAUNCH_FWD_SORT(3, false, true, false);
+        else if (survivors) TS_LAUNCH_FWD_SORT(3, false, false, true);
+        else TS_LAUNCH_FWD_SORT(3, false, false, false);
+    } else {
+        if (split && segs) TS_LAUNCH_FWD_SORT(4, true, true, false);
+        else if (split) TS_LAUNCH_FWD_SORT(4, true, false, false);
+        else if (segs && survivors) TS_LAUNCH_FWD_SORT(4, false, true, true);
+        else if (segs) TS_LAUNCH_FWD_SORT(4, false, true, false);
+        else if (survivors) TS_LAUNCH_FWD_SORT(4, false, false, true);
+        else TS_LAUNCH_FWD_SORT(4, false, false, false);
+    }
+#undef TS_LAUNCH_FWD_SORT
+    return launch_status();
+}
+
+int raster_bwd(int32_t channels, int32_t flags, int64_t num_intersects, const ts_camera* cam,
+               const int32_t* tile_bins, const int32_t* gaussian_ids_sorted, const float* splats,
+               const float* background, const float* final_Ts, const int32_t* final_index,
+               const float* v_out_img, const float* v_out_depth, int32_t planes,
+               const float* v_out_alpha, const uint8_t* clamp_mask,
+               float* partials, uint8_t* row_flags, const int32_t* bucket_ids, const int32_t* survivors,
+               void* stream) {
     if (!cam || (channels != 3 && channels != 4) || num_intersects < 0) return TS_E_BADARG;
+    if (survivors && (!bucket_ids || (flags & (TS_RASTER_SPLIT_BLOCKS | TS_RASTER_NARROW_WAVES)) || cam->wide_tiles))
+        return TS_E_BADARG;
     if (planes ? channels != 4 : v_out_depth != nullptr) return TS_E_BADARG;
     const bool narrow = cam->wide_tiles != 0 && (flags & TS_RASTER_NARROW_WAVES) != 0;
     const int nt = narrow ? cam->tile_rows * cam->tile_bounds_x : ts_num_tiles(cam);
@@ -2387,16 +2563,19 @@ int ts_raster_bwd_planes(int32_t channels, int32_t flags, int64_t num_intersects
         grid = 8 * (((units + kBwdWaves - 1) / kBwdWaves + 7) / 8);            // see xcd_tile_group
     }
     const float4* sp = reinterpret_cast<const float4*>(splats);
-#define TS_LAUNCH_BWD(C, S, X, L)                                                                  \
-    hipLaunchKernelGGL((raster_bwd_kernel<C, S, X, L>), dim3(grid), dim3(64 * kBwdWaves), 0, s, *cam, nt, \
+    const int* sv_cnt = survivors;
+    const int* sv_meta = survivors ? survivors + survivor_counts(nt) : nullptr;
+#define TS_LAUNCH_BWD(C, S, X, L, V)                                                               \
+    hipLaunchKernelGGL((raster_bwd_kernel<C, S, X, L, V>), dim3(grid), dim3(64 * kBwdWaves), 0, s, *cam, nt, \
                        isects_tagged, tile_bins, gaussian_ids_sorted, sp, background,              \
                        final_Ts, final_index, v_out_img, v_out_depth, planes ? 1 : 0, v_out_alpha,  \
-                       clamp_mask, partials, row_flags)
+                       clamp_mask, partials, row_flags, bucket_ids, sv_meta, sv_cnt)
 #define TS_LAUNCH_BWD_X(C, S)                                                                      \
     do {                                                                                           \
-        if (wide) TS_LAUNCH_BWD(C, S, 4, false);                                                   \
-        else if (narrow) TS_LAUNCH_BWD(C, S, 2, true);                                             \
-        else TS_LAUNCH_BWD(C, S, 2, false);                                                        \
+        if (wide) TS_LAUNCH_BWD(C, S, 4, false, false);                                            \
+        else if (narrow) TS_LAUNCH_BWD(C, S, 2, true, false);                                      \
+        else if (survivors) TS_LAUNCH_BWD(C, false, 2, false, true);       /* (never split) */     \
+        else TS_LAUNCH_BWD(C, S, 2, false, false);                                                 \
     } while (0)
     if (channels == 3) { if (split) TS_LAUNCH_BWD_X(3, true); else TS_LAUNCH_BWD_X(3, false); }
     else { if (split) TS_LAUNCH_BWD_X(4, true); else TS_LAUNCH_BWD_X(4, false); }
@@ -2404,6 +2583,10 @@ int ts_raster_bwd_planes(int32_t channels, int32_t flags, int64_t num_intersects
 #undef TS_LAUNCH_BWD
     return launch_status();
 }
+
+}  // namespace ts_surv
+
+extern "C" {
 
 int ts_reduce_partials(int32_t n, int32_t channels, int32_t flags, const int32_t* num_tiles_hit,
                        const int32_t* cum_tiles_hit, const float* partials,

@@ -288,6 +288,13 @@ INLINE_SORT = os.environ.get("TS_INLINE_SORT", "1") != "0"
 
 DIRECT_GRADS = os.environ.get("TS_DIRECT_GRADS", "1") != "0"      # A/B switch (see _RenderFrame.backward)
 
+# SURVIVOR LISTS (TS_FRAME_SURVIVORS, csrc/raster.hip): a full frame on 16x16 lists with the in-kernel sort, not split,
+# that keeps what the backward pass needs - the forward compositing pass writes the entries it staged (ids into the dead
+# bucket_ids, one word per entry + per-tile counts behind gaussian_ids_sorted) and the backward pass replays those instead
+# of gathering and culling every listed entry again.  Same rows, same gradients.  TS_SURVIVORS=0: the re-culling replay.
+# (Frames timed per C-ABI entry - kernel_timer - keep the re-culling replay: the entries take no survivor lists.)
+SURVIVORS = os.environ.get("TS_SURVIVORS", "1") != "0"
+
 # CAPACITY ALLOCATION (option, off by default): the per-intersection buffers (bucket_ids | gaussian_ids_sorted;
 # partials in backward) are sized by the bounding-box pair count I, which only the GPU knows (gsplat synchronises
 # for it at the same place, rasterize.py:44).  With TS_CAPACITY_ALLOC=1, from the second frame of a (scene size,
@@ -450,6 +457,9 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
         fr.flags = ((1 if TIGHT_BINNING else 0) | (2 if F.split else 0) | (8 if mode == 2 else 0) | (16 if stripe else 0)
                     | (0 if TWO_HOP_SCATTER else 32) | (64 if F.planes else 0) | (0 if INLINE_SORT else 128)
                     | (256 if (full and not timed_) else 0))            # TS_FRAME_LIST_STATS (the slot holds four words)
+        surv = SURVIVORS and keep and full and mode == 0 and not F.split and INLINE_SORT and not timed_
+        if surv:
+            fr.flags |= 512                                               # TS_FRAME_SURVIVORS
         if full and not timed_:
             _stats_mode[dev.index] = mode
         fr.cam = cam
@@ -474,8 +484,12 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
 
         def lists(size):
             cap = alloc_quantum(size)                             # (a multiple of 64; sizes that repeat from frame to frame)
-            F.bucket_ids = torch.empty((2 * cap,), **i32)         # bucket_ids | gaussian_ids_sorted
+            # bucket_ids | gaussian_ids_sorted [| survivor counts (8 per tile, to a multiple of 64) + one word per entry]
+            counts = (8 * num_tiles + 63) // 64 * 64 if surv else 0
+            F.bucket_ids = torch.empty(((3 * cap + counts) if surv else 2 * cap,), **i32)
             fr.bucket_ids, fr.gaussian_ids_sorted = F.bucket_ids.data_ptr(), F.bucket_ids.data_ptr() + 4 * cap
+            if surv:
+                fr.survivors = F.bucket_ids.data_ptr() + 8 * cap
             return cap
 
         def prepare():
