@@ -742,6 +742,60 @@ int64_t ts_segment_sum_ws_bytes(int64_t entries, int32_t width);
 int ts_segment_sum(int64_t entries, int32_t width, int32_t num_keys, const int32_t* keys_sorted, const int64_t* perm,
                    const float* vals, const float* scale, float* out, void* ws, void* stream);
 
+/* SuGaR level-set surface points (model_gaussian.py:401-460, scene.py:165-192).  Additive
+ * entries: the ABI version is unchanged.  None of them allocates, synchronises or needs a workspace of its own; all
+ * are deterministic (plain stores, no atomics).
+ * ts_extract_pack: per Gaussian, records float32 [n, TS_EXTRACT_RECORD] <- {mean, U00 U01 U02 U11 U12 U22, sigmoid(o)}
+ * with Sigma^-1 = R diag(exp(-2 s)) R^T = U^T U (U upper triangular, evaluated in double, rounded once), and
+ * p_std float32 [n] <- |exp(scales)|.  TS_E_BADARG: n < 1, a NULL pointer.
+ * ts_extract_rays: per flat pixel index pixel_ids[i] (int64 [m]; an index outside [0, H * W) is an empty pixel and
+ * reads nothing): depth z = depth[f], NDC x / y by the convention (TS_EXTRACT_PIX_REFERENCE: x = f % H, y = f / H,
+ * ((x + 0.5) - W / 2) / H * 2 and ((y + 0.5) - H / 2) / W * 2 with integer halves, the reference as it stands;
+ * TS_EXTRACT_PIX_SCREEN: column f % W, row f / W, (col + 0.5 - W/2) * 2 / W), z_ndc = (P22 z + P23) / z, the product with
+ * inverse(P V) and the divide by w.  camera_host: host float[TS_EXTRACT_CAMERA_FLOATS] = {inverse(P V) row-major,
+ * camera position xyz, P22, P23}.  p_world / dirs float32 [m,3] <- the point and normalize(point - position) (eps
+ * 1e-12); valid int32 [m] <- 1, or 0 for depth <= 0, a non-finite depth or result: then p_world = anchor[0..2] (a
+ * device float[3], the first mean: its neighbours are found at once) and dirs = 0, so everything downstream stays finite.  TS_E_BADARG: m < 1, H or W < 1, H * W >= 2^31, an unknown
+ * convention, a NULL pointer, a non-finite camera value.
+ * ts_extract_samples: nearest int32 [m] (the k = 1 search of p_world among the means) -> p_std [m] <-
+ * p_std_table[nearest], samples float32 [m, steps, 3] <- p_world + (linspace(-e, e, steps)[s] * p_std) * dirs
+ * (torch's float32 linspace).  TS_E_BADARG: n < 1, m < 1, steps outside 2..TS_EXTRACT_MAX_STEPS, m * steps >= 2^31,
+ * extent_sigmas not positive and finite, a NULL pointer.
+ * ts_extract_march: knn int32 [m * steps, TS_EXTRACT_K] (the samples' neighbours, 64-byte aligned rows) -> per ray
+ * first int32 <- the first sample with d > level (0 if none), keep int32 <- valid && d[0] < level && first >= 1,
+ * t float32 <- the linear interpolation of the level between samples first - 1 and first, points float32 [m,3] <-
+ * p_world + t * dirs (t and points 0 where keep is 0); density: NULL, or float32 [m, steps] <- d.  d = sum over the
+ * neighbours of sigmoid(o) exp(-clamp(q, 0, 1e8) / 2), q = |U (p - mu)|^2 (a q that is NaN - an infinite entry of U
+ * from an extreme scale times a zero offset - counts as 1e8: no contribution; the reference gives NaN there), values
+ * above 1 set to 1.  A wave handles
+ * floor(64 / steps) rays.  TS_E_BADARG: as ts_extract_samples, a non-finite level, a NULL pointer (density may be).
+ * ts_extract_normals: points float32 [m,3] with their own neighbours knn int32 [m, TS_EXTRACT_K] -> normals float32
+ * [m,3] <- -grad d / |grad d| (the analytic gradient of d above; 0 where d was clamped to 1 or the gradient is 0).
+ * TS_E_BADARG: n < 1, m < 1, a NULL pointer.
+ * ts_extract_chunk_bytes: the bytes of one chunk of `rays` rays: ts_knn's workspace for rays * steps queries, then
+ * 256-byte aligned p_world, dirs, points (12 B per ray), seven 4-byte per-ray arrays, the samples and the k-NN
+ * distance and index outputs.  TS_E_BADARG: n < TS_EXTRACT_K, rays < 1, steps out of range, rays * steps >= 2^31. */
+#define TS_EXTRACT_K 16
+#define TS_EXTRACT_RECORD 10
+#define TS_EXTRACT_MAX_STEPS 64
+#define TS_EXTRACT_CAMERA_FLOATS 21
+#define TS_EXTRACT_PIX_REFERENCE 0
+#define TS_EXTRACT_PIX_SCREEN 1
+int ts_extract_pack(int32_t n, const float* means, const float* scales, const float* quats, const float* opacities,
+                    float* records, float* p_std, void* stream);
+int ts_extract_rays(int32_t m, const int64_t* pixel_ids, int32_t height, int32_t width, const float* depth,
+                    int32_t convention, const float* camera_host, const float* anchor, float* p_world, float* dirs,
+                    int32_t* valid, void* stream);
+int ts_extract_samples(int32_t n, int32_t m, int32_t steps, float extent_sigmas, const float* p_world, const float* dirs,
+                       const int32_t* nearest, const float* p_std_table, float* p_std, float* samples, void* stream);
+int ts_extract_march(int32_t n, int32_t m, int32_t steps, float extent_sigmas, float level, const float* samples,
+                     const int32_t* knn, const float* records, const float* p_world, const float* dirs,
+                     const float* p_std, const int32_t* valid, int32_t* keep, int32_t* first, float* t, float* points,
+                     float* density, void* stream);
+int ts_extract_normals(int32_t n, int32_t m, const float* points, const int32_t* knn, const float* records,
+                       float* normals, void* stream);
+int64_t ts_extract_chunk_bytes(int32_t n, int32_t rays, int32_t steps);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

@@ -30,6 +30,8 @@ SOURCES = [
     ("surface.hip", ["-ffp-contract=off"]),
     # density.hip: the density term and its gradient are compared with a float32 restatement of the reference
     ("density.hip", ["-ffp-contract=off"]),
+    # extract.hip: sample positions, densities and crossings are compared with a float64 restatement of the reference
+    ("extract.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

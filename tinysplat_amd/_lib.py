@@ -186,6 +186,13 @@ SIGNATURES = {
                                   c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ts_segment_sum_ws_bytes": (c_int64, [c_int64, c_int32]),
     "ts_segment_sum": (c_int32, [c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_extract_pack": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_extract_rays": (c_int32, [c_int32, _P, c_int32, c_int32, _P, c_int32, _P, _P, _P, _P, _P, _P]),
+    "ts_extract_samples": (c_int32, [c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_extract_march": (c_int32, [c_int32, c_int32, c_int32, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P]),
+    "ts_extract_normals": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "ts_extract_chunk_bytes": (c_int64, [c_int32, c_int32, c_int32]),
 }
 
 _lib = None

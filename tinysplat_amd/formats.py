@@ -139,3 +139,46 @@ def load_ply(path, device) -> SplatModel:
     return SplatModel(out["means"], out["colors_dc"], out["colors_rest"], out["scales"], out["quats"],
                       out["opacities"], active_sh_degree=deg_from_sh(k_rest + 1),
                       background=torch.zeros(3, device=dev))
+
+
+_POINT_FIELDS = ("x", "y", "z", "nx", "ny", "nz")
+
+
+def export_points_ply(points, path) -> None:
+    """An oriented point cloud as a binary little-endian PLY, ``x y z nx ny nz`` (float) per vertex: the input of
+    Poisson reconstruction tools.  ``points``: an ``extract.SurfacePoints`` (or anything with ``points`` [P,3] and
+    ``normals`` [P,3] or None: zero normals are written then), on any device."""
+    xyz = torch.as_tensor(points.points).detach().to("cpu", torch.float32)
+    nrm = getattr(points, "normals", None)
+    nrm = torch.zeros_like(xyz) if nrm is None else torch.as_tensor(nrm).detach().to("cpu", torch.float32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or nrm.shape != xyz.shape:
+        raise ValueError("points [P,3] and normals [P,3] expected")
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {xyz.shape[0]}",
+              *(f"property float {name}" for name in _POINT_FIELDS), "end_header"]
+    rows = np.ascontiguousarray(torch.cat((xyz, nrm), 1).numpy().astype("<f4"))
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(rows.tobytes())
+
+
+def read_points_ply(path):
+    """The inverse of ``export_points_ply`` -> ``(points float32 [P,3], normals float32 [P,3])`` on the CPU.  Reads
+    only what that function writes (six float properties in that order)."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    marker = b"end_header\n"
+    at = blob.find(marker)
+    if at < 0 or not blob.startswith(b"ply"):
+        raise ValueError("not a PLY file")
+    lines = [ln.strip() for ln in blob[:at].decode("ascii").split("\n") if ln.strip()]
+    if "format binary_little_endian 1.0" not in lines:
+        raise ValueError("only binary_little_endian PLY is supported")
+    elements = [ln.split() for ln in lines if ln.startswith("element")]
+    props = [ln.split() for ln in lines if ln.startswith("property")]
+    if len(elements) != 1 or elements[0][1] != "vertex" or \
+            [tuple(p[1:]) for p in props] != [("float", name) for name in _POINT_FIELDS]:
+        raise ValueError("expected one vertex element with float x y z nx ny nz")
+    n = int(elements[0][2])
+    rows = np.frombuffer(blob, dtype="<f4", count=n * 6, offset=at + len(marker)).reshape(n, 6)
+    t = torch.from_numpy(rows.astype(np.float32))
+    return t[:, :3].contiguous(), t[:, 3:].contiguous()

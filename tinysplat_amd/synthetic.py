@@ -115,8 +115,58 @@ def _rescale(self, factor: float) -> None:
     self.update_proj_matrix(self.fov_x, self.fov_y)
 
 
+def _project_points(self, points: torch.Tensor, screen_coordinates: bool = True,
+                    return_depth: bool = False) -> torch.Tensor:
+    """scene.py:138-163 without the ``clip`` branch (it reads attributes the reference's camera does not have):
+    world [M,3] -> NDC or screen coordinates, on the device of ``points``.  The reference's quirk is kept: x is
+    scaled by the height and y by the width, with integer image centres."""
+    assert points.shape[1] == 3
+    view = self.view_matrix.to(points.device)
+    proj = self.proj_matrix.to(points.device)
+    pts = points @ view[:3, :3].T + view[:3, 3]
+    pts = torch.cat([pts, torch.ones(pts.shape[0], device=points.device)[..., None]], dim=1)
+    pts = pts @ proj[:, :].T
+    if return_depth:
+        pts[:, :2] = pts[:, :2] / pts[:, 3].unsqueeze(1)
+    else:
+        pts = pts / pts[:, 3].unsqueeze(1)
+    pts = pts[:, :3]
+    if screen_coordinates:
+        c_x = self.width // 2
+        c_y = self.height // 2
+        pts[:, 0] = (0.5 * self.height * pts[:, 0]) - 0.5 + c_x
+        pts[:, 1] = 0.5 * self.width * pts[:, 1] - 0.5 + c_y
+    return pts
+
+
+def _backproject_points(self, points: torch.Tensor, scale_depth: bool = True,
+                        screen_coordinates: bool = True) -> torch.Tensor:
+    """scene.py:165-192: (x, y, depth) rows [M,3] -> world, on the device of ``points``, operation for operation
+    (the float32 ``inverse`` of the float32 ``P V`` included; x divided by the height and y by the width).  The
+    level-set extraction does this in csrc/extract.hip with the inverse taken in double."""
+    assert points.shape[1] == 3
+    full_inv = (self.proj_matrix @ self.view_matrix).inverse().to(points.device)
+    if scale_depth or screen_coordinates:
+        points = points.clone()
+    if scale_depth:
+        f1 = self.proj_matrix[2, 2]
+        f2 = self.proj_matrix[2, 3]
+        points[:, 2] = (f1 * points[:, 2] + f2) / points[:, 2]
+    if screen_coordinates:
+        c_x = self.width // 2
+        c_y = self.height // 2
+        points[:, 0] = (points[:, 0] + 0.5 - c_x) / self.height * 2
+        points[:, 1] = (points[:, 1] + 0.5 - c_y) / self.width * 2
+    points = torch.cat([points, torch.ones(points.shape[0], 1, device=points.device, dtype=points.dtype)], dim=1)
+    points = torch.matmul(points, full_inv.T)
+    points = points / points[:, 3][..., None]
+    return points[:, :3]
+
+
 PinholeCamera.update_proj_matrix = _update_proj_matrix
 PinholeCamera.rescale = _rescale
+PinholeCamera.project_points = _project_points
+PinholeCamera.backproject_points = _backproject_points
 
 
 def RGB2SH(rgb):
