@@ -300,9 +300,6 @@ __device__ __forceinline__ void walk_chunk(int g0, int g1, const float* __restri
 // every Gaussian its item range; the items are written out in windows of kItemCap and phase 2 hands consecutive
 // items to consecutive lanes.  Same decisions as walk_chunk (same TightTest members, same row_range), different
 // ORDER of the emits - which no caller depends on (LDS histogram / cursors; the per-tile sort follows).
-#ifndef TS_BIN_BALANCED
-#define TS_BIN_BALANCED 1
-#endif
 constexpr int kItemCap = 4096;                    // items per window
 constexpr int kStashWords = 11;                   // per Gaussian: 10 TightTest floats + (minx | maxx << 16)
 constexpr size_t kBalancedLds = (size_t)(kStashWords * kBinThreads + kItemCap + 32) * 4;      // static LDS it needs
@@ -599,9 +596,6 @@ __global__ __launch_bounds__(kBinThreads) void bin_scatter_coarse_kernel(
 #ifndef TS_FINE_AHEAD
 #define TS_FINE_AHEAD 8
 #endif
-#ifndef TS_FINE_REORDER
-#define TS_FINE_REORDER 1
-#endif
 constexpr int kFineThreads = TS_FINE_THREADS;
 constexpr int kFineAhead = TS_FINE_AHEAD;
 constexpr int kFinePass = kFineThreads * kFineAhead;     // entries handled together
@@ -619,7 +613,6 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_kernel(int num_
     const int t0 = blockIdx.x << kCoarseShift, t1 = min(num_tiles, t0 + kCoarseTiles);
     if ((int)threadIdx.x < t1 - t0) cursor[threadIdx.x] = tile_start[t0 + threadIdx.x];
     const int begin = tile_start[t0], end = tile_start[t1];
-#if TS_FINE_REORDER
     __shared__ int hist[kCoarseTiles], loff[kCoarseTiles + 1], gbase[kCoarseTiles];
     __shared__ int ids[kFinePass];
     __shared__ unsigned char tiles[kFinePass];
@@ -678,19 +671,6 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_kernel(int num_
         }
         __syncthreads();                                              // ids / tiles / loff are rewritten by the next pass
     }
-#else
-    __syncthreads();
-    for (int j = begin + threadIdx.x; j < end; j += kFineAhead * kFineThreads) {
-        unsigned int w[kFineAhead];
-#pragma unroll
-        for (int u = 0; u < kFineAhead; ++u)
-            if (j + u * kFineThreads < end) w[u] = (unsigned int)scratch[j + u * kFineThreads];
-#pragma unroll
-        for (int u = 0; u < kFineAhead; ++u)
-            if (j + u * kFineThreads < end)
-                bucket_ids[atomicAdd(&cursor[w[u] >> kCoarseIdBits], 1)] = (int)(w[u] & ((1u << kCoarseIdBits) - 1u));
-    }
-#endif
 }
 
 // ---- per-tile bitonic sort ---------------------------------------------------------------------
@@ -1073,7 +1053,7 @@ int ts_bin_scatter(int32_t n, const float* xys, const int32_t* radii, const floa
         const int groups = (nt + kCoarseTiles - 1) >> kCoarseShift;
         // load-balanced walk where the caller says a Gaussian covers many tiles (ts_camera.hints & TS_HINT_BALANCED_WALK):
         // config 5 (16 bounding-box tiles per Gaussian) coarse hop 369 -> 274 us; config 3 (6 tiles) 51 -> 56 us
-        if (TS_BIN_BALANCED && (cam->hints & TS_HINT_BALANCED_WALK))
+        if (cam->hints & TS_HINT_BALANCED_WALK)
             hipLaunchKernelGGL(bin_scatter_coarse_kernel<true>, dim3(chunks), dim3(kBinThreads),
                                (size_t)groups * sizeof(int), (hipStream_t)stream, n, chunk, xys, radii,
                                reinterpret_cast<const float4*>(splats), *cam, nt, bin_ws, tile_start, scratch);

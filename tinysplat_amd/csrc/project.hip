@@ -26,35 +26,19 @@ constexpr int kThreads = 256;
 #ifndef TS_SH_THREADS_BWD
 #define TS_SH_THREADS_BWD 256
 #endif
-#ifndef TS_NT_STORE
 // Write-once gradient streams (192 N bytes of v_colors_rest per frame) leave with NON-TEMPORAL stores: they do
 // not displace the coefficient rows that the next frame's forward reads from the 256 MB Infinity Cache
-// (measured on config 3: sh_colors_bwd 51 -> 47 us and colors_pack_fwd 73 -> 66 us).  TS_NT_STORE=0 for A/B timing.
-#define TS_NT_STORE 1
-#endif
+// (measured on config 3: sh_colors_bwd 51 -> 47 us and colors_pack_fwd 73 -> 66 us).
 typedef float f4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store4(float4* p, float a, float b, float c, float d) {
-    if (TS_NT_STORE) {
-        f4v v = {a, b, c, d};
-        __builtin_nontemporal_store(v, reinterpret_cast<f4v*>(p));
-    } else {
-        *p = make_float4(a, b, c, d);
-    }
+    f4v v = {a, b, c, d};
+    __builtin_nontemporal_store(v, reinterpret_cast<f4v*>(p));
 }
-#ifndef TS_NT_GRADS
-#define TS_NT_GRADS 0        // project_bwd's three gradient streams non-temporal (A/B knob)
-#endif
 constexpr int kShThreadsFwd = TS_SH_THREADS_FWD, kShThreadsBwd = TS_SH_THREADS_BWD;
-#ifndef TS_NT_LOAD
 // the 180-byte coefficient rows are read once per frame: non-temporal loads (colors_pack_fwd 64 -> 56 us on config 3)
-#define TS_NT_LOAD 1
-#endif
 __device__ __forceinline__ float4 load4_stream(const float4* p) {
-    if (TS_NT_LOAD) {
-        const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    }
-    return *p;
+    const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
 }
 
 #include "project_inputs.h"
@@ -177,20 +161,12 @@ __global__ __launch_bounds__(kThreads) void project_bwd_kernel(
         }
         return;
     }
-#if TS_NT_GRADS
-    __builtin_nontemporal_store(g.v_mean[0], v_means3d + 3 * i); __builtin_nontemporal_store(g.v_mean[1], v_means3d + 3 * i + 1);
-    __builtin_nontemporal_store(g.v_mean[2], v_means3d + 3 * i + 2);
-    __builtin_nontemporal_store(g.v_scale[0], v_scales + 3 * i); __builtin_nontemporal_store(g.v_scale[1], v_scales + 3 * i + 1);
-    __builtin_nontemporal_store(g.v_scale[2], v_scales + 3 * i + 2);
-    store4(reinterpret_cast<float4*>(v_quats) + i, g.v_quat[0], g.v_quat[1], g.v_quat[2], g.v_quat[3]);
-#else
     v_means3d[3 * i] = g.v_mean[0]; v_means3d[3 * i + 1] = g.v_mean[1];
     v_means3d[3 * i + 2] = g.v_mean[2];
     v_scales[3 * i] = g.v_scale[0]; v_scales[3 * i + 1] = g.v_scale[1];
     v_scales[3 * i + 2] = g.v_scale[2];
     reinterpret_cast<float4*>(v_quats)[i] =
         make_float4(g.v_quat[0], g.v_quat[1], g.v_quat[2], g.v_quat[3]);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -57,7 +57,7 @@ namespace {
 #define TS_FWD_MIN_WAVES_RGB 5         // the 16x16, three-channel forward kernel keeps its five waves per SIMD (<= 96 VGPRs)
 #endif
 #ifndef TS_FWD_MIN_WAVES_RGBD
-#define TS_FWD_MIN_WAVES_RGBD 5        // ... and so does the four-channel one since the next chunk's records land in LDS (TS_LDS_DMA):
+#define TS_FWD_MIN_WAVES_RGBD 5        // ... and so does the four-channel one since the next chunk's records land in LDS (dma_record):
                                        // the hybrid instantiation spills 160 bytes at chunk level, raster_fwd 327 -> 304 us (round 5)
 #endif
 #ifndef TS_BWD_MIN_WAVES
@@ -65,7 +65,7 @@ namespace {
 #endif
 #ifndef TS_BWD_MIN_WAVES_16
 #define TS_BWD_MIN_WAVES_16 5          // the 16x16 backward kernels at five waves per SIMD (96 VGPRs: 5 - 11 dwords spilled at
-#endif                                 // chunk level with TS_LDS_DMA; they took 107 / 115).  Round 5: raster_bwd 465 -> 450 us
+#endif                                 // chunk level with dma_record; they took 107 / 115).  Round 5: raster_bwd 465 -> 450 us
 
 #ifndef TS_ABLATE
 #define TS_ABLATE 0                    // timing experiments only (results are wrong when != 0): 3 = no per-entry loop at all
@@ -160,12 +160,10 @@ struct WaveClock {
 #define TS_LDS_PAD_DECL() ((void)0)
 #endif
 
-// TS_LDS_DMA: the packed records of the NEXT chunk travel from global memory straight into LDS
+// The packed records of the NEXT chunk travel from global memory straight into LDS
 // (global_load_lds_dwordx4: 16 bytes per lane to base + lane * 16) instead of through twelve VGPRs that stay live
-// across the whole chunk - the registers that kept raster_bwd at four and raster_fwd at five waves per SIMD.
-#ifndef TS_LDS_DMA
-#define TS_LDS_DMA 1                   // (round 4: no gain on its own; round 5: what lets raster_bwd fit five waves per SIMD)
-#endif
+// across the whole chunk - the registers that kept raster_bwd at four and raster_fwd at five waves per SIMD
+// (round 4: no gain on its own; round 5: what lets raster_bwd fit five waves per SIMD).
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 __device__ __forceinline__ void dma_record(const float4* __restrict__ splats, int g, float4* raw) {
@@ -177,31 +175,12 @@ __device__ __forceinline__ void dma_record(const float4* __restrict__ splats, in
 #define TS_DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #define TS_LDS_WAIT() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
-#ifndef TS_FLAG_WITH_ROW
-#define TS_FLAG_WITH_ROW (CH == 4)     // measured: four channels 561 -> 544 us, three channels 507 -> 512 us
-#endif
-#ifndef TS_SELECT_SGPR
-#define TS_SELECT_SGPR 1
-#endif
-#ifndef TS_BWD_EXEC_MASK
-#define TS_BWD_EXEC_MASK 0             // measured (round 5): the body's second half under EXEC = valid lanes: 450 -> 459 us
-#endif
-#ifndef TS_BWD_EARLY_RECORD
-#define TS_BWD_EARLY_RECORD 0          // measured (round 5): next record requested in front of the row flush: 451 -> 458 - 465 us
-#endif
-
-#ifndef TS_NT_ROWS
-#define TS_NT_ROWS 0                    // gradient rows written (raster_bwd) / read (reduce_partials) non-temporally
-#endif
-
 #ifndef TS_REDUCE_AHEAD
 #define TS_REDUCE_AHEAD 4                // rows of a Gaussian requested together by reduce_partials
 #endif
 
-#ifndef TS_RASTER_WAVES
-#define TS_RASTER_WAVES 4
-#endif
-constexpr int kWaves = TS_RASTER_WAVES;   // tiles (= waves) per workgroup; waves never synchronise
+constexpr int kWaves = 4;                 // tiles (= waves) per workgroup; waves never synchronise (COOPERATIVE TILES: the four
+                                          // waves of a workgroup composite the four 8x8 blocks of one tile)
 constexpr int kThreads = 64 * kWaves;
 // float4s per gradient row slot.  (Round 4 tried 64-byte slots, whole-sector stores: WRITE_SIZE 218 -> 221 MB,
 // reduce_partials 57 -> 60 us - the 1.9x "write amplification" of round 3 is the row's FLAG BYTE, a 32-byte sector
@@ -246,11 +225,7 @@ __device__ __forceinline__ float sigma_l2(float hA, float B, float hC, float neg
 // every XCD has a private 4 MiB L2.  Handing XCD x the x-th contiguous eighth of the tile groups
 // (a band of tile rows) keeps the packed-record gathers of neighbouring tiles, which share most of
 // their Gaussians, in one L2.  Placement only affects speed.  Grid = 8 * ceil(groups / 8).
-#ifndef TS_XCD_MAP
-#define TS_XCD_MAP 1
-#endif
 __device__ __forceinline__ int xcd_tile_group(int num_groups) {
-    if (!TS_XCD_MAP) return (int)blockIdx.x;
     const int per_xcd = (num_groups + 7) >> 3;
     return (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
 }
@@ -401,31 +376,13 @@ constexpr int kSegMax = 8;
 // >= list_len where the list has fewer segments; boundary 0 is the start.  Integer arithmetic on the list length
 // alone: both passes (and the four waves of a split forward launch) compute the same values.  The FRONT segments are
 // the expensive ones - every pixel is still alive there, late in the list most (Gaussian, block) pairs are culled -
-// so the boundaries are not equidistant (TS_SEG_SHAPE: 0 = equal counts, 1 = halfway, 2 = quadratic).
-#ifndef TS_SEG_SHAPE
-#define TS_SEG_SHAPE 2
-#endif
-#ifndef TS_FWD_LATE_PREFETCH
-#define TS_FWD_LATE_PREFETCH 0
-#endif
-#ifndef TS_FWD_CUT_FIRST
-#define TS_FWD_CUT_FIRST 1
-#endif
-#ifndef TS_LOC_LDS
-#define TS_LOC_LDS 0                   // 1: the per-segment sums of a whole-tile wave in LDS (LocLds) instead of registers: slower
-#endif
-#ifndef TS_SEG_CAP_CHUNKS
-#define TS_SEG_CAP_CHUNKS 0
-#endif
+// so the boundaries are not equidistant: boundary k of S lies at (k / S)^2 of the list's chunks.
 __device__ __forceinline__ int seg_bound(int list_len, int S, int s) {
     if (S <= 1 || list_len < kSegMinList) return 0x7fffff00;
-    const int C = TS_SEG_CAP_CHUNKS > 0 ? min((list_len + 63) >> 6, TS_SEG_CAP_CHUNKS) : (list_len + 63) >> 6;
+    const int C = (list_len + 63) >> 6;
     int b = 0;
     for (int k = 1; k <= s; ++k) {                 // S <= 8: a few scalar operations
-        int f;
-        if (TS_SEG_SHAPE == 0) f = (C * k + S - 1) / S;
-        else if (TS_SEG_SHAPE == 1) f = (C * (k * k + k * S) + 2 * S * S - 1) / (2 * S * S);
-        else f = (C * k * k + S * S - 1) / (S * S);
+        const int f = (C * k * k + S * S - 1) / (S * S);
         b = max(f, b + 1);                         // strictly increasing, at least one chunk per segment
     }
     return b << 6;
@@ -492,9 +449,7 @@ __device__ __forceinline__ void ckpt_store(float* rec, int k, int lane, float T,
 // positive-definite conic with opacity <= 0.99 (bit 4 of the staged mask).
 // Per-segment colour sums of the forward pass (LIST SEGMENTS): what the entries of the CURRENT segment contributed to
 // each pixel, kept beside the running sum.  LocRegs<CH, N>: N sets in registers (0 = none; 1 = a wave of a split
-// launch owns ONE block).  LocLds<CH>: one set per block of a whole-tile wave in LDS, accumulated with ds_add_f32 -
-// twelve more live registers cost the forward kernel its fifth wave per SIMD (122 VGPRs, or 31 spilled), the LDS
-// form costs three multiplies and three LDS atomics per body of a cut tile and no register.
+// launch owns ONE block; NB = a whole-tile wave, twelve more live registers that are spilled at the five-wave budget).
 template <int CH, int N>
 struct LocRegs {
     static constexpr bool on = N > 0;
@@ -514,29 +469,8 @@ struct LocRegs {
         for (int c = 0; c < CH; ++c) D[c] = v[N == 1 ? 0 : k][c];
     }
 };
-template <int CH, int NB>
-struct LocLds {
-    static constexpr bool on = true;
-    float4* p;                                       // this lane's sums of block 0; block k at p[64 k] (16 bytes per lane)
-    __device__ __forceinline__ void zero() {
-#pragma unroll
-        for (int k = 0; k < NB; ++k) p[64 * k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __device__ __forceinline__ void add(int k, const float (&col)[CH], float vis) {
-        float4 v = p[64 * k];
-        v.x = __builtin_fmaf(col[0], vis, v.x); v.y = __builtin_fmaf(col[1], vis, v.y); v.z = __builtin_fmaf(col[2], vis, v.z);
-        if (CH == 4) v.w = __builtin_fmaf(col[CH - 1], vis, v.w);
-        p[64 * k] = v;
-    }
-    __device__ __forceinline__ void get(int k, float (&D)[CH]) const {
-        const float4 v = p[64 * k];
-        D[0] = v.x; D[1] = v.y; D[2] = v.z;
-        if (CH == 4) D[CH - 1] = v.w;
-    }
-};
-
-// The per-pixel update of the forward pass behind the exponent, hand-scheduled (round 6, TS_FWD_ASM).  The compiler's
-// code for the C++ form below spent 5 wait states (s_nop 0 / 1 / 1) and one register copy on every block body:
+// The per-pixel update of the forward pass behind the exponent, hand-scheduled (round 6).  The compiler's
+// code for the C++ form (written out beside fwd_update) spent 5 wait states (s_nop 0 / 1 / 1) and one register copy on every block body:
 // it folds the negation of `-ae` and the `-|T|` of the stop into v_cndmask_b32_e64 source modifiers, and a VOP3 select
 // that reads vcc as a CONSTANT needs two wait states behind the v_cmp that wrote it (an e32 select, which reads vcc
 // implicitly, needs none); the new T was built in a temporary and moved.  Here: both value selects are e32 (the
@@ -545,13 +479,9 @@ struct LocLds {
 // stands three instructions behind its compare, and T is updated in place: 21 VALU issues + 1 wait state per body where
 // the compiler had 21 + 5 (measured: no change of the launch - a wait state is an issue slot of one wave that its four
 // neighbours fill; what the launch pays for is the pipe cost of the 21 instructions, 56 cycles: DESIGN.md section 4).  Same operations on the same operands: image, final_Ts and final_index are bit for bit the
-// C++ form's (tests/test_gpu_parity.py compares the frame with the oracle; tools/variant_check.py the two builds).
-#ifndef TS_FWD_ASM
-#define TS_FWD_ASM 1
-#endif
+// C++ form's (tests/test_gpu_parity.py compares the frame with the oracle).
 // ae = exp2(-sgl) >= 1/255 ? exp2(-sgl) : 0
 __device__ __forceinline__ float fwd_alpha(float sgl) {
-#if TS_FWD_ASM
     float a, ae;
     asm("v_exp_f32_e64 %0, -%2\n\t"
         "s_nop 0\n\t"
@@ -561,10 +491,6 @@ __device__ __forceinline__ float fwd_alpha(float sgl) {
         : "v"(sgl), "s"(ts::kAlphaMin)
         : "vcc");
     return ae;
-#else
-    const float a = __builtin_amdgcn_exp2f(-sgl);
-    return a >= ts::kAlphaMin ? a : 0.0f;
-#endif
 }
 // the lean path (no clamp, no sigma >= 0 test between the two): ONE block, so that the compiler puts no wait state of
 // its own between two asm statements
@@ -590,10 +516,11 @@ __device__ __forceinline__ float fwd_alpha_update(float sgl, float& T, int& fidx
         : "vcc");
     return vis;
 }
-// T, fidx and the first three channels of acc updated for one pixel; returns vis (the weight of the colour)
+// T, fidx and the first three channels of acc updated for one pixel; returns vis (the weight of the colour):
+//     nT = fma(-ae, T, T);  Tn = nT <= kTEps ? -|T| : nT   (the stopping Gaussian is not composited)
+//     vis = |T| - |Tn|;  acc += colour * vis;  fidx = vis > 0 ? idx : fidx;  T = Tn
 __device__ __forceinline__ float fwd_update(float ae, float& T, int& fidx, int idx, float& a0, float& a1, float& a2,
                                             float c0, float c1, float c2) {
-#if TS_FWD_ASM
     float nT, d, vis;
     asm("v_fma_f32 %0, -%8, %3, %3\n\t"                    // nT = T - ae T
         "v_sub_f32_e32 %1, %3, %0\n\t"                      // d = T - nT
@@ -609,65 +536,12 @@ __device__ __forceinline__ float fwd_update(float ae, float& T, int& fidx, int i
         : "v"(ae), "v"(c0), "v"(c1), "v"(c2), "v"(idx), "s"(ts::kTEps)
         : "vcc");
     return vis;
-#else
-    const float nT = __builtin_fmaf(-ae, T, T);
-    const float Tn = nT <= ts::kTEps ? -__builtin_fabsf(T) : nT;   // the stopping Gaussian is not composited
-    const float vis = __builtin_fabsf(T) - __builtin_fabsf(Tn);
-    a0 = __builtin_fmaf(c0, vis, a0); a1 = __builtin_fmaf(c1, vis, a1); a2 = __builtin_fmaf(c2, vis, a2);
-    fidx = vis > 0.0f ? idx : fidx;
-    T = Tn;
-    return vis;
-#endif
-}
-
-// FINISHED PIXELS AS A SCALAR MASK (round 6, TS_FWD_ALIVE).  With instructions priced per class a
-// forward body is 56 pipe cycles of which the three compare -> select decisions are 21: alpha >= 1/255, the stop test
-// with its TWO selects (vis, T), and "was it composited" for fidx.  A pixel stops ONCE in its life, and "finished" was
-// kept in the sign of T, which every body had to restore.  Now a block's unfinished pixels are a 64-bit mask in SGPRs:
-//   m1 = ballot(alpha >= 1/255) & alive            (scalar and)          ae = m1 ? alpha : 0
-//   nT = T - ae T,  d = T - nT  (= vis: 0 wherever ae = 0),   go = ballot(!(nT <= kTEps))
-//   common case, no pixel of the block stops in this body:  acc += colour * d;  fidx = m1 ? idx : fidx;  T = nT
-// - no select for vis or T, no compare for fidx (m1 is the answer): 46 cycles.  A body in which a pixel stops (wave-uniform
-// scalar branch) applies the selects and clears the pixel's alive bit.  Same operations on the same operands for every
-// pixel that is still alive, no update of the others: image, final_Ts, final_index bit for bit.
-// MEASURED (round 6, profiles/r06h_fwd_alive_mask.txt): bit for bit, and NO gain - raster_fwd 298 / 302 us against 295 / 300
-// (config 3), 311 against 307 (RGB + depth), 628 against 619 (config 5): the 8 pipe cycles a body loses are paid back by
-// two more scalar instructions and a v_cmp -> s_and -> select dependency in every body's chain.  Off; kept as a knob.
-#ifndef TS_FWD_ALIVE
-#define TS_FWD_ALIVE 0
-#endif
-template <int CH, bool LOC>
-__device__ __forceinline__ void fwd_update_alive(float a, mask64 m1, float& T, mask64& alive, int& fidx, int idx,
-                                                 float (&acc)[CH], const float (&col)[CH], float (&loc)[CH]) {
-#pragma clang fp contract(off)
-    float ae;
-    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(ae) : "v"(a), "s"(m1));
-    float nT = __builtin_fmaf(-ae, T, T);
-    float d = T - nT;
-    const mask64 go = TS_BALLOT(!(nT <= ts::kTEps));
-    if (__builtin_expect(~go != 0ull, 0)) {
-        // a pixel of this block stops here (once per pixel): d, nT and m1 are corrected IN PLACE (asm with "+v": the
-        // common path below must not be re-emitted with its values in fresh registers and copied at the join)
-        asm("v_cndmask_b32_e64 %0, 0, %0, %1" : "+v"(d) : "s"(go));
-        asm("v_cndmask_b32_e64 %0, %1, %0, %2" : "+v"(nT) : "v"(T), "s"(go));
-        m1 &= go;
-        alive &= go;
-    }
-    asm volatile("" : "+v"(d), "+v"(nT), "+s"(m1));
-#pragma unroll
-    for (int c = 0; c < CH; ++c) acc[c] = __builtin_fmaf(col[c], d, acc[c]);
-    if (LOC) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) loc[c] = __builtin_fmaf(col[c], d, loc[c]);
-    }
-    asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(fidx) : "v"(idx), "s"(m1));
-    T = nT;
 }
 
 template <int CH, bool GENERAL, int NBX, class Loc>
 __device__ __forceinline__ void fwd_chunk(const float4* __restrict__ lds, int cnt, const float (&fpx)[NBX],
                                           const float (&fpy)[2], float (&T)[2 * NBX], int (&fidx)[2 * NBX],
-                                          float (&acc)[2 * NBX][CH], Loc& loc, mask64 (&alive)[2 * NBX] TS_SEG_PARAM) {
+                                          float (&acc)[2 * NBX][CH], Loc& loc TS_SEG_PARAM) {
 #pragma clang fp contract(off)          // as in bwd_chunk: both instantiations must round alike
     constexpr bool LOC = Loc::on;
     TS_WORK(0, cnt);
@@ -701,33 +575,18 @@ __device__ __forceinline__ void fwd_chunk(const float4* __restrict__ lds, int cn
             // Every decision below is ONE compare feeding ONE select, with no scalar mask arithmetic in between:
             // a v_cmp -> s_and / s_xor -> v_cndmask chain costs a wave 36 cycles and a select on a vcc that the
             // scalar unit wrote 19 (tools/micro/lat_bench.hip), a compare -> select pair 11.
-            float vis;
-            if constexpr (TS_FWD_ALIVE && !Loc::on) {
-                // (segment sums - Loc - keep the sign form: the cut tiles of a hybrid launch are a sixth of the frame)
-                const float a = __builtin_amdgcn_exp2f(-sgl);
-                mask64 m1 = TS_BALLOT(a >= ts::kAlphaMin) & alive[k];
-                float ag = a;
-                if (GENERAL) {
-                    ag = fminf(ts::kAlphaMax, a);
-                    m1 &= TS_BALLOT(sgl >= neg_lo);                   // sigma >= 0
-                }
-                float no_loc_[CH];
-                fwd_update_alive<CH, false>(ag, m1, T[k], alive[k], fidx[k], idx, acc[k], col, no_loc_);
-                continue;
-            }
-            if (TS_FWD_ASM && !GENERAL) {
-                vis = fwd_alpha_update(sgl, T[k], fidx[k], idx, acc[k][0], acc[k][1], acc[k][2], col[0], col[1], col[2]);
-            } else {
-            float ae = fwd_alpha(sgl);                                // alpha >= 1/255 ? alpha : 0
-            if (GENERAL) {
-                ae = fminf(ts::kAlphaMax, ae);
-                ae = sgl >= neg_lo ? ae : 0.0f;                       // sigma >= 0
-            }
             // A finished pixel (T < 0) needs no test of its own: nT = T (1 - ae) stays negative, `stop` fires and
             // -|T| puts T back; vis is 0.  An unfinished pixel always has T > kTEps (it would have stopped
             // otherwise), so with ae = 0 (Gaussian below 1/255) nT = T and `stop` cannot fire: no `& ok` needed.
             // composited <=> alpha >= 1/255 and not stopped <=> vis = alpha T > 0 (alpha >= 1/255, T > 1e-4)
-            vis = fwd_update(ae, T[k], fidx[k], idx, acc[k][0], acc[k][1], acc[k][2], col[0], col[1], col[2]);
+            float vis;
+            if (!GENERAL) {
+                vis = fwd_alpha_update(sgl, T[k], fidx[k], idx, acc[k][0], acc[k][1], acc[k][2], col[0], col[1], col[2]);
+            } else {
+                float ae = fwd_alpha(sgl);                            // alpha >= 1/255 ? alpha : 0
+                ae = fminf(ts::kAlphaMax, ae);
+                ae = sgl >= neg_lo ? ae : 0.0f;                       // sigma >= 0
+                vis = fwd_update(ae, T[k], fidx[k], idx, acc[k][0], acc[k][1], acc[k][2], col[0], col[1], col[2]);
             }
             if (CH == 4) acc[k][CH - 1] = __builtin_fmaf(col[CH - 1], vis, acc[k][CH - 1]);
             if (LOC) loc.add(k, col, vis);      // the same contribution summed per list segment (LIST SEGMENTS)
@@ -752,23 +611,11 @@ __device__ __forceinline__ void fwd_chunk(const float4* __restrict__ lds, int cn
 // Every pixel sees the same entries in the same order through the same arithmetic: image, final_Ts and final_index
 // are bitwise those of the whole-tile waves.
 #define TS_CAM_COOP16(cam) (((cam).hints >> 16) & 15)
-#ifndef TS_COOP
-#define TS_COOP (TS_RASTER_WAVES == 4)
-#endif
+static_assert(kWaves == 4, "a cooperative workgroup is one wave per 8x8 block of a 16x16 tile");
 #ifndef TS_COOP_AHEAD
 #define TS_COOP_AHEAD 4
 #endif
 constexpr int kCoopAhead = TS_COOP_AHEAD;
-// TS_SEGS_COOP=1 (measured, not the default): in a launch that keeps boundary state (hybrid launch, S > 1) the CUT tiles
-// are the cooperative ones - a cooperative wave has one pixel per lane, so the per-segment colour sums are three
-// registers there, where they are twelve (spilled at the five-wave budget) in the whole-tile waves of such a launch;
-// C16 is ignored then.  The whole-tile waves lose their spills (96 VGPRs + 92 bytes -> 94), but the boundary records
-// and the three extra FMAs per body then sit in the items that END the launch instead of the ones that start it:
-// raster_fwd 290 -> 300 us on config 3.
-#ifndef TS_SEGS_COOP
-#define TS_SEGS_COOP 0
-#endif
-constexpr bool kSegsCoop = TS_SEGS_COOP && TS_COOP;
 // internal (set by ts_raster_fwd* in the camera copy it hands to the kernel, never by callers): the launch asked for
 // TS_RASTER_SPLIT_BLOCKS under TS_HINT_COOP_SPLIT - every tile (S > 1: every cut tile) is a cooperative workgroup
 constexpr int kHintCoopAll = 1 << 21;
@@ -785,22 +632,22 @@ __host__ __device__ __forceinline__ FwdPlan fwd_plan(int num_tiles, int hints, b
     p.per_xcd = (groups + 7) >> 3;
     const int w16 = (hints >> 12) & 15, c16 = (hints >> 16) & 15;
     const CutTiles m = cut_tiles(num_tiles, hints);           // (band = kWaves * per_xcd tiles for kWaves == 4)
-    if (TS_COOP && coop_ok && (hints & kHintCoopAll) && !segs) {      // a small launch, no boundary state: every tile
+    if (coop_ok && (hints & kHintCoopAll) && !segs) {      // a small launch, no boundary state: every tile
         p.coop = p.per_xcd;
         p.coop_lo = 0;
         p.descending = false;
         return p;
     }
-    if (segs && coop_ok && (kSegsCoop || (TS_COOP && (hints & kHintCoopAll)))) {
+    if (segs && coop_ok && (hints & kHintCoopAll)) {
         p.coop = (m.band - m.whole) / kWaves;                 // W16 = 0: every tile is cut
         p.coop_lo = m.whole / kWaves;
         p.descending = false;
         return p;
     }
-    p.coop = (TS_COOP && coop_ok) ? (p.per_xcd * c16) / 16 : 0;
+    p.coop = coop_ok ? (p.per_xcd * c16) / 16 : 0;
     if (segs) p.coop = w16 > 0 ? min(p.coop, m.whole / kWaves) : 0;     // a cut tile keeps its boundary state: whole-tile wave
     p.coop_lo = 0;
-    p.descending = (segs && TS_FWD_CUT_FIRST && w16 > 0) || p.coop > 0;
+    p.descending = (segs && w16 > 0) || p.coop > 0;
     return p;
 }
 
@@ -816,14 +663,12 @@ __device__ __forceinline__ void fwd_body1(const float4 r0, const float4 r1, cons
     if (CH == 4) col[CH - 1] = r2.y;
     const float sgl = sigma_l2(r0.z, r0.w, r1.x, neg_lo, r0.x - fpx, r0.y - fpy);
     float vis;
-    if (TS_FWD_ASM && !GENERAL) {
+    if (!GENERAL) {
         vis = fwd_alpha_update(sgl, T, fidx, idx, acc[0], acc[1], acc[2], col[0], col[1], col[2]);
     } else {
         float ae = fwd_alpha(sgl);
-        if (GENERAL) {
-            ae = fminf(ts::kAlphaMax, ae);
-            ae = sgl >= neg_lo ? ae : 0.0f;
-        }
+        ae = fminf(ts::kAlphaMax, ae);
+        ae = sgl >= neg_lo ? ae : 0.0f;
         vis = fwd_update(ae, T, fidx, idx, acc[0], acc[1], acc[2], col[0], col[1], col[2]);
     }
     if (CH == 4) acc[CH - 1] = __builtin_fmaf(col[CH - 1], vis, acc[CH - 1]);
@@ -1170,21 +1015,21 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     const float* __restrict__ background, float* __restrict__ out_img, float* __restrict__ out_depth,
     float* __restrict__ final_Ts, int* __restrict__ final_index, const int clamp_rgb,
     unsigned char* __restrict__ clamp_mask, int* sv_id, int* sv_meta, int* sv_cnt) {
-    static_assert(!SURV || (!SPLIT && NBX == 2 && !WL && TS_LDS_DMA && !kSegsCoop), "survivor lists: one wave per 16x16 tile");
+    static_assert(!SURV || (!SPLIT && NBX == 2 && !WL), "survivor lists: one wave per 16x16 tile");
     constexpr int NB = 2 * NBX;
     TS_LDS_PAD_DECL();
     __shared__ float4 lds_all[kWaves][64 * 3];
     __shared__ float4 rect_all[kWaves][NB];
-    __shared__ float4 raw_all[TS_LDS_DMA ? kWaves : 1][3 * 64];      // landing zone of the next chunk's records
+    __shared__ float4 raw_all[kWaves][3 * 64];                       // landing zone of the next chunk's records
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int units = SPLIT ? NB * num_tiles : num_tiles;
     int unit = xcd_tile_group((units + kWaves - 1) / kWaves) * kWaves + wave;
-    constexpr bool kCoop = TS_COOP && !SPLIT && NBX == 2 && !WL;
+    constexpr bool kCoop = !SPLIT && NBX == 2 && !WL;
     if constexpr (!SPLIT && NBX == 2 && !WL) {
         // hybrid launch: the cut tiles of a band - the ones that also keep their boundary state, the longest items of
         // this launch - are handed out FIRST here (the backward launch hands them out last, as small items); the
         // tiles handed out last - C16 / 16 of a band from its start - are composited by a workgroup each (COOPERATIVE
-        // TILES; TS_SEGS_COOP=1: the cut tiles themselves)
+        // TILES)
         const FwdPlan pl = fwd_plan(num_tiles, cam.hints, SEGS && final_Ts != nullptr && TS_CAM_SEGS(cam) > 1, kCoop);
         const int xcd = (int)(blockIdx.x & 7), slot = (int)(blockIdx.x >> 3);
         if (slot < pl.per_xcd - pl.coop) {
@@ -1221,7 +1066,6 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
 
     // T > 0: transmittance of an unfinished pixel; T < 0: finished or outside, final value |T|
     float T[NB], acc[NB][CH];
-    mask64 alive[NB];
     int fidx[NB];
     bool inside[NB];
     int live = 0;                                   // blocks that still have unfinished pixels
@@ -1229,7 +1073,6 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     for (int k = 0; k < NB; ++k) {
         inside[k] = (px0 + 8 * (k % NBX) < W) && (py0 + 8 * (k / NBX) < H) && (!SPLIT || k == only);
         T[k] = inside[k] ? 1.0f : -1.0f;
-        alive[k] = TS_BALLOT(inside[k]);              // (TS_FWD_ALIVE: the unfinished pixels of block k)
         fidx[k] = 0;
 #pragma unroll
         for (int c = 0; c < CH; ++c) acc[k][c] = 0.0f;
@@ -1270,26 +1113,18 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     // c+1 are in flight while chunk c is composited (two dependent gathers = ~2 us of latency
     // that a wave with ~3 co-resident waves per SIMD cannot hide otherwise).
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4* raw = raw_all[TS_LDS_DMA ? wave : 0];
-#if !TS_LDS_DMA
-    float4 n0 = zero4, n1 = zero4, n2 = zero4;
-#endif
+    float4* raw = raw_all[wave];
     int id_next = 0;
     if (range.x + lane < range.y) {
         const int g = ids[range.x + lane];
-#if TS_LDS_DMA
         dma_record(splats, g, raw);
-#else
-        n0 = splats[3 * (size_t)g]; n1 = splats[3 * (size_t)g + 1]; n2 = splats[3 * (size_t)g + 2];
-#endif
     }
     if (range.x + 64 + lane < range.y) id_next = ids[range.x + 64 + lane];
 
     // list segments: this pass leaves the per-pixel state at the segment boundaries for the backward pass - in a SPLIT
     // launch for every tile (each of the four waves keeps the pixels of its block), with one wave per tile for the CUT
     // tiles of a hybrid launch (or, W16 = 0, for all of them)
-    // (one wave per tile, TS_SEGS_COOP: the cut tiles are cooperative workgroups - no whole-tile wave keeps boundary state)
-    constexpr bool kSegsF = SEGS && NBX == 2 && !WL && (SPLIT || !kSegsCoop);
+    constexpr bool kSegsF = SEGS && NBX == 2 && !WL;
     const int S_seg = max(1, min(TS_CAM_SEGS(cam), kSegMax));
     int ck_block = -1;                                               // the tile's checkpoint block, -1 = none
     if (kSegsF && final_Ts != nullptr && S_seg > 1 && range.y - range.x >= kSegMinList)
@@ -1301,16 +1136,8 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     int ck = 1;                                                      // its number (1 .. S-1)
     // colour the entries of the CURRENT segment contributed (the running sum `acc` rounds at the magnitude of the whole
     // pixel colour: differences of it would know what lies behind a boundary only to that rounding)
-    constexpr bool kLocLds = kSegsF && !SPLIT && TS_LOC_LDS;
-    using LocT = std::conditional_t<kLocLds, LocLds<CH, NB>, LocRegs<CH, !kSegsF ? 0 : (SPLIT ? 1 : NB)>>;
-    LocT loc;
-    if constexpr (kLocLds) {
-        __shared__ float4 loc_all[kWaves][kLocLds ? NB * 64 : 1];
-        loc.p = loc_all[wave] + lane;
-        if (seg_on) loc.zero();
-    } else {
-        loc.zero();
-    }
+    LocRegs<CH, !kSegsF ? 0 : (SPLIT ? 1 : NB)> loc;
+    loc.zero();
     LocRegs<CH, 0> no_loc;
     // boundary `number` (1 .. S-1) is reached: record `number` = T in front of it and the colour of the segment that ends
     auto store_ck = [&](int number) {
@@ -1334,7 +1161,6 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
         TS_SEG_T0(tseg_p);
         const int i = base + lane;
         const bool have = i < range.y;
-#if TS_LDS_DMA
         TS_DMA_WAIT();                               // this chunk's records have landed (and id_next has arrived)
         const float4 q0 = have ? raw[lane] : zero4, q1 = have ? raw[64 + lane] : zero4,
                      q2 = have ? raw[128 + lane] : zero4;
@@ -1342,25 +1168,7 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
         int g_cur = 0;                               // (SURV) this chunk's ids, requested in front of the next chunk's
         if constexpr (SURV) if (have) g_cur = ids[i];
         if (i + 64 < range.y) dma_record(splats, id_next, raw);
-#else
-        // (LOCP: the per-segment sums need twelve registers more; there the next chunk's records are requested AFTER
-        // this chunk's have been staged, so that the two sets are never live together - the chunk's bodies still
-        // cover the round trip)
-        constexpr bool kLate = LOCP && TS_FWD_LATE_PREFETCH;
-        const float4 q0 = n0, q1 = n1, q2 = n2;
-        const int g_cur = 0;                         // (SURV needs TS_LDS_DMA)
-        auto prefetch = [&]() {
-            if (i + 64 < range.y) {
-                const int g = id_next;
-                n0 = splats[3 * (size_t)g]; n1 = splats[3 * (size_t)g + 1]; n2 = splats[3 * (size_t)g + 2];
-            }
-            if (i + 128 < range.y) id_next = ids[i + 128];
-        };
-        if constexpr (!kLate) prefetch();
-#endif
-#if TS_LDS_DMA
         if (i + 128 < range.y) id_next = ids[i + 128];
-#endif
         if constexpr (LOCP) {
             // a segment boundary (wave-uniform; never the list's first entry).  The record's stores are issued BEHIND the
             // loads of the next chunk's records: the wait for those loads then leaves the stores in flight
@@ -1375,7 +1183,7 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
             // Gaussians, so late in the list most (Gaussian, block) pairs are culled here
             bool sel[NB];
 #pragma unroll
-            for (int k = 0; k < NB; ++k) sel[k] = (TS_FWD_ALIVE && !LOCP) ? TS_LANE(alive[k]) : T[k] > 0.0f;
+            for (int k = 0; k < NB; ++k) sel[k] = T[k] > 0.0f;
             live = update_rects<NBX>(sel, X0, Y0, rects, lane);
             TS_WAVE_SYNC();
             if (live == 0) break;
@@ -1399,16 +1207,13 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
         TS_WAVE_SYNC();
         TS_STAT(0, cnt);
         const bool general = __ballot(keep && (s.mask & (1 << NB))) != 0ull;
-#if !TS_LDS_DMA
-        if constexpr (kLate) prefetch();
-#endif
         // bit NB of a staged mask = that Gaussian needs the general per-pixel code; the choice is made
         // once per chunk so that the common case runs a loop without those tests
         TS_SEG_ADD(ts_wave_clock_.seg, 0, tseg_p);
         if (general)
-            fwd_chunk<CH, true, NBX>(lds, cnt, fpx, fpy, T, fidx, acc, loc_, alive TS_SEG_ARG);
+            fwd_chunk<CH, true, NBX>(lds, cnt, fpx, fpy, T, fidx, acc, loc_ TS_SEG_ARG);
         else
-            fwd_chunk<CH, false, NBX>(lds, cnt, fpx, fpy, T, fidx, acc, loc_, alive TS_SEG_ARG);
+            fwd_chunk<CH, false, NBX>(lds, cnt, fpx, fpy, T, fidx, acc, loc_ TS_SEG_ARG);
         TS_WAVE_SYNC();
     }
     };
@@ -1464,49 +1269,17 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     }
 }
 
-// Butterfly merge of two per-lane partial vectors: lanes whose `bit` is clear keep a, the others
-// keep b, and each adds the kept quantity of its partner lane (partner given by the DPP control).
 typedef float f2 __attribute__((ext_vector_type(2)));
-
-template <int CTRL>
-__device__ __forceinline__ float merge2(float a, float b, bool bit) {
-    const float keep = bit ? b : a, send = bit ? a : b;
-    return keep + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(send), CTRL, 0xF, 0xF, true));
-}
 
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_add_t(float v) {
     return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, true));
 }
 
-// Reduces ten per-lane values over the wave in one merged butterfly.  On return lane l holds the wave
-// sum of value (l & 7) if bit 3 of l is clear, of value 8 + (l & 1) otherwise.
-//   level 1  partner l ^ 1 (quad_perm):  5 merges, lanes with bit 0 keep the odd value of each pair
-//   level 2  partner l ^ 2 (quad_perm):  2 merges (bit 1) + 1 plain add for the {8,9} pair
-//   level 3  row_ror:4:                  1 merge (bit 2) + 1 plain add
-//   level 4  row_ror:8:                  1 merge (bit 3): values 0..7 | values 8,9  -> row-of-16 totals
-//   rows are combined lane-wise through the LDS crossbar (ds_bpermute; the single-lane row_bcast forms
-//   cannot be used because lanes of a row hold different values).
-// 31 VALU issues + 2 ds_bpermute for 10 values (a plain DPP reduction is 6-8 per value).
-template <bool HAVE9>
-__device__ __forceinline__ float wave_sum10(const float v[10], int lane) {
-    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
-    const float u0 = merge2<0xB1>(v[0], v[1], b0), u1 = merge2<0xB1>(v[2], v[3], b0);
-    const float u2 = merge2<0xB1>(v[4], v[5], b0), u3 = merge2<0xB1>(v[6], v[7], b0);
-    // without a tenth value the {8,9} "pair" is a plain add (both lanes of a pair then hold value 8)
-    float t = HAVE9 ? merge2<0xB1>(v[8], v[9], b0) : dpp_add_t<0xB1, 0xF>(v[8]);
-    const float w0 = merge2<0x4E>(u0, u1, b1), w1 = merge2<0x4E>(u2, u3, b1);
-    t = dpp_add_t<0x4E, 0xF>(t);
-    float x = merge2<0x124>(w0, w1, b2);     // row_ror:4  (source lane differs in bit 2, same bits 1:0)
-    t = dpp_add_t<0x124, 0xF>(t);
-    x = merge2<0x128>(x, t, b3);             // row_ror:8
-    x += __shfl_xor(x, 16, 64);
-    x += __shfl_xor(x, 32, 64);
-    return x;
-}
-
-// The same reduction with the levels reordered so that the two in-row levels which DPP can write under a
-// BANK MASK run first, while there are most values: lane bit 3 (partner lane ^ 8 = row_ror:8, banks 2-3 =
+// Reduces ten per-lane values over the wave in one merged butterfly: a level that pairs the lanes differing in one
+// lane bit MERGES two value vectors while it adds them (the lanes with the bit clear keep a, the others b, and each
+// adds what its partner kept), so every level halves the number of live values.  The two in-row levels which DPP
+// can write under a BANK MASK run first, while there are most values: lane bit 3 (partner lane ^ 8 = row_ror:8, banks 2-3 =
 // bank_mask 0xC) and lane bit 2 (row_half_mirror pairs the two quads of a half-row, banks 1,3 = 0xA).  A merge
 // of two values is then two masked DPP adds (all lanes take a + perm(a), the lanes of the set bit are
 // overwritten with b + perm(b)) instead of two selects and a DPP add.  The compiler cannot be made to emit a
@@ -1516,18 +1289,12 @@ __device__ __forceinline__ float wave_sum10(const float v[10], int lane) {
 // values to three registers; the cross-row levels and the two quad levels follow on those.
 //   c0: value 2 * bit2 + bit3 | c1: value 4 + 2 * bit2 + bit3 | c2: value 8 + bit3
 // returns x with lane l holding the wave sum of value 4 * bit4 + 2 * bit2 + bit3 (l < 32) or 8 + bit3 (l >= 32).
-#ifndef TS_FLUSH_SWAP32
-#define TS_FLUSH_SWAP32 1
-#endif
-#ifndef TS_FLUSH_ASM
-#define TS_FLUSH_ASM 1
-#endif
 #define TS_DPP_ROR8 "row_ror:8 row_mask:0xf bank_mask:0xf"
 #define TS_DPP_ROR8_HI "row_ror:8 row_mask:0xf bank_mask:0xc"
 #define TS_DPP_HM "row_half_mirror row_mask:0xf bank_mask:0xf"
 #define TS_DPP_HM_HI "row_half_mirror row_mask:0xf bank_mask:0xa"
 typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-// `zero` (TS_FLUSH_ZERO_EARLY): called right behind the asm block, which is the last reader of the caller's accumulators -
+// `zero`: called right behind the asm block, which is the last reader of the caller's accumulators -
 // the caller's zeroing moves then stand where the permlane / DPP hazards below would otherwise need s_nops
 template <bool HAVE9, class Zero>
 __device__ __forceinline__ float wave_sum10_masked(const float v[10], int lane, Zero zero) {
@@ -1577,61 +1344,65 @@ __device__ __forceinline__ float wave_sum10_masked(const float v[10], int lane, 
     // lane bit 4: odd / even rows exchanged in one issue (v_permlane16_swap), c0 stays in the even rows
     const u2v r = __builtin_amdgcn_permlane16_swap(__float_as_uint(c0), __float_as_uint(c1), false, false);
     const float d = __uint_as_float(r.x) + __uint_as_float(r.y);
-#if TS_FLUSH_SWAP32
     // c2: the same exchange with itself; lane bit 5: v_permlane32_swap hands the upper half of d and the lower half
     // of c2 across in one issue, so lanes 0-31 end with d's total and lanes 32-63 with c2's - the same pairs of
-    // summands as the ds_bpermute form below (bit-identical rows) without three trips through the LDS crossbar
+    // summands as a ds_bpermute exchange (__shfl_xor 16 / 32) without its three trips through the LDS crossbar
     // (~65 cycles each, two of them dependent) on every row
     const u2v q = __builtin_amdgcn_permlane16_swap(__float_as_uint(c2), __float_as_uint(c2), false, false);
     const float e = __uint_as_float(q.x) + __uint_as_float(q.y);
     const u2v h = __builtin_amdgcn_permlane32_swap(__float_as_uint(d), __float_as_uint(e), false, false);
     float x = __uint_as_float(h.x) + __uint_as_float(h.y);
-#else
-    float dd = d + __shfl_xor(d, 32, 64);            // lane bit 5
-    c2 += __shfl_xor(c2, 16, 64);
-    c2 += __shfl_xor(c2, 32, 64);
-    float x = (lane & 32) ? c2 : dd;                 // one register for the two quad levels
-#endif
     x = dpp_add_t<0x4E, 0xF>(x);
     return dpp_add_t<0xB1, 0xF>(x);
 }
 
-// Wave-reduces the 6+CH per-lane sums of one (tile, Gaussian) and writes its row of `partials`
-// (lanes 48..57 each store one float of the 40/48-byte row, lane 58 sets the flag; TS_FLUSH_ASM: the first lane
-// of ten quads stores, lane 1 sets the flag).
-#ifndef TS_FLUSH_ZERO_EARLY
-#define TS_FLUSH_ZERO_EARLY 1
-#endif
-// ROWS THROUGH LDS (round 6, TS_ROWS_LDS).  The ablation table of round 6 (profiles/r06d_compositing_ablation.txt) put
+// STAGED RECORD of the backward pass: RS = 3 (three channels) or 4 float4s per entry in the wave's `lds`, written by
+// the staging code of raster_bwd_kernel (bwd_record_tail) and read by bwd_chunk.  Words 0..9 are the Gaussian's staged
+// fields and colour (CH == 3: word 9 carries the block mask); the two words behind them are named, because the record
+// is reused once its bodies have read it (ROWS THROUGH LDS below):
+constexpr int kRecIdxWord = 10;            // list index of the entry; kRowMark once the entry's row is parked in the record
+constexpr int kRecSlotWord = 11;           // row slot of the (tile, Gaussian) in `partials` - kept while the row is parked
+constexpr int kRowMark = -1;               // (no list index is negative)
+static_assert(kRecIdxWord == 4 * 2 + 2 && kRecSlotWord == 4 * 2 + 3, "the .z and .w of the record's float4 2");
+static_assert(6 + 4 <= kRecIdxWord, "a parked row (6 + CH values, words 0 ..) must leave the mark and the slot alone");
+__device__ __forceinline__ float4 bwd_record_tail(float w8, float w9, int idx, int slot) {      // float4 2 of a record
+    return make_float4(w8, w9, __int_as_float(idx), __int_as_float(slot));
+}
+__device__ __forceinline__ int rec_idx(const float4& tail) { return __float_as_int(tail.z); }     // word kRecIdxWord
+__device__ __forceinline__ int rec_slot(const float4& tail) { return __float_as_int(tail.w); }    // word kRecSlotWord
+
+// ROWS THROUGH LDS (round 6).  The ablation table of round 6 (profiles/r06d_compositing_ablation.txt) put
 // a number on the flush for the first time: raster_bwd 453 us, without any flush 183 us, with the stores but without the
 // cross-lane butterfly 383 us - the two scattered stores per row (ten dwords from ten lanes + a flag byte: 4.85 M
 // vector-memory instructions per launch, each one a trip through the CU's one address unit at a quarter rate for
 // 64-bit addresses) cost THREE times what the 24-issue butterfly costs.  So a row is no longer stored when it is
 // reduced: the writer lanes park it in LDS - in the 48 bytes of the entry's own staged record, which is dead once its
-// bodies have read it; the row slot stays where the record keeps it (word 11), word 10 (the list index) becomes the
-// mark "this entry has a row" - and when the chunk is done lane j stores row j with three 16-byte stores and its flag
-// byte: four vector-memory instructions per chunk of up to 64 rows instead of two per row.  Same values in the same
-// places: gradients bit for bit.
-#ifndef TS_ROWS_LDS
-#define TS_ROWS_LDS 1
-#endif
-constexpr int kRowMark = -1;               // word 10 of a staged record once its row has been parked there
-// word of the record this lane fills when a row is parked (-1: none): the reduction leaves value w in the first lane of
-// ten quads (see wave_sum10_masked); lane 36 - first lane of an idle quad - writes the mark
-__device__ __forceinline__ int row_word_of_lane(int lane, int values) {
+// bodies have read it; the row slot stays where the record keeps it (kRecSlotWord), kRecIdxWord (the list index)
+// becomes the mark "this entry has a row" - and when the chunk is done lane j stores row j with three 16-byte stores
+// and its flag byte (the end of bwd_chunk): four vector-memory instructions per chunk of up to 64 rows instead of two
+// per row.  Same values in the same places: gradients bit for bit.
+//
+// Quad lane that holds value w of a reduced row (see wave_sum10_masked), or -1: the first lane of ten quads.
+__device__ __forceinline__ int row_value_of_lane(int lane, int values) {
     const int b2 = (lane >> 2) & 1, b3 = (lane >> 3) & 1, b4 = (lane >> 4) & 1;
     const int w = (lane & 32) ? 8 + b3 : 4 * b4 + 2 * b2 + b3;
     const bool writer = (lane & 3) == 0 && ((lane & 32) == 0 || (lane & 0x14) == 0);
-    if (lane == 36) return 10;
     return (writer && w < values) ? w : -1;
 }
+// word of the record this lane fills when a row is parked (-1: none): its value of the row, and lane 36 - first lane
+// of an idle quad - writes the mark
+__device__ __forceinline__ int row_word_of_lane(int lane, int values) {
+    const int w = row_value_of_lane(lane, values);
+    return lane == 36 ? kRecIdxWord : w;
+}
+// Wave-reduces the 6+CH per-lane sums of one (tile, Gaussian), zeroes them, and parks the row in the entry's staged
+// record `lds_row` (row_word: row_word_of_lane of this lane).  lds_row == nullptr - TS_ABLATE builds only - stores
+// the row and its flag directly into slot `slot_i` from the quad lanes instead.
 template <int CH>
 __device__ __forceinline__ void flush_row(float (&v)[6 + CH], int slot_i, long long num_isects,
                                           float* __restrict__ partials,
                                           unsigned char* __restrict__ row_flags, int lane,
                                           float* lds_row = nullptr, int row_word = -1) {
-    // num_isects carries the row-flag value in its top byte (see ts_raster_bwd: TS_RASTER_FLAG_GEN)
-    const unsigned char flag_val = (unsigned char)((unsigned long long)num_isects >> 56);
     float r;
     if (TS_ABLATE == 4) {               // timing experiment: no cross-lane reduction
         r = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7])) + v[8];
@@ -1640,7 +1411,6 @@ __device__ __forceinline__ void flush_row(float (&v)[6 + CH], int slot_i, long l
 #pragma unroll
         for (int c = 0; c < 10; ++c) v10[c] = c < 6 + CH ? v[c] : 0.0f;
         auto zero = [&]() {
-            if (!TS_FLUSH_ZERO_EARLY) return;
             // zero the accumulators two at a time (v_mov_b64 on a register pair)
 #pragma unroll
             for (int c = 0; c + 1 < 6 + CH; c += 2) {
@@ -1650,37 +1420,25 @@ __device__ __forceinline__ void flush_row(float (&v)[6 + CH], int slot_i, long l
             }
             if ((6 + CH) & 1) v[5 + CH] = 0.0f;
         };
-        if (TS_FLUSH_ASM) r = wave_sum10_masked<(CH == 4)>(v10, lane, zero);
-        else { r = wave_sum10<(CH == 4)>(v10, lane); zero(); }
+        r = wave_sum10_masked<(CH == 4)>(v10, lane, zero);
     }
-    if (TS_ROWS_LDS && TS_FLUSH_ASM && lds_row != nullptr) {   // park the row in the entry's staged record
-        if (row_word >= 0) lds_row[row_word] = row_word == 10 ? __int_as_float(kRowMark) : r;
+    if (lds_row != nullptr) {           // park the row in the entry's staged record
+        if (row_word >= 0) lds_row[row_word] = row_word == kRecIdxWord ? __int_as_float(kRowMark) : r;
         return;
     }
+    // ablation builds only: the row stored where it is reduced
+    // num_isects carries the row-flag value in its top byte (see ts_raster_bwd: TS_RASTER_FLAG_GEN)
+    const unsigned char flag_val = (unsigned char)((unsigned long long)num_isects >> 56);
     const long long slot = (long long)slot_i;                  // < num_isects by construction (pack_splats)
-    (void)num_isects;
-    if (TS_FLUSH_ASM) {
-        const int b2 = (lane >> 2) & 1, b3 = (lane >> 3) & 1, b4 = (lane >> 4) & 1;
-        const int w = (lane & 32) ? 8 + b3 : 4 * b4 + 2 * b2 + b3;
-        const bool writer = (lane & 3) == 0 && ((lane & 32) == 0 || (lane & 0x14) == 0);
-        if (writer && w < 6 + CH) {
-            partials[slot * TS_PARTIAL_ROW_FLOATS + w] = r;
-            // "this row now holds data": stored by every writer lane (same byte, one transaction) inside the row's
-            // exec region - a second region for one lane cost a saveexec / restore / branch per row
-            if (TS_FLAG_WITH_ROW) row_flags[slot] = flag_val;
-        }
-        if (!TS_FLAG_WITH_ROW && lane == 1) row_flags[slot] = flag_val;
-        return;
-    }
-    const int w = lane - 48;                                   // row 3: lane 48+w holds value w, w < 10
+    constexpr bool kFlagWithRow = CH == 4;     // measured: four channels 561 -> 544 us, three channels 507 -> 512 us
+    const int w = row_value_of_lane(lane, 6 + CH);
     if (w >= 0) {
-        if (w < 6 + CH) {
-            if (TS_NT_ROWS) __builtin_nontemporal_store(r, partials + slot * TS_PARTIAL_ROW_FLOATS + w);
-            else partials[slot * TS_PARTIAL_ROW_FLOATS + w] = r;
-        } else if (w == 10) {
-            row_flags[slot] = flag_val;                        // this row now holds data
-        }
+        partials[slot * TS_PARTIAL_ROW_FLOATS + w] = r;
+        // "this row now holds data": stored by every writer lane (same byte, one transaction) inside the row's
+        // exec region - a second region for one lane cost a saveexec / restore / branch per row
+        if (kFlagWithRow) row_flags[slot] = flag_val;
     }
+    if (!kFlagWithRow && lane == 1) row_flags[slot] = flag_val;
 }
 
 // Replays the `cnt` staged Gaussians of one chunk back to front (backward).
@@ -1689,15 +1447,10 @@ __device__ __forceinline__ void flush_row(float (&v)[6 + CH], int slot_i, long l
 //   vo = v_out, fidx = index of the last Gaussian the forward pass composited.
 // Inside a block the body is full-exec and branch free: a lane that is not valid uses alpha = 0
 // (ra = 1, fac = 0, v_sig = 0) and changes nothing.
-// STARTED (round 6, TS_BWD_STARTED): every pixel of every block that takes part in this chunk has its whole list in
-// front of it (fidx >= the chunk's highest index - true for all but the last one or two chunks of a list, since nearly
-// every pixel's last contribution lies there), so `idx <= fidx[k]` holds for every entry and lane: the body drops the
-// compare and the s_and_b64 of the two ballots (2 of its ~43 issue slots).  Same sums, bit for bit.
-#ifndef TS_BWD_STARTED
-#define TS_BWD_STARTED 0          // measured (round 6, config 3): raster_bwd 447 - 453 us either way; off
-#endif
-template <int CH, bool GENERAL, int NBX, bool STARTED = false>
-__device__ __forceinline__ void bwd_chunk(const float4* __restrict__ lds, int cnt, const float (&fpx)[NBX],
+// `lds`: the chunk's staged records (STAGED RECORD).  Every entry that got a row leaves it parked in its own record;
+// the rows are stored to `partials` when the chunk is done (ROWS THROUGH LDS), and the records are dead on return.
+template <int CH, bool GENERAL, int NBX>
+__device__ __forceinline__ void bwd_chunk(float4* __restrict__ lds, int cnt, const float (&fpx)[NBX],
                                           const float (&fpy)[2], float (&T)[2 * NBX], float (&R)[2 * NBX],
                                           const float (&vo)[2 * NBX][CH], const int (&fidx)[2 * NBX],
                                           float (&acc)[6 + CH], long long num_isects,
@@ -1709,25 +1462,16 @@ __device__ __forceinline__ void bwd_chunk(const float4* __restrict__ lds, int cn
 #pragma clang fp contract(off)
     TS_WORK(0, cnt);
     // staged record: three float4 for three channels (the block mask rides in the unused fourth colour word),
-    // four for RGB + depth.  TS_BWD_EARLY_RECORD (an experiment, off): the NEXT entry's record requested in front of the
-    // row flush of this one - its registers are dead by then, and the flush (no LDS access in it) would cover the round
-    // trip that the wave waits out at the top of every iteration (7.6 % of a backward wave's cycles); slower (above)
+    // four for RGB + depth
     constexpr int RS = CH == 3 ? 3 : 4;
-    const int row_word = row_word_of_lane(lane, 6 + CH);      // (TS_ROWS_LDS) the word of a parked row this lane writes
-    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
-    float bm_f = 0.0f;
-    if (TS_BWD_EARLY_RECORD && cnt > 0 && TS_ABLATE != 3) {
-        r0 = lds[0]; r1 = lds[1]; r2 = lds[2];
-        bm_f = CH == 3 ? r2.y : lds[3].x;
-    }
+    constexpr bool kRowsLds = TS_ABLATE == 0;                 // (ablation builds store every row where it is reduced)
+    const int row_word = row_word_of_lane(lane, 6 + CH);      // the word of a parked row this lane writes
     for (int j = 0; j < (TS_ABLATE == 3 ? 0 : cnt); ++j) {
         TS_SEG_T0(tseg_a);
-        if (!TS_BWD_EARLY_RECORD) {
-            r0 = lds[RS * j]; r1 = lds[RS * j + 1]; r2 = lds[RS * j + 2];
-            bm_f = CH == 3 ? r2.y : lds[RS * j + 3].x;
-        }
+        const float4 r0 = lds[RS * j], r1 = lds[RS * j + 1], r2 = lds[RS * j + 2];
+        const float bm_f = CH == 3 ? r2.y : lds[RS * j + 3].x;
         const int bm = __builtin_amdgcn_readfirstlane(__float_as_int(bm_f));
-        const int idx = __float_as_int(r2.z);
+        const int idx = rec_idx(r2);
         const float neg_lo = -r1.y;
         float col[CH];
         col[0] = r1.z; col[1] = r1.w; col[2] = r2.x;
@@ -1749,8 +1493,7 @@ __device__ __forceinline__ void bwd_chunk(const float4* __restrict__ lds, int cn
             const float sgl = sigma_l2(r0.z, r0.w, r1.x, neg_lo, dx, dy);
             const float araw = __builtin_amdgcn_exp2f(-sgl);           // opacity * exp(-sigma)
             float a = araw;
-            mask64 validm = TS_BALLOT(araw >= ts::kAlphaMin);
-            if (!STARTED) validm &= TS_BALLOT(idx <= fidx[k]);
+            mask64 validm = TS_BALLOT(araw >= ts::kAlphaMin) & TS_BALLOT(idx <= fidx[k]);
             if (GENERAL) {
                 a = fminf(ts::kAlphaMaxBwd, araw);
                 validm &= TS_BALLOT(sgl >= neg_lo);                    // sigma >= 0
@@ -1771,14 +1514,8 @@ __device__ __forceinline__ void bwd_chunk(const float4* __restrict__ lds, int cn
             any = 1;
             // the select takes its mask from an ordinary SGPR pair: the VOP2 form on a vcc that the SCALAR unit
             // wrote (the s_and of the two ballots) costs a wave 19 cycles instead of 5 (tools/micro/lat_bench.hip)
-            float am;
-            if (TS_BWD_EXEC_MASK) am = a;
-            else if (TS_SELECT_SGPR) asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(am) : "v"(a), "s"(validm));
-            else am = TS_LANE(validm) ? a : 0.0f;
-#if TS_BWD_EXEC_MASK
-            // experiment: the rest of the body under EXEC = valid lanes (an invalid lane adds +-0 everywhere: same bits)
-            if (TS_LANE(validm)) {
-#endif
+            float am;                                   // = valid ? a : 0
+            asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(am) : "v"(a), "s"(validm));
             const float ra = __builtin_amdgcn_rcpf(1.0f - am);
             const float Tk = T[k] * ra;                 // transmittance in front of the Gaussian
             const float fac = am * Tk;
@@ -1800,9 +1537,6 @@ __device__ __forceinline__ void bwd_chunk(const float4* __restrict__ lds, int cn
             acc[3] = __builtin_fmaf(vdx, dx, acc[3]);
             acc[4] = __builtin_fmaf(vdx, dy, acc[4]);
             acc[5] = __builtin_fmaf(vdy, dy, acc[5]);
-#if TS_BWD_EXEC_MASK
-            }
-#endif
         }
         // `any` is wave-uniform.  It is passed through an empty asm so that the compiler cannot prove
         // "block 3 ran => a flush follows": with that knowledge it specialises the last block body
@@ -1811,22 +1545,17 @@ __device__ __forceinline__ void bwd_chunk(const float4* __restrict__ lds, int cn
         asm volatile("" : "+s"(any));
         TS_SEG_ADD(ts_seg_, 2, tseg_b);
         TS_SEG_T0(tseg_c);
-        constexpr bool kRowsLds = TS_ROWS_LDS && TS_FLUSH_ASM && TS_ABLATE == 0;
-        const int row_slot = kRowsLds ? 0 : __builtin_amdgcn_readfirstlane(__float_as_int(r2.w));
-        if (TS_BWD_EARLY_RECORD && j + 1 < cnt) {
-            r0 = lds[RS * (j + 1)]; r1 = lds[RS * (j + 1) + 1]; r2 = lds[RS * (j + 1) + 2];
-            bm_f = CH == 3 ? r2.y : lds[RS * (j + 1) + 3].x;
-        }
+        const int row_slot = kRowsLds ? 0 : __builtin_amdgcn_readfirstlane(rec_slot(r2));
         if (any && TS_ABLATE != 7) {
             TS_STAT(5, 1);
             TS_WORK(2, 1);
-            if (kRowsLds)
+            if (kRowsLds)       // the row takes the place of the entry's record, which nothing reads any more
                 flush_row<CH>(acc, row_slot, num_isects, partials, row_flags, lane,
-                              reinterpret_cast<float*>(const_cast<float4*>(lds) + RS * j), row_word);
+                              reinterpret_cast<float*>(lds + RS * j), row_word);
             else
                 flush_row<CH>(acc, row_slot, num_isects, partials, row_flags, lane);
-            if (!TS_FLUSH_ZERO_EARLY || TS_ABLATE == 4) {
-                // zero the accumulators two at a time (v_mov_b64 on a register pair)
+            if (TS_ABLATE == 4) {
+                // (the butterfly's zeroing did not run) zero the accumulators two at a time (v_mov_b64 on a register pair)
 #pragma unroll
                 for (int c = 0; c + 1 < 6 + CH; c += 2) {
                     f2 z = (f2)(0.0f);
@@ -1838,13 +1567,13 @@ __device__ __forceinline__ void bwd_chunk(const float4* __restrict__ lds, int cn
         }
         TS_SEG_ADD(ts_seg_, 3, tseg_c);
     }
-    if (TS_ROWS_LDS && TS_FLUSH_ASM && TS_ABLATE == 0) {
+    if (kRowsLds) {
         // the chunk's rows, parked in LDS by the flushes above: lane j stores the row of staged entry j
         TS_WAVE_SYNC();
         if (lane < cnt) {
             float4 p2 = lds[RS * lane + 2];
-            if (__float_as_int(p2.z) == kRowMark) {
-                const long long slot = (long long)__float_as_int(p2.w);      // < num_isects by construction (pack_splats)
+            if (rec_idx(p2) == kRowMark) {
+                const long long slot = (long long)rec_slot(p2);              // < num_isects by construction (pack_splats)
                 const float4 p0 = lds[RS * lane], p1 = lds[RS * lane + 1];
                 if (CH == 3) p2.y = 0.0f;
                 p2.z = 0.0f; p2.w = 0.0f;
@@ -1857,13 +1586,10 @@ __device__ __forceinline__ void bwd_chunk(const float4* __restrict__ lds, int cn
     }
 }
 
-// Workgroups of the backward launch are ONE wave (TS_BWD_WAVES): its waves never synchronise, and a workgroup's wave
+// Workgroups of the backward launch are ONE wave: its waves never synchronise, and a workgroup's wave
 // slots and LDS are only handed to the next workgroup when ALL its waves are done - with four tiles per workgroup a
 // wave that finished early left its slot idle until the slowest of the four was through (raster_bwd 532 -> 522 us).
-#ifndef TS_BWD_WAVES
-#define TS_BWD_WAVES 1
-#endif
-constexpr int kBwdWaves = TS_BWD_WAVES;
+constexpr int kBwdWaves = 1;
 // SURVIVOR LISTS (SURV; one wave per 16x16 tile on 16x16 lists, whole tiles and list-segment items).  The forward pass
 // stages entry i against the rectangles of the pixels still unfinished at the start of i's chunk, and every pixel whose
 // final_index is >= i is among them: its block mask (raster_fwd_kernel<.., SURV>) covers every block in which entry i
@@ -1883,12 +1609,12 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
     const float* __restrict__ v_out_alpha, const unsigned char* __restrict__ clamp_mask,
     float* __restrict__ partials, unsigned char* __restrict__ row_flags,
     const int* __restrict__ sv_id, const int* __restrict__ sv_meta, const int* __restrict__ sv_cnt) {
-    static_assert(!SURV || (!SPLIT && NBX == 2 && !WL && TS_LDS_DMA), "survivor lists: one wave per 16x16 tile");
+    static_assert(!SURV || (!SPLIT && NBX == 2 && !WL), "survivor lists: one wave per 16x16 tile");
     constexpr int NB = 2 * NBX;
     TS_LDS_PAD_DECL();
     __shared__ float4 lds_all[kBwdWaves][64 * 4];
     __shared__ float4 rect_all[kBwdWaves][NB];
-    __shared__ float4 raw_all[TS_LDS_DMA ? kBwdWaves : 1][3 * 64];   // landing zone of the next chunk's records
+    __shared__ float4 raw_all[kBwdWaves][3 * 64];                    // landing zone of the next chunk's records
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // list segments: S work items per cut tile, item `seg` replays the entries [sb, se) of the list; whole tiles (hybrid
     // launch: the first `whole` of every band) are one item.  Work items are handed out band by band: workgroup b
@@ -1930,7 +1656,6 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
     int sb = range.x, se = range.y;
     bool front = false;                           // entries lie behind this segment: it starts from a checkpoint
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    [[maybe_unused]] float4 n0 = zero4, n1 = zero4, n2 = zero4;
     int id_next = 0;
     if (kSegs && S_seg > 1) {
         const int len = range.y - range.x;
@@ -2039,7 +1764,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
     for (int c = 0; c < 6 + CH; ++c) acc[c] = 0.0f;
 
     // same software pipeline as the forward kernel, walking the list back to front
-    float4* raw = raw_all[TS_LDS_DMA ? wave : 0];
+    float4* raw = raw_all[wave];
     if constexpr (SURV) {
         // the item's survivors [pb, pe) (positions in the tile's survivor list; clamped to the list)
         const int* cnt_t = sv_cnt + 8 * (size_t)tile;
@@ -2093,8 +1818,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
                 constexpr int RS = CH == 3 ? 3 : 4;
                 lds[RS * pos] = make_float4(s.gx, s.gy, s.hA, s.B);
                 lds[RS * pos + 1] = make_float4(s.hC, s.lo, q1.z, q1.w);
-                lds[RS * pos + 2] = make_float4(q2.x, CH == 3 ? __int_as_float(mask) : q2.y, __int_as_float(i),
-                                                __int_as_float(slot));
+                lds[RS * pos + 2] = bwd_record_tail(q2.x, CH == 3 ? __int_as_float(mask) : q2.y, i, slot);
                 if (CH == 4) lds[RS * pos + 3] = make_float4(__int_as_float(mask), 0.f, 0.f, 0.f);
             }
             TS_WAVE_SYNC();
@@ -2114,11 +1838,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
     }
     if (last - lane >= sb) {
         const int g = ids_sorted[last - lane];
-#if TS_LDS_DMA
         dma_record(splats, g, raw);
-#else
-        n0 = splats[3 * (size_t)g]; n1 = splats[3 * (size_t)g + 1]; n2 = splats[3 * (size_t)g + 2];
-#endif
     }
     if (last - 64 - lane >= sb) id_next = ids_sorted[last - 64 - lane];
 
@@ -2126,19 +1846,11 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
         TS_SEG_T0(tseg_p);
         const int i = hi - lane;
         const bool have = i >= sb;
-#if TS_LDS_DMA
         TS_DMA_WAIT();                               // this chunk's records have landed (and id_next has arrived)
         const float4 q0 = have ? raw[lane] : zero4, q1 = have ? raw[64 + lane] : zero4,
                      q2 = have ? raw[128 + lane] : zero4;
         TS_LDS_WAIT();                               // read out before the next chunk's records may overwrite them
         if (i - 64 >= sb) dma_record(splats, id_next, raw);
-#else
-        const float4 q0 = n0, q1 = n1, q2 = n2;
-        if (i - 64 >= sb) {
-            const int g = id_next;
-            n0 = splats[3 * (size_t)g]; n1 = splats[3 * (size_t)g + 1]; n2 = splats[3 * (size_t)g + 2];
-        }
-#endif
         if (i - 128 >= sb) id_next = ids_sorted[i - 128];
         int blocks;
         {   // rectangle of the pixels whose forward list reaches into this chunk (fidx >= chunk low)
@@ -2171,31 +1883,17 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
             constexpr int RS = CH == 3 ? 3 : 4;           // see bwd_chunk
             lds[RS * pos] = make_float4(s.gx, s.gy, s.hA, s.B);
             lds[RS * pos + 1] = make_float4(s.hC, s.lo, q1.z, q1.w);
-            lds[RS * pos + 2] = make_float4(q2.x, CH == 3 ? __int_as_float(s.mask) : q2.y, __int_as_float(i),
-                                            __int_as_float(slot));
+            lds[RS * pos + 2] = bwd_record_tail(q2.x, CH == 3 ? __int_as_float(s.mask) : q2.y, i, slot);
             if (CH == 4) lds[RS * pos + 3] = make_float4(__int_as_float(s.mask), 0.f, 0.f, 0.f);
         }
         TS_WAVE_SYNC();
         TS_STAT(2, cnt);
         TS_STAT(7, min(64, hi - sb + 1));
         TS_SEG_ADD(ts_wave_clock_.seg, 0, tseg_p);
-        // every block that takes part (a pixel's list reaches into the chunk) has ALL its pixels' lists in front of the
-        // chunk's last entry: no per-entry `idx <= fidx` test (see STARTED)
-        bool started = TS_BWD_STARTED && NBX == 2 && !SPLIT;
-        if (started) {
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                const unsigned long long all = __ballot(fidx[k] >= hi);
-                if ((blocks & (1 << k)) && all != ~0ull) started = false;
-            }
-        }
         const bool general = __ballot(keep && (s.mask & (1 << NB))) != 0ull;
         if (general)
             bwd_chunk<CH, true, NBX>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
                                      row_flags, lane TS_SEG_ARG);
-        else if (started)
-            bwd_chunk<CH, false, NBX, true>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
-                                            row_flags, lane TS_SEG_ARG);
         else
             bwd_chunk<CH, false, NBX>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
                                       row_flags, lane TS_SEG_ARG);
@@ -2208,21 +1906,9 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
 // with d = xy - pixel.  The conic / opacity factors are applied once per Gaussian here.
 // color_mask (may be NULL): clamp mask of the colour stage, applied here (bit c clear -> v_colors[c] = 0)
 // when the gradients are summed over ranks before the colour stage's backward runs.
-// LANES per Gaussian (TS_REDUCE_LANES, round 6): one lane per Gaussian walked ALL its slots, so a wave took as long as the
-// largest of its 64 Gaussians (6 slots on average, 100+ for a large one) and every lane's walk was a chain of dependent
-// flag -> row loads.  Now LANES consecutive lanes share a Gaussian: lane j takes the slots j, j + LANES, ... of its
-// range in ascending order (the flags of LANES neighbouring slots are neighbouring bytes), sums them in double, and the
-// LANES partial sums are combined pairwise (j ^ 1, then j ^ 2, ...) - a fixed order, so the gradients stay
-// bit-reproducible run to run.
-#ifndef TS_REDUCE_LANES
-#define TS_REDUCE_LANES 1          // measured (config 3 / 5, us): 1: 59 / 431, 2: 56 / -, 4: 58 / 452, 8: 87 / 571, 16: 183 / 985 - the walk is bound by its row gathers, not by its longest lane
-#endif
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, m, 64);
-    hi = __shfl_xor(hi, m, 64);
-    return __hiloint2double(hi, lo);
-}
+// One lane per Gaussian walks all its slots in ascending order - a fixed order, so the gradients stay bit-reproducible
+// run to run.  (Several lanes per Gaussian did not pay: the walk is bound by its row gathers, not by its longest lane -
+// profiles/HISTORY.md, "build-time variants retired from the tree".)
 template <int CH>
 __global__ __launch_bounds__(256) void reduce_partials_kernel(
     int n, int flags, const int* __restrict__ num_tiles_hit, const int* __restrict__ cum_tiles_hit,
@@ -2230,11 +1916,8 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
     const float4* __restrict__ splats, float* __restrict__ v_xy, float* __restrict__ v_conic,
     float* __restrict__ v_colors, float* __restrict__ v_opacity, float* __restrict__ v_depth,
     const unsigned char* __restrict__ color_mask, float4* __restrict__ grad_rows) {
-    constexpr int L = TS_REDUCE_LANES;
-    static_assert(L == 1 || L == 2 || L == 4 || L == 8 || L == 16, "lanes per Gaussian: a power of two within a row of 16");
-    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int i = (int)(gi / L), j = (int)(gi % L);
-    if (i >= n) return;                           // (all L lanes of a Gaussian leave together)
+    const int i = (int)((long long)blockIdx.x * 256 + threadIdx.x);
+    if (i >= n) return;
     const int cnt = num_tiles_hit[i];
     const long long end = cum_tiles_hit[i];
     // a row holds data of THIS pass iff its flag equals the pass's value (legacy value 1 on a zeroed array, or
@@ -2255,7 +1938,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
     };
     if (flags & TS_RASTER_SPLIT_BLOCKS) {         // four rows per (tile, Gaussian): one flag word per pair
         const unsigned int* flags4 = reinterpret_cast<const unsigned int*>(row_flags);
-        for (long long sl = end - cnt + j; sl < end; sl += L) {
+        for (long long sl = end - cnt; sl < end; ++sl) {
             const unsigned int fw = flags4[sl];
             unsigned int f = 0u;                      // byte k set: row k of the slot was written in this pass
 #pragma unroll
@@ -2275,20 +1958,20 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
             }
         }
     } else {
-        // kAhead slots per lane and step: their flags, then the rows of the flagged ones, are all requested before the
+        // kAhead slots per step: their flags, then the rows of the flagged ones, are all requested before the
         // first addition, which happens in slot order - a lane's walk is otherwise a chain of dependent
         // flag -> row -> flag loads
         constexpr int kAhead = TS_REDUCE_AHEAD;
-        for (long long s0 = end - cnt + j; s0 < end; s0 += kAhead * L) {
+        for (long long s0 = end - cnt; s0 < end; s0 += kAhead) {
             bool f[kAhead];
             float4 p0[kAhead], p1[kAhead], p2[kAhead];
 #pragma unroll
-            for (int u = 0; u < kAhead; ++u) f[u] = (s0 + u * L < end) && row_flags[s0 + u * L] == gen;   // else: not written in this pass (stale)
+            for (int u = 0; u < kAhead; ++u) f[u] = (s0 + u < end) && row_flags[s0 + u] == gen;   // else: not written in this pass (stale)
 #pragma unroll
             for (int u = 0; u < kAhead; ++u) {
                 if (f[u]) {
-                    p0[u] = partials[kRowF4 * (s0 + u * L)]; p1[u] = partials[kRowF4 * (s0 + u * L) + 1];
-                    p2[u] = partials[kRowF4 * (s0 + u * L) + 2];
+                    p0[u] = partials[kRowF4 * (s0 + u)]; p1[u] = partials[kRowF4 * (s0 + u) + 1];
+                    p2[u] = partials[kRowF4 * (s0 + u) + 2];
                 }
             }
 #pragma unroll
@@ -2297,12 +1980,6 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
             }
         }
     }
-#pragma unroll
-    for (int m = 1; m < L; m <<= 1) {
-#pragma unroll
-        for (int c = 0; c < 10; ++c) s[c] += shfl_xor_f64(s[c], m);
-    }
-    if (j != 0) return;
     float4 a0 = make_float4((float)s[0], (float)s[1], (float)s[2], (float)s[3]);
     float4 a1 = make_float4((float)s[4], (float)s[5], (float)s[6], (float)s[7]);
     float4 a2 = make_float4((float)s[8], (float)s[9], 0.f, 0.f);
@@ -2403,7 +2080,7 @@ int ts_raster_fwd_planes(int32_t channels, int32_t flags, const ts_camera* cam, 
     const bool wide = cam->wide_tiles != 0 && !narrow;
     ts_camera kcam = *cam;
     kcam.hints &= ~kHintCoopAll;
-    if (split && TS_COOP && !wide && !narrow && (cam->hints & TS_HINT_COOP_SPLIT)) {
+    if (split && !wide && !narrow && (cam->hints & TS_HINT_COOP_SPLIT)) {
         split = false;                          // four waves per tile with SHARED staging instead (COOPERATIVE TILES)
         kcam.hints |= kHintCoopAll;
     }
@@ -2484,7 +2161,7 @@ int raster_fwd_sort(int32_t channels, int32_t flags, const ts_camera* cam, const
     if (survivors && (split || !final_Ts)) return TS_E_BADARG;
     ts_camera kcam = *cam;
     kcam.hints &= ~kHintCoopAll;
-    if (split && TS_COOP && (cam->hints & TS_HINT_COOP_SPLIT)) {          // see ts_raster_fwd_planes
+    if (split && (cam->hints & TS_HINT_COOP_SPLIT)) {          // see ts_raster_fwd_planes
         split = false;
         kcam.hints |= kHintCoopAll;
     }
@@ -2600,7 +2277,7 @@ int ts_reduce_partials(int32_t n, int32_t channels, int32_t flags, const int32_t
     hipStream_t s = (hipStream_t)stream;
     const float4* pr = reinterpret_cast<const float4*>(partials);
     const float4* sp = reinterpret_cast<const float4*>(splats);
-    const int grid = (int)(((long long)n * TS_REDUCE_LANES + 255) / 256);
+    const int grid = (int)(((long long)n + 255) / 256);
     if (channels == 3)
         hipLaunchKernelGGL(reduce_partials_kernel<3>, dim3(grid), dim3(256), 0, s, n, (int)flags, num_tiles_hit,
                            cum_tiles_hit, pr, row_flags, sp, v_xy, v_conic, v_colors, v_opacity, v_depth, color_mask,
@@ -2622,7 +2299,7 @@ int ts_reduce_partials_rows(int32_t n, int32_t channels, int32_t flags, const in
     const float4* pr = reinterpret_cast<const float4*>(partials);
     const float4* sp = reinterpret_cast<const float4*>(splats);
     float4* gr = reinterpret_cast<float4*>(grad_rows);
-    const int grid = (int)(((long long)n * TS_REDUCE_LANES + 255) / 256);
+    const int grid = (int)(((long long)n + 255) / 256);
     if (channels == 3)
         hipLaunchKernelGGL(reduce_partials_kernel<3>, dim3(grid), dim3(256), 0, s, n, (int)flags, num_tiles_hit,
                            cum_tiles_hit, pr, row_flags, sp, (float*)nullptr, (float*)nullptr, (float*)nullptr,

@@ -10,8 +10,7 @@
 //     launch over a table of tensors with per-tensor learning rates (model_gaussian.py:112-120).
 //
 // SSIM pass 1 (the five filtered maps, the SSIM sum, three partial-derivative maps) is a sliding window: one wave per
-// 64 map columns and channel, the filtered rows in a register ring (ssim_fwd_rows_kernel; the tiled kernel of rounds
-// 1 - 5 stays behind -DTS_SSIM_ROWS=0).  Pass 2 (the image gradient) stages a (32+10) x (32+10) patch of the maps in
+// 64 map columns and channel, the filtered rows in a register ring (ssim_fwd_rows_kernel).  Pass 2 (the image gradient) stages a (32+10) x (32+10) patch of the maps in
 // LDS and runs the two 11-tap passes from there, so each map byte is read from HBM ~1.7x.  Adam streams at HBM rate.
 #include <hip/hip_runtime.h>
 
@@ -68,155 +67,21 @@ __device__ __forceinline__ void horizontal_strip(const float (*p)[kPatch + 1], i
     }
 }
 
-__device__ __forceinline__ float block_sum(float v, float* scratch) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) scratch[wave] = v;
-    __syncthreads();
-    const float t = scratch[0] + scratch[1] + scratch[2] + scratch[3];
-    __syncthreads();
-    return t;
-}
-
-// Pass 1: per 32x32 tile of the SSIM map: the five filtered maps, the SSIM value (summed per block
-// into sums[block*2+0]) and the three partial-derivative maps dS/d filt(X), dS/d filt(X^2),
-// dS/d filt(XY) written to dmaps[3][3 channels][Ho][Wo] (planar).  Also the L1 sum of the tile's own 32x32 pixels
-// (image tiles of the same grid cover the whole image; sums[block*2+1]).
+// Pass 1: the five filtered maps, the SSIM sum and the three partial-derivative maps dS/d filt(X), dS/d filt(X^2),
+// dS/d filt(XY) written to dmaps[3][3 channels][Ho][Wo] (planar), and the L1 sums.
 // X has `xs` floats per pixel (3: an RGB image; 4: the compositing kernels' RGB+depth output, whose
 // channel 3 is compared with the depth target D when D != nullptr, train.py:65-69).
 // Xd (with xs == 3): the depth as its own [H,W] plane (ts_photometric_loss_planes).
-__global__ __launch_bounds__(kThreads) void ssim_fwd_kernel(int H, int W, int xs,
-                                                            const float* __restrict__ X,
-                                                            const float* __restrict__ Xd,
-                                                            const float* __restrict__ Y,
-                                                            const float* __restrict__ D,
-                                                            float* __restrict__ dmaps,
-                                                            float* __restrict__ sums) {
-    __shared__ float px[kPatch][kPatch + 1], py[kPatch][kPatch + 1];
-    __shared__ float h0[kPatch][kTile + 1], h1[kPatch][kTile + 1], h2[kPatch][kTile + 1],
-        h3[kPatch][kTile + 1], h4[kPatch][kTile + 1];
-    __shared__ float scratch[4];
-    float g[kWin];
-    gauss_window(g);
-    const int Ho = H - kHalo, Wo = W - kHalo;
-    const int ox0 = blockIdx.x * kTile, oy0 = blockIdx.y * kTile;
-    float ssim_sum = 0.0f, l1_sum = 0.0f, depth_sum = 0.0f;
-    // every thread's share of the 42 x 42 pixel patch is fetched ONCE for the three channels (one
-    // 16-byte load per pixel of a 4-float image) instead of one strided 4-byte load per channel pass
-    constexpr int kShare = (kPatch * kPatch + kThreads - 1) / kThreads;
-    float xa[kShare][3], ya[kShare][3];
-#pragma unroll
-    for (int u = 0; u < kShare; ++u) {
-        const int i = threadIdx.x + u * kThreads;
-        const int r = i / kPatch, q = i % kPatch;
-        const int y = oy0 + r, x = ox0 + q;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) xa[u][c] = ya[u][c] = 0.0f;
-        if (i < kPatch * kPatch && y < H && x < W) {
-            const size_t pix = (size_t)y * W + x;
-            float x3 = 0.0f;
-            if (xs == 4) {
-                const float4 v = reinterpret_cast<const float4*>(X)[pix];
-                xa[u][0] = v.x; xa[u][1] = v.y; xa[u][2] = v.z; x3 = v.w;
-            } else {
-                xa[u][0] = X[pix * 3]; xa[u][1] = X[pix * 3 + 1]; xa[u][2] = X[pix * 3 + 2];
-                if (Xd && D && r < kTile && q < kTile) x3 = Xd[pix];
-            }
-            ya[u][0] = Y[pix * 3]; ya[u][1] = Y[pix * 3 + 1]; ya[u][2] = Y[pix * 3 + 2];
-            if (r < kTile && q < kTile) {
-                l1_sum += fabsf(xa[u][0] - ya[u][0]);
-                l1_sum += fabsf(xa[u][1] - ya[u][1]);
-                l1_sum += fabsf(xa[u][2] - ya[u][2]);
-                if (D) depth_sum += fabsf(x3 - D[pix]);
-            }
-        }
-    }
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int u = 0; u < kShare; ++u) {
-            const int i = threadIdx.x + u * kThreads;
-            if (i < kPatch * kPatch) {
-                const int r = i / kPatch, q = i % kPatch;
-                px[r][q] = c == 0 ? xa[u][0] : (c == 1 ? xa[u][1] : xa[u][2]);
-                py[r][q] = c == 0 ? ya[u][0] : (c == 1 ? ya[u][1] : ya[u][2]);
-            }
-        }
-        __syncthreads();
-        // horizontal pass: 42 rows x 32 columns, five quantities.  One item = kStrip adjacent
-        // outputs of a row: its kWin + kStrip - 1 inputs are read from LDS once and reused from
-        // registers (14 reads for 4 outputs instead of 44).
-        for (int i = threadIdx.x; i < kPatch * (kTile / kStrip); i += kThreads) {
-            const int r = i / (kTile / kStrip), q0 = (i % (kTile / kStrip)) * kStrip;
-            float a[kWin + kStrip - 1], b[kWin + kStrip - 1];
-#pragma unroll
-            for (int k = 0; k < kWin + kStrip - 1; ++k) { a[k] = px[r][q0 + k]; b[k] = py[r][q0 + k]; }
-#pragma unroll
-            for (int j = 0; j < kStrip; ++j) {
-                float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
-#pragma unroll
-                for (int k = 0; k < kWin; ++k) {
-                    const float av = a[j + k], bv = b[j + k], w = g[k];
-                    s0 += w * av; s1 += w * bv; s2 += w * av * av; s3 += w * bv * bv; s4 += w * av * bv;
-                }
-                h0[r][q0 + j] = s0; h1[r][q0 + j] = s1; h2[r][q0 + j] = s2; h3[r][q0 + j] = s3;
-                h4[r][q0 + j] = s4;
-            }
-        }
-        __syncthreads();
-        // vertical pass + SSIM
-        for (int i = threadIdx.x; i < kTile * (kTile / kStrip); i += kThreads) {
-            // one item = kStrip vertically adjacent outputs of a column (register sliding window)
-            const int q = i % kTile, r0 = (i / kTile) * kStrip;
-            float f[5][kStrip];
-            vertical_strip(h0, r0, q, g, f[0]); vertical_strip(h1, r0, q, g, f[1]);
-            vertical_strip(h2, r0, q, g, f[2]); vertical_strip(h3, r0, q, g, f[3]);
-            vertical_strip(h4, r0, q, g, f[4]);
-#pragma unroll
-          for (int j = 0; j < kStrip; ++j) {
-            const int r = r0 + j;
-            const int y = oy0 + r, x = ox0 + q;
-            if (y >= Ho || x >= Wo) continue;
-            const float m1 = f[0][j], m2 = f[1][j], q1 = f[2][j], q2 = f[3][j], r12 = f[4][j];
-            const float s1 = q1 - m1 * m1, s2 = q2 - m2 * m2, s12 = r12 - m1 * m2;
-            const float A1 = 2.0f * m1 * m2 + kC1, A2 = 2.0f * s12 + kC2;
-            const float B1 = m1 * m1 + m2 * m2 + kC1, B2 = s1 + s2 + kC2;
-            const float inv = 1.0f / (B1 * B2);
-            const float S = A1 * A2 * inv;
-            ssim_sum += S;
-            const size_t o = ((size_t)c * Ho + y) * Wo + x;      // planar per channel: coalesced in x
-            const size_t plane = (size_t)Ho * Wo * 3;
-            dmaps[o] = 2.0f * m2 * (A2 - A1) * inv - 2.0f * m1 * S * (1.0f / B1 - 1.0f / B2);  // d/d filt(X)
-            dmaps[plane + o] = -S / B2;                                                        // d/d filt(X^2)
-            dmaps[2 * plane + o] = 2.0f * A1 * inv;                                            // d/d filt(XY)
-          }
-        }
-        __syncthreads();
-    }
-    const float ts = block_sum(ssim_sum, scratch);
-    const float tl = block_sum(l1_sum, scratch);
-    const float td = block_sum(depth_sum, scratch);
-    if (threadIdx.x == 0) {
-        const int b = blockIdx.y * gridDim.x + blockIdx.x;
-        sums[3 * b] = ts;
-        sums[3 * b + 1] = tl;
-        sums[3 * b + 2] = td;
-    }
-}
-
-// Pass 1 as a SLIDING WINDOW (round 6; the tiled kernel above stays for -DTS_SSIM_ROWS=0).  One wave owns 64 columns
+// A SLIDING WINDOW (round 6).  One wave owns 64 columns
 // of the SSIM map for one colour channel and walks `seg` map rows from the top: a pixel row is read once (64 + 10
 // columns, the next rows already in flight), filtered horizontally through a wave-private LDS line - no workgroup
 // barrier anywhere - and the eleven most recent horizontally filtered rows of the five maps stay in REGISTERS (a ring,
 // the row loop unrolled by the window length so that every index is static), so the vertical pass costs no memory
 // traffic at all.  Image bytes read 1.16 x (columns) x (seg + 10) / seg (rows) instead of 1.72 x, a third of the
-// LDS traffic and none of the nine barriers of the tiled kernel, which ran at 1.8 TB/s of its own traffic (95 us at
+// LDS traffic and none of the nine barriers of the 32x32-tile kernel of rounds 1 - 5, which ran at 1.8 TB/s of its own traffic (95 us at
 // 1920 x 1080: three workgroups per CU, 2.7 rounds).  The three channel waves of a column block share a workgroup (and
 // so the L1 lines of the interleaved pixels); its fourth wave sums the depth term.  sums: {ssim, l1, depth l1} per wave at
 // sums[3 * ((seg * column_blocks + block) * 4 + wave)]; every pixel's L1 term is counted by exactly one wave.
-#ifndef TS_SSIM_ROWS
-#define TS_SSIM_ROWS 1
-#endif
 constexpr int kCols = 64;              // map columns per wave
 // Map rows per wave, chosen per image so that the launch is ONE round of resident workgroups (three per CU at 140 - 168
 // VGPRs): 1080p on 256 CUs: 30 column blocks x 25 segments of 43 rows = 750 <= 768.  A small image gets short segments
@@ -580,27 +445,20 @@ extern "C" {
 int64_t ts_photometric_ws_floats(int32_t height, int32_t width) {
     if (height <= kHalo || width <= kHalo) return 0;
     const int64_t ho = height - kHalo, wo = width - kHalo;
-    const int64_t seg = TS_SSIM_ROWS ? ssim_segment_rows((int)ho, (int)wo) : 1;
-    const int64_t tiles = TS_SSIM_ROWS ? kRowsWaves * ((wo + kCols - 1) / kCols) * ((ho + seg - 1) / seg)      // one triple per wave
-                                       : (int64_t)((width + kTile - 1) / kTile) * ((height + kTile - 1) / kTile);
-    return 3 * ho * wo * 3 + 3 * tiles;
+    const int64_t seg = ssim_segment_rows((int)ho, (int)wo);
+    const int64_t waves = kRowsWaves * ((wo + kCols - 1) / kCols) * ((ho + seg - 1) / seg);      // one triple per wave
+    return 3 * ho * wo * 3 + 3 * waves;
 }
 
 namespace {
-// pass 1 of the loss: per-wave (per-tile) sums behind the three partial-derivative maps in ws
+// pass 1 of the loss: per-wave sums behind the three partial-derivative maps in ws
 void launch_ssim_fwd(int height, int width, int xs, const float* image, const float* depth, const float* target,
                      const float* depth_target, float* ws, hipStream_t s) {
     const size_t plane3 = (size_t)3 * (height - kHalo) * (width - kHalo) * 3;
-    if (TS_SSIM_ROWS) {
-        const int seg = ssim_segment_rows(height - kHalo, width - kHalo);
-        const dim3 grid((width - kHalo + kCols - 1) / kCols, (height - kHalo + seg - 1) / seg);
-        hipLaunchKernelGGL(ssim_fwd_rows_kernel, grid, dim3(64 * kRowsWaves), 0, s, height, width, xs, seg, image, depth,
-                           target, depth_target, ws, ws + plane3);
-    } else {
-        const dim3 grid((width + kTile - 1) / kTile, (height + kTile - 1) / kTile);
-        hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(kThreads), 0, s, height, width, xs, image, depth, target,
-                           depth_target, ws, ws + plane3);
-    }
+    const int seg = ssim_segment_rows(height - kHalo, width - kHalo);
+    const dim3 grid((width - kHalo + kCols - 1) / kCols, (height - kHalo + seg - 1) / seg);
+    hipLaunchKernelGGL(ssim_fwd_rows_kernel, grid, dim3(64 * kRowsWaves), 0, s, height, width, xs, seg, image, depth,
+                       target, depth_target, ws, ws + plane3);
 }
 }  // namespace
 
