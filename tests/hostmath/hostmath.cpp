@@ -66,4 +66,54 @@ void hm_tile_bbox(int n, const float* xys, const float* radii, int tbx, int tby,
     }
 }
 
+// ---- the two alpha culls, with exactly the operands the kernels hand them ------------------------------------------
+// records: 6 floats per case, the packed record's words x, y, opacity, conic.xx, conic.xy, conic.yy.
+
+// raster.hip: stage_splat for ONE block rectangle per case.  rects: {x0, x1, y0, y1} inclusive sample positions.
+// out[i]: 1 = the block is kept, 0 = rejected (the opacity gate of stage_splat included: op <= 0, tau < -0.02).
+// The gate is a hand-written MIRROR of stage_splat's (op > 0, tau >= -0.02, geometric cull only for hA, hC > 0): a change
+// there must be repeated here.  tests/test_gpu_cull.py composites the same cases on the device, which binds the two.
+void hm_rect_may_contribute(int n, const float* records, const float* rects, int* out) {
+    for (int i = 0; i < n; ++i) {
+        const float* q = records + 6 * i;
+        const float* r = rects + 4 * i;
+        const float gx = q[0], gy = q[1], op = q[2];
+        const float hA = 0.5f * ts::kLog2e * q[3], B = ts::kLog2e * q[4], hC = 0.5f * ts::kLog2e * q[5];
+        out[i] = 0;
+        if (!(op > 0.0f)) continue;
+        const float tau = ts::fast_log2(op) + ts::kLog2_255;
+        if (!(tau >= -0.02f)) continue;
+        if (hA > 0.0f && hC > 0.0f)
+            out[i] = ts::rect_may_contribute(hA, B, hC, 0.5f / hA, 0.5f / hC, tau, gx, gy, r[0], r[1], r[2], r[3]) ? 1 : 0;
+        else
+            out[i] = 1;                                   // not a PSD conic: no geometric cull
+    }
+}
+
+// forms: hA, B, hC (log2 domain, hA, hC > 0); rects: xlo, xhi, ylo, yhi (offsets centre - sample)
+void hm_min_form_on_rect(int n, const float* forms, const float* rects, float* out) {
+    for (int i = 0; i < n; ++i) {
+        const float* f = forms + 3 * i;
+        const float* r = rects + 4 * i;
+        out[i] = ts::min_form_on_rect(f[0], f[1], f[2], 0.5f / f[0], 0.5f / f[2], r[0], r[1], r[2], r[3]);
+    }
+}
+
+// binning.hip: walk_chunk for one Gaussian per case.  boxes: minx, miny, maxx, maxy of ts::tile_bbox; rows of the box
+// are written to lo / hi at row_off[i] + (ty - miny): the kept tiles of tile row ty are [lo, hi) (hi <= lo: none;
+// cull_all: every row empty).
+void hm_tight_rows(int n, const float* records, const int* radii, const int* boxes, const int64_t* row_off,
+                   int* lo, int* hi) {
+    for (int i = 0; i < n; ++i) {
+        const float* q = records + 6 * i;
+        const int* b = boxes + 4 * i;
+        const ts::TightTest t(true, q[0], q[1], q[2], q[3], q[4], q[5], (float)radii[i]);
+        for (int ty = b[1]; ty < b[3]; ++ty) {
+            const int64_t k = row_off[i] + (ty - b[1]);
+            if (t.cull_all) { lo[k] = b[0]; hi[k] = b[0]; continue; }
+            t.row_range(ty, b[0], b[2], lo[k], hi[k]);
+        }
+    }
+}
+
 }  // extern "C"

@@ -173,65 +173,9 @@ inline int bin_window_tiles(int n, int num_tiles) {
 // compositing kernels ever see them.  Count and scatter make the same decisions (same code, same
 // inputs).  With splats == nullptr the lists are gsplat's bounding-box lists.
 //
-// The level set {alpha >= 1/255} is the ellipse  hA dx^2 + B dx dy + hC dy^2 <= tau  (log2 domain,
-// d = pixel - centre).  Instead of testing every tile of the box, each tile ROW gets the x-interval
-// of the ellipse over the row's y-band in closed form: for a fixed dy the ellipse is the interval
-// (-B dy -+ sqrt(disc(dy))) / (2 hA) with disc = 4 hA tau - D4 dy^2, D4 = 4 hA hC - B^2; its left
-// end is convex and its right end concave in dy, so over a band the union is spanned by the band's
-// two ends and, when they lie in the band, the ellipse's leftmost / rightmost points.  tau carries
-// the same slack as ts::rect_may_contribute (evaluated for the farthest pixel of the box) and the
-// interval is widened by kTightEps pixels, which makes the kept set a superset of every pixel whose
-// alpha test can pass in the compositing kernels.
-constexpr int kTilePix = 16;              // tile edge in pixels (rasterize.py:19-20)
-constexpr float kTightEps = 0.02f;
-struct TightTest {
-    bool cull_all, geometric;
-    float gx, gy, hA, B, tau4A, D4, inv2A, dymax, dxext, dy_left;
-    __device__ __forceinline__ TightTest(bool tight, const float4 q0, const float4 q1, float radius) {
-        cull_all = false; geometric = false;
-        gx = gy = hA = B = tau4A = D4 = inv2A = dymax = dxext = dy_left = 0.0f;
-        if (!tight) return;
-        gx = q0.x - ts::kPixOff; gy = q0.y - ts::kPixOff;      // (row_range works on pixel INDICES: sample = index + off)
-        hA = 0.5f * ts::kLog2e * q0.w; B = ts::kLog2e * q1.x;
-        const float hC = 0.5f * ts::kLog2e * q1.y;
-        const float op = q0.z;
-        float tau = __log2f(op) + ts::kLog2_255;
-        if (!(op > 0.0f) || !(tau >= -0.02f)) { cull_all = true; return; }
-        D4 = 4.0f * hA * hC - B * B;
-        // D4 = 4 hA hC (1 - rho^2) cancels for a rotated needle: its float32 relative error is ~2e-7 / (1 - rho^2),
-        // and the ellipse's extent sqrt(tau / D4) inherits half of it.  Below 1 - rho^2 = 1e-2 (axis ratio > 20 at
-        // 45 degrees) that error is no longer small against the slack of the test: keep the bounding box.
-        if (!(hA > 0.0f && hC > 0.0f && D4 > 1e-2f * (4.0f * hA * hC))) return;
-        const float far = radius + (float)kTilePix;                            // farthest pixel offset
-        tau += 0.02f + 4.0e-6f * (hA + hC + fabsf(B)) * far * far;
-        geometric = true;
-        inv2A = 0.5f / hA;
-        tau4A = 4.0f * hA * tau;
-        dymax = sqrtf(tau4A / D4) + kTightEps;
-        dxext = sqrtf(4.0f * hC * tau / D4);
-        dy_left = B * dxext / (2.0f * hC);           // dy of the leftmost point (rightmost: -dy_left)
-    }
-    // tiles [lo, hi) of tile row ty (clipped to [minx, maxx)) the ellipse can reach
-    __device__ __forceinline__ void row_range(int ty, int minx, int maxx, int& lo, int& hi) const {
-        lo = minx; hi = maxx;
-        if (!geometric) return;
-        const float a = fmaxf((float)(ty * kTilePix) - gy - kTightEps, -dymax);
-        const float b = fminf((float)(ty * kTilePix + kTilePix - 1) - gy + kTightEps, dymax);
-        if (a > b) { hi = lo; return; }
-        const float sa = sqrtf(fmaxf(tau4A - D4 * a * a, 0.0f)), sb = sqrtf(fmaxf(tau4A - D4 * b * b, 0.0f));
-        float left = fminf((-B * a - sa) * inv2A, (-B * b - sb) * inv2A);
-        float right = fmaxf((-B * a + sa) * inv2A, (-B * b + sb) * inv2A);
-        if (dy_left >= a && dy_left <= b) left = -dxext;
-        if (-dy_left >= a && -dy_left <= b) right = dxext;
-        left = fminf(left, right);                                   // rounding near a tangent band
-        const float xl = gx + left - kTightEps, xr = gx + right + kTightEps;
-        // tile tx holds sample positions 16 tx .. 16 tx + 15
-        const int tlo = (int)ceilf((xl - (float)(kTilePix - 1)) * (1.0f / kTilePix));
-        const int thi = (int)floorf(xr * (1.0f / kTilePix)) + 1;
-        lo = max(lo, tlo); hi = min(hi, thi);
-        if (hi < lo) hi = lo;
-    }
-};
+// The test itself is ts::TightTest in splat_math.h, beside ts::rect_may_contribute: the header compiles for the host
+// too, and tests/test_hostmath_cull.py checks every rejection against a float64 per-pixel evaluation.
+using ts::TightTest;
 
 // Walks the Gaussians of a chunk and calls emit(t) for every list (tile of the lists' shape, index t
 // inside the launch) a Gaussian is entered in.  Count and scatter replay the same walk, so they agree.
@@ -278,7 +222,7 @@ __device__ __forceinline__ void walk_chunk(int g0, int g1, const float* __restri
             const ts::TileBox b = ts::tile_bbox(xy[u].x, xy[u].y, (float)r[u], cam.tile_bounds_x,
                                                 cam.tile_bounds_y, cam.tile_row0, cam.tile_rows);
             if (b.maxy <= b.miny || b.maxx <= b.minx) continue;  // not in this stripe (its record was never written)
-            const TightTest tight(tight_lists, q0[u], q1[u], (float)r[u]);
+            const TightTest tight(tight_lists, q0[u].x, q0[u].y, q0[u].z, q0[u].w, q1[u].x, q1[u].y, (float)r[u]);
             if (tight.cull_all) continue;
             const int i = base + u * kBinThreads;
             for (int ty = b.miny; ty < b.maxy; ++ty) {
@@ -329,7 +273,7 @@ __device__ __forceinline__ void walk_chunk_balanced(int g0, int g1, const float*
                 const ts::TileBox b = ts::tile_bbox(xy.x, xy.y, (float)r, cam.tile_bounds_x, cam.tile_bounds_y,
                                                     cam.tile_row0, cam.tile_rows);
                 if (b.maxy > b.miny && b.maxx > b.minx) {
-                    const TightTest t(tight_lists, q0, q1, (float)r);
+                    const TightTest t(tight_lists, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, (float)r);
                     if (!t.cull_all) {
                         rows = b.maxy - b.miny;
                         miny = b.miny;
@@ -371,7 +315,7 @@ __device__ __forceinline__ void walk_chunk_balanced(int g0, int g1, const float*
             const int m = min(kItemCap, total - w0);
             for (int j = tid; j < m; j += kBinThreads) {
                 const int it = items[j], lt = it & 1023, k = it >> 10;
-                TightTest t(false, make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), 0.0f);
+                TightTest t(false, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f);
                 const float d0 = stash[0][lt];
                 t.geometric = d0 >= 0.0f;
                 t.dymax = d0;

@@ -287,6 +287,7 @@ __device__ __forceinline__ Staged stage_splat(bool have, const float4 q0, const 
     // positive-definite conic and opacity <= 0.99 neither can trigger (sigma >= 0 up to rounding,
     // alpha = opacity * exp(-sigma) <= opacity), and the kernels take a leaner wave-uniform path.
     const bool general = !(s.hA > 0.0f && s.hC > 0.0f && 4.0f * s.hA * s.hC > s.B * s.B && op <= 0.99f);
+    // (this gate is mirrored by hand in tests/hostmath/hostmath.cpp: hm_rect_may_contribute - change both)
     if (have && op > 0.0f) {
         const float tau = s.lo + kLog2_255;            // sigma' <= tau  <=>  alpha >= 1/255
         if (tau >= -0.02f) {

@@ -413,4 +413,74 @@ TS_HD bool rect_may_contribute(float hA, float B, float hC, float inv2A, float i
     return m <= tau + 0.02f + 4.0e-6f * mag;
 }
 
+// log2 as the kernels take it: the hardware's v_log_f32 (1 ulp) on the device, libm on the host.
+TS_HD float fast_log2(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __log2f(x);
+#else
+    return log2f(x);
+#endif
+}
+
+// ---- tight tile binning (binning.hip: walk_chunk, walk_chunk_balanced) -------------------------------------------
+// The level set {alpha >= 1/255} is the ellipse  hA dx^2 + B dx dy + hC dy^2 <= tau  (log2 domain,
+// d = pixel - centre).  Instead of testing every tile of the box, each tile ROW gets the x-interval
+// of the ellipse over the row's y-band in closed form: for a fixed dy the ellipse is the interval
+// (-B dy -+ sqrt(disc(dy))) / (2 hA) with disc = 4 hA tau - D4 dy^2, D4 = 4 hA hC - B^2; its left
+// end is convex and its right end concave in dy, so over a band the union is spanned by the band's
+// two ends and, when they lie in the band, the ellipse's leftmost / rightmost points.  tau carries
+// the same slack as rect_may_contribute (evaluated for the farthest pixel of the box) and the
+// interval is widened by kTightEps pixels, which makes the kept set a superset of every pixel whose
+// alpha test can pass in the compositing kernels.  Operands: the packed record's words x, y, opacity,
+// conic.xx, conic.xy, conic.yy and the integer radius.
+constexpr int kTilePix = 16;              // tile edge in pixels (rasterize.py:19-20)
+constexpr float kTightEps = 0.02f;
+struct TightTest {
+    bool cull_all, geometric;
+    float gx, gy, hA, B, tau4A, D4, inv2A, dymax, dxext, dy_left;
+    TS_HD TightTest(bool tight, float x, float y, float op, float cxx, float cxy, float cyy, float radius) {
+        cull_all = false; geometric = false;
+        gx = gy = hA = B = tau4A = D4 = inv2A = dymax = dxext = dy_left = 0.0f;
+        if (!tight) return;
+        gx = x - kPixOff; gy = y - kPixOff;          // (row_range works on pixel INDICES: sample = index + off)
+        hA = 0.5f * kLog2e * cxx; B = kLog2e * cxy;
+        const float hC = 0.5f * kLog2e * cyy;
+        float tau = fast_log2(op) + kLog2_255;
+        if (!(op > 0.0f) || !(tau >= -0.02f)) { cull_all = true; return; }
+        D4 = 4.0f * hA * hC - B * B;
+        // D4 = 4 hA hC (1 - rho^2) cancels for a rotated needle: its float32 relative error is ~2e-7 / (1 - rho^2),
+        // and the ellipse's extent sqrt(tau / D4) inherits half of it.  Below 1 - rho^2 = 1e-2 (axis ratio > 20 at
+        // 45 degrees) that error is no longer small against the slack of the test: keep the bounding box.
+        if (!(hA > 0.0f && hC > 0.0f && D4 > 1e-2f * (4.0f * hA * hC))) return;
+        const float far = radius + (float)kTilePix;                            // farthest pixel offset
+        tau += 0.02f + 4.0e-6f * (hA + hC + fabsf(B)) * far * far;
+        geometric = true;
+        inv2A = 0.5f / hA;
+        tau4A = 4.0f * hA * tau;
+        dymax = sqrtf(tau4A / D4) + kTightEps;
+        dxext = sqrtf(4.0f * hC * tau / D4);
+        dy_left = B * dxext / (2.0f * hC);           // dy of the leftmost point (rightmost: -dy_left)
+    }
+    // tiles [lo, hi) of tile row ty (clipped to [minx, maxx)) the ellipse can reach
+    TS_HD void row_range(int ty, int minx, int maxx, int& lo, int& hi) const {
+        lo = minx; hi = maxx;
+        if (!geometric) return;
+        const float a = fmaxf((float)(ty * kTilePix) - gy - kTightEps, -dymax);
+        const float b = fminf((float)(ty * kTilePix + kTilePix - 1) - gy + kTightEps, dymax);
+        if (a > b) { hi = lo; return; }
+        const float sa = sqrtf(fmaxf(tau4A - D4 * a * a, 0.0f)), sb = sqrtf(fmaxf(tau4A - D4 * b * b, 0.0f));
+        float left = fminf((-B * a - sa) * inv2A, (-B * b - sb) * inv2A);
+        float right = fmaxf((-B * a + sa) * inv2A, (-B * b + sb) * inv2A);
+        if (dy_left >= a && dy_left <= b) left = -dxext;
+        if (-dy_left >= a && -dy_left <= b) right = dxext;
+        left = fminf(left, right);                                   // rounding near a tangent band
+        const float xl = gx + left - kTightEps, xr = gx + right + kTightEps;
+        // tile tx holds sample positions 16 tx .. 16 tx + 15
+        const int tlo = (int)ceilf((xl - (float)(kTilePix - 1)) * (1.0f / kTilePix));
+        const int thi = (int)floorf(xr * (1.0f / kTilePix)) + 1;
+        lo = lo < tlo ? tlo : lo; hi = hi > thi ? thi : hi;
+        if (hi < lo) hi = lo;
+    }
+};
+
 }  // namespace ts
