@@ -399,6 +399,18 @@ int ts_frame_fwd_composite(const ts_frame* f, void* stream);
 int ts_frame_bwd_composite(const ts_frame* f, void* stream);
 int ts_frame_bwd_params(const ts_frame* f, void* stream);
 
+/* ENTRY PROBE: while one is set, every executor function (ts_frame_*, ts_shard_*) calls fn(entry, 0, user) before and
+ * fn(entry, 1, user) after each per-stage entry it issues - also when that entry fails and the executor returns early,
+ * so the calls always pair up.  `entry` is the entry's name in a per-entry table: ts_tile_offsets also stands for
+ * ts_tile_offsets_stats, ts_sort_tiles for ts_sort_tiles_above, ts_raster_fwd / ts_raster_bwd for whichever compositing
+ * launch the frame takes, ts_route_count for ts_route_count_padded, ts_owner_fwd_fused / ts_owner_bwd_fused for
+ * ts_shard_owner_*_fused.  The executor's own copies and fills (the count word, the send buffer) lie outside every
+ * pair.  What ops.kernel_timer records events with: the table times the frame that runs.  One probe per process, seen by
+ * every thread (a frame's backward pass may run on another thread than its forward pass); fn must not throw.  NULL
+ * switches it off: an entry then costs one relaxed load.  Returns 0. */
+typedef void (*ts_entry_probe)(const char* entry, int32_t end, void* user);
+int ts_set_entry_probe(ts_entry_probe fn, void* user);
+
 /* ============== Gaussian-sharded multi-GPU frame (csrc/shard.hip) =====================
  * One rank per GPU owns a contiguous range of Gaussians and one stripe of tile rows.  Per frame it projects and
  * colours its own Gaussians (ts_project_fwd / ts_colors_pack_fwd with the FULL-frame camera), routes a 64-byte

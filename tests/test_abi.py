@@ -150,6 +150,27 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert lib.ts_bin_scatter(-1, None, None, None, cam, None, None, None, None) == -1
 
 
+def test_entry_probe_brackets_every_entry_the_executor_issues():
+    """ts_set_entry_probe: declared, exported and bound; the executor reports an entry before and after it issues it -
+    also when the entry refuses its arguments and the executor returns early - and nothing once the probe is removed."""
+    from tinysplat_amd import _lib
+    assert "ts_set_entry_probe" in _declared() and "ts_set_entry_probe" in _lib.SIGNATURES
+    lib = _lib.load()
+    seen = []
+    probe = _lib.ENTRY_PROBE(lambda entry, end, user: seen.append((entry.decode(), end)))
+    assert lib.ts_set_entry_probe(probe, None) == 0
+    try:
+        assert lib.ts_frame_fwd_project(None, None) == -1 and seen == []      # refused by the executor: no entry was issued
+        fr = _lib.TsFrame()
+        fr.n, fr.channels, fr.num_bases = 4, 3, 1                             # passes the executor's check; no pointer is set,
+        assert lib.ts_frame_fwd_project(ctypes.byref(fr), None) == -1         # so ts_project_fwd refuses before any launch
+        assert seen == [("ts_project_fwd", 0), ("ts_project_fwd", 1)]
+    finally:
+        assert lib.ts_set_entry_probe(None, None) == 0
+    del seen[:]
+    assert lib.ts_frame_fwd_project(ctypes.byref(fr), None) == -1 and seen == []
+
+
 def test_ops_refuse_cpu_tensors_and_product_never_imports_the_oracle():
     import tinysplat_amd
     with pytest.raises(RuntimeError, match="no CPU fallback"):

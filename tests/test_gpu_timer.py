@@ -1,0 +1,168 @@
+"""``ops.kernel_timer`` watches the frame executor (csrc/frame.hip) through the library's entry probe instead of replacing
+it: a frame rendered while the timer records is, bit for bit, the frame rendered without it - image, compositing state,
+every gradient, a fused-Adam training step, the stripes of a sharded frame - and the table it returns names every entry
+the executor issued, once per launch.  The key lists and launch counts below are those of the commit before the probe
+existed, whose timed frames issued the entries from Python (its ``frame._steps_*`` functions and the timed branches of
+``sharded.py``'s stage functions name them one by one)."""
+import math
+
+import pytest
+import torch
+
+from tinysplat_amd import frame
+from tinysplat_amd.ops import kernel_timer
+from tinysplat_amd.rasterizer import GaussianRasterizer, camera_on_device
+from tinysplat_amd.sharded import simulate_frame
+
+from helpers import scene_args
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+W = H = 256                 # 256 16x16 tiles: a "small launch" (split) unless SPLIT_BLOCKS_BELOW = 0
+NAMES = ("means", "colors_dc", "colors_rest", "scales", "quats", "opacities")
+
+# what one single-GPU frame issues, forward then backward
+FRAME_KEYS = ["ts_project_fwd", "ts_scan_tiles", "ts_colors_pack_fwd", "ts_bin_count", "ts_tile_offsets", "ts_bin_scatter",
+              "ts_sort_tiles", "ts_raster_fwd", "ts_raster_bwd", "ts_reduce_partials", "ts_sh_colors_bwd", "ts_project_bwd"]
+# a TrainStep: the loss on the two planes, and the parameter stage that applies Adam itself
+TRAIN_KEYS = FRAME_KEYS[:-2] + ["ts_sh_colors_bwd_adam", "ts_project_bwd_adam", "ts_photometric_loss_rgbd",
+                                "ts_photometric_loss_reduce"]
+# two ranks of a sharded frame with small shards, each entry once per rank
+SHARD_KEYS = ["ts_owner_fwd_fused", "ts_route_pack", "ts_import_records", "ts_scan_tiles", "ts_import_pack", "ts_bin_count",
+              "ts_tile_offsets", "ts_bin_scatter", "ts_sort_tiles", "ts_raster_fwd", "ts_raster_bwd",
+              "ts_reduce_partials_rows", "ts_owner_bwd_fused"]
+
+# name -> (frame.* constants, scene size, planes, tile rows, channels)
+CASES = {
+    "default": ({"LIST_SEGMENTS_FROM": 32}, 3000, False, None, 4),      # small launch: cooperative split, list segments
+    "full16": ({"SPLIT_BLOCKS_BELOW": 0}, 3000, False, None, 4),        # 16x16 lists, in-kernel sort, survivor lists
+    "wide": ({"WIDE_TILES": 2}, 3000, False, None, 4),
+    "planes": ({}, 3000, True, None, 4),
+    "stripe": ({}, 3000, False, (4, 12), 3),
+    "empty": ({}, 0, False, None, 4),
+}
+
+
+def _set(monkeypatch, consts):
+    """the constants of a case; the launch policy starts from no earlier frame (what other tests rendered on the device
+    must not decide the list shape here)"""
+    for name, value in {"WIDE_TILES": 0, **consts}.items():
+        monkeypatch.setattr(frame, name, value)
+    for name in ("_pairs_per_tile", "_longest_list", "_stats_mode"):
+        monkeypatch.setattr(frame, name, {})
+
+
+def _timed(fn, timed):
+    """-> (fn(), the timer's table or None)"""
+    if timed:
+        kernel_timer.start()
+    try:
+        out = fn()
+    finally:
+        table = kernel_timer.stop() if timed else None
+    return out, table
+
+
+def render_case(case, timed):
+    """One forward + backward frame of ``case`` -> ([tensors to compare], ts_frame flags, table)."""
+    _, n, planes, rows, ch = CASES[case]
+    model, cam = scene_args(n, 1, W, H, seed=21, scale_mult=12.0)
+    md = model.to(DEV).requires_grad_(True)
+    view, projview, origin = camera_on_device(cam, torch.device(DEV))
+    args = (view[:3, :], projview, origin, cam.f_x, cam.f_y, W, H)
+    rows_px = H if rows is None else 16 * (rows[1] - rows[0])
+    g = torch.Generator().manual_seed(22)
+    w_img = torch.rand(rows_px, W, ch, generator=g).to(DEV)
+
+    def run():
+        if planes:
+            rgb, depth, xys, _ = frame.render_frame_planes(md, *args)
+            images, loss = [rgb, depth], (rgb * w_img[..., :3]).sum() + (depth * w_img[..., 3]).sum()
+        else:
+            img, xys, _ = frame.render_frame(md, *args, ch == 4, tile_rows=rows)
+            images, loss = [img], (img * w_img).sum()
+        F = images[0].grad_fn.frame
+        base, nbytes = F.wf.data_ptr(), 4 * rows_px * W          # final_Ts / final_index live in the frame's workspace
+        state = [F.wf[F.fr.final_Ts - base:][:nbytes].clone(), F.wf[F.fr.final_index - base:][:nbytes].clone()]
+        loss.backward()
+        torch.cuda.synchronize()
+        return [t.detach() for t in images] + state + [p.grad for p in md.parameters()] + [xys.grad], F.fr.flags
+    (outs, flags), table = _timed(run, timed)
+    return outs, flags, table
+
+
+def _same(a, b):
+    assert len(a) == len(b)
+    for x, y in zip(a, b):
+        assert x.shape == y.shape and torch.equal(x, y)
+
+
+def _check_table(table, keys, launches=1):
+    assert sorted(table) == sorted(keys)
+    for key, (count, mean_ms) in table.items():
+        assert count == launches, (key, count)
+        assert math.isfinite(mean_ms) and mean_ms >= 0.0, (key, mean_ms)
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_timed_frame_is_the_untimed_frame_bit_for_bit(case, monkeypatch):
+    _set(monkeypatch, CASES[case][0])
+    plain, flags0, _ = render_case(case, False)
+    _set(monkeypatch, CASES[case][0])
+    timed, flags1, table = render_case(case, True)
+    _same(plain, timed)
+    assert flags0 == flags1
+    if case == "default":
+        assert frame.last_segments[0] > 1                     # the backward pass did replay list segments
+    if case == "full16":
+        assert flags1 & 512                                   # the timed frame kept its survivor lists
+        _check_table(table, FRAME_KEYS)
+        render_case(case, False)                              # a frame after stop() is nobody's business
+        assert kernel_timer.records == {}
+    if case == "empty":                                       # nothing listed: no scatter, no sort
+        _check_table(table, [k for k in FRAME_KEYS if k not in ("ts_bin_scatter", "ts_sort_tiles")])
+
+
+def test_timed_training_step_is_the_untimed_step(monkeypatch):
+    from tinysplat_amd.synthetic import make_scene
+    from tinysplat_amd.training import TrainStep
+    n, sh = 3000, 1
+    target, cam = make_scene(n, sh, W, H, seed=21, scale_mult=12.0)
+    with torch.no_grad():
+        tgt, extras = GaussianRasterizer(target.to(DEV), None, device=torch.device(DEV))(cam, None, sh)
+    tgt, tgt_d = tgt.clone(), extras["depth"].clone()
+    gen = torch.Generator().manual_seed(23)
+    start, _ = make_scene(n, sh, W, H, seed=21, scale_mult=12.0)
+    start.colors_dc = start.colors_dc + 0.3 * torch.randn(n, 3, generator=gen)
+    start.means = start.means + 0.02 * torch.randn(n, 3, generator=gen)
+    runs = []
+    for timed in (False, True):
+        _set(monkeypatch, {})
+        model = start.to(DEV)
+        for nm in NAMES:
+            setattr(model, nm, getattr(model, nm).detach().clone())
+        step = TrainStep(model, DEV)
+        out, table = _timed(lambda: step(cam, tgt, tgt_d), timed)
+        assert step.optimizer.fused_steps == 1                # the frame's backward pass applied the update
+        runs.append((model, out))
+    (m0, o0), (m1, o1) = runs
+    assert torch.equal(o0["loss"], o1["loss"]) and torch.equal(o0["xys_grad"], o1["xys_grad"])
+    for nm in NAMES:
+        assert torch.equal(getattr(m0, nm), getattr(m1, nm)), nm
+    _check_table(table, TRAIN_KEYS)
+
+
+def test_timed_sharded_frame_is_the_untimed_frame(monkeypatch):
+    model, cam = scene_args(2000, 1, W, H, seed=24, scale_mult=12.0)
+    model = model.to(DEV)
+    g = torch.Generator().manual_seed(25)
+    w_img = torch.rand(H, W, 3, generator=g).to(DEV)
+    runs = []
+    for timed in (False, True):
+        _set(monkeypatch, {})
+        (images, _, grads, v_xy, _), table = _timed(
+            lambda: simulate_frame(model, cam, (W, H), DEV, 2, lambda k, img, rows: w_img[rows[0]:rows[1]]), timed)
+        torch.cuda.synchronize()
+        runs.append(list(images) + list(grads) + [v_xy])
+    _same(*runs)
+    _check_table(table, SHARD_KEYS, launches=2)

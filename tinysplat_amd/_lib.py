@@ -94,6 +94,8 @@ class TsRankStep(ctypes.Structure):
 
 _RANK = POINTER(TsRankStep)
 
+ENTRY_PROBE = ctypes.CFUNCTYPE(None, ctypes.c_char_p, c_int32, c_void_p)      # ts_entry_probe
+
 # name -> (restype, argtypes); mirrors include/tinysplat_hip.h declaration by declaration
 SIGNATURES = {
     "ts_abi_version": (c_int32, []),
@@ -174,6 +176,7 @@ SIGNATURES = {
     "ts_frame_fwd_composite": (c_int32, [_FRAME, _P]),
     "ts_frame_bwd_composite": (c_int32, [_FRAME, _P]),
     "ts_frame_bwd_params": (c_int32, [_FRAME, _P]),
+    "ts_set_entry_probe": (c_int32, [_P, _P]),       # (an ENTRY_PROBE instance, or None)
     "ts_knn_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ts_knn": (c_int32, [c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P, _P]),
     "ts_init_from_points": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

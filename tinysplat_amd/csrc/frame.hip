@@ -7,12 +7,15 @@
 // survivor lists to the same launches) in the order frame.py used to call them one by one through
 // ctypes.  What it buys is host time: a frame is ~30 kernel launches, and issuing them from Python
 // costs ~0.45 ms per frame - more than the GPU needs for a 100 k-Gaussian scene or for one tile
-// stripe of a multi-GPU frame.  From here a launch costs ~2 us.  The one host round trip of the path
+// stripe of a multi-GPU frame.  From here a launch costs ~2 us.  This file is the only description of a
+// frame's launches: a per-entry timing table (ops.kernel_timer, bench.py --full) watches these very calls
+// through the entry probe below - it times the frame that runs, not a copy of it.  The one host round trip of the path
 // (the intersection count that sizes the per-intersection buffers) stays with the caller: the scan kernel
 // stores it into the caller's mapped pinned word (ts_frame_fwd_project), where the caller polls it between
 // _prepare and _composite.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdlib>
 // roctx is optional: a ROCm install without rocprofiler-sdk still builds and loads the library (ranges become no-ops)
 #if !defined(TS_NO_ROCTX) && __has_include(<rocprofiler-sdk-roctx/roctx.h>)
@@ -35,6 +38,32 @@ struct TsRange {
     explicit TsRange(const char*) {}
 #endif
 };
+
+// ENTRY PROBE (ts_set_entry_probe): a process-wide callback around every per-stage entry the executor calls - not
+// thread-local: autograd runs a frame's backward pass on its device thread.  Without a probe an entry costs one
+// relaxed load and a branch.  The guard keeps the probe it saw on the way in, so the pairs balance on every return
+// path (TS_TRY's early ones included) and across a ts_set_entry_probe from another thread.
+static std::atomic<ts_entry_probe> g_probe{nullptr};
+static std::atomic<void*> g_probe_user{nullptr};
+
+struct TsEntry {
+    explicit TsEntry(const char* label) : fn_(g_probe.load(std::memory_order_relaxed)), label_(label) {
+        if (fn_) {
+            std::atomic_thread_fence(std::memory_order_acquire);
+            user_ = g_probe_user.load(std::memory_order_relaxed);
+            fn_(label_, 0, user_);
+        }
+    }
+    ~TsEntry() {
+        if (fn_) fn_(label_, 1, user_);
+    }
+    ts_entry_probe fn_;
+    const char* label_;
+    void* user_ = nullptr;
+};
+// `label` is the key the timing table files the entry under (bench.py: STAGE_OF), not always the callee's name; the
+// temporary lives until `call` has returned
+#define TS_ENTRY(label, call) ((void)TsEntry(label), (call))
 
 #define TS_TRY(call)                 \
     do {                             \
@@ -98,17 +127,26 @@ extern "C" {
 
 int32_t ts_frame_struct_bytes(void) { return (int32_t)sizeof(ts_frame); }
 
+int ts_set_entry_probe(ts_entry_probe fn, void* user) {
+    // the context first: an entry that sees `fn` (TsEntry's acquire fence) also sees its `user`
+    g_probe_user.store(user, std::memory_order_relaxed);
+    g_probe.store(fn, std::memory_order_release);
+    return 0;
+}
+
 int ts_frame_fwd_project(const ts_frame* f, void* stream) {
     TsRange range_("ts_frame_fwd_project");
     if (bad(f)) return TS_E_BADARG;
     // flags 3: log-scales and raw quaternions go in as they are (rasterize.py:72-73 folded into the kernel);
     // cov3d is not produced (the adapter discards it, rasterize.py:32)
-    TS_TRY(ts_project_fwd(f->n, f->means, f->scales, f->quats, f->view34, f->projview, &f->cam, 3, f->xys,
-                          f->depths, f->radii, f->conics, f->num_tiles_hit, nullptr, stream));
+    TS_TRY(TS_ENTRY("ts_project_fwd",
+                    ts_project_fwd(f->n, f->means, f->scales, f->quats, f->view34, f->projview, &f->cam, 3, f->xys,
+                                   f->depths, f->radii, f->conics, f->num_tiles_hit, nullptr, stream)));
     // the count goes to the caller's pinned word from the scan kernel itself when that memory is mapped
     // into the device's address space (hipHostMalloc'd memory is); otherwise by a 4-byte copy
     int32_t* total_dev = f->total_host ? mapped_pointer(f->total_host) : nullptr;
-    TS_TRY(ts_scan_tiles(f->n, f->num_tiles_hit, f->cum_tiles_hit, f->scan_ws, total_dev, stream));
+    TS_TRY(TS_ENTRY("ts_scan_tiles",
+                    ts_scan_tiles(f->n, f->num_tiles_hit, f->cum_tiles_hit, f->scan_ws, total_dev, stream)));
     if (f->n > 0 && f->total_host && !total_dev) {
         const hipError_t e = hipMemcpyAsync(f->total_host, f->cum_tiles_hit + (f->n - 1), sizeof(int32_t),
                                             hipMemcpyDeviceToHost, (hipStream_t)stream);
@@ -122,13 +160,15 @@ int ts_frame_fwd_prepare(const ts_frame* f, void* stream) {
     if (bad(f)) return TS_E_BADARG;
     // colour stage and record packing in one launch; channel 3 of an RGB + depth frame is the depth itself
     // (rasterize.py:48-50), taken from `depths`
-    TS_TRY(ts_colors_pack_fwd(f->n, f->sh_degree, f->num_bases, f->means, f->origin, f->colors_dc,
-                              f->num_bases > 1 ? f->colors_rest : nullptr, f->sh_mask,
-                              (f->flags & TS_FRAME_STRIPE) ? f->num_tiles_hit : nullptr, f->channels,
-                              TS_RASTER_LOGIT_OPACITY, f->xys, f->radii, f->conics, f->opacities, f->cum_tiles_hit,
-                              &f->cam, f->channels == 4 ? f->depths : nullptr, f->splats, stream));
+    TS_TRY(TS_ENTRY("ts_colors_pack_fwd",
+                    ts_colors_pack_fwd(f->n, f->sh_degree, f->num_bases, f->means, f->origin, f->colors_dc,
+                                       f->num_bases > 1 ? f->colors_rest : nullptr, f->sh_mask,
+                                       (f->flags & TS_FRAME_STRIPE) ? f->num_tiles_hit : nullptr, f->channels,
+                                       TS_RASTER_LOGIT_OPACITY, f->xys, f->radii, f->conics, f->opacities,
+                                       f->cum_tiles_hit, &f->cam, f->channels == 4 ? f->depths : nullptr, f->splats,
+                                       stream)));
     const float* tight = (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr;
-    TS_TRY(ts_bin_count(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, stream));
+    TS_TRY(TS_ENTRY("ts_bin_count", ts_bin_count(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, stream)));
     // (TS_FRAME_LIST_STATS: the longest list goes to the word behind the count word - read a frame later by the caller's
     // launch policy, never waited for)
     int32_t* longest = nullptr;
@@ -136,7 +176,9 @@ int ts_frame_fwd_prepare(const ts_frame* f, void* stream) {
         int32_t* dev = mapped_pointer(f->total_host);
         if (dev) longest = dev + 1;
     }
-    TS_TRY(ts_tile_offsets_stats(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->cum_tiles_hit, f->capacity, longest, stream));
+    TS_TRY(TS_ENTRY("ts_tile_offsets",
+                    ts_tile_offsets_stats(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->cum_tiles_hit, f->capacity,
+                                          longest, stream)));
     return 0;
 }
 
@@ -152,24 +194,31 @@ int ts_frame_fwd_composite(const ts_frame* f, void* stream) {
     if (f->num_intersects > 0) {
         const float* tight = (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr;
         // the sorted-id buffer is dead until the sort: it carries the ids between the two scatter hops
-        TS_TRY(ts_bin_scatter(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, f->bucket_ids,
-                              (f->flags & TS_FRAME_DIRECT_SCATTER) ? nullptr : f->gaussian_ids_sorted, stream));
+        TS_TRY(TS_ENTRY("ts_bin_scatter",
+                        ts_bin_scatter(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, f->bucket_ids,
+                                       (f->flags & TS_FRAME_DIRECT_SCATTER) ? nullptr : f->gaussian_ids_sorted,
+                                       stream)));
         int32_t* counter = f->bin_ws + (ts_bin_ws_ints(f->n, num_tiles(f)) - 1);
         if (fused_sort)
-            TS_TRY(ts_sort_tiles_above(num_tiles(f), f->tile_bins, f->depths, f->bucket_ids, f->gaussian_ids_sorted,
-                                       f->bin_ws, counter, stream));
+            TS_TRY(TS_ENTRY("ts_sort_tiles",
+                            ts_sort_tiles_above(num_tiles(f), f->tile_bins, f->depths, f->bucket_ids,
+                                                f->gaussian_ids_sorted, f->bin_ws, counter, stream)));
         else
-            TS_TRY(ts_sort_tiles(num_tiles(f), f->tile_bins, f->depths, f->bucket_ids, f->gaussian_ids_sorted,
-                                 f->bin_ws, counter, stream));
+            TS_TRY(TS_ENTRY("ts_sort_tiles",
+                            ts_sort_tiles(num_tiles(f), f->tile_bins, f->depths, f->bucket_ids, f->gaussian_ids_sorted,
+                                          f->bin_ws, counter, stream)));
     }
     if (fused_sort)
-        return ts_surv::raster_fwd_sort(f->channels, raster_flags(f), &f->cam, f->tile_bins, f->bucket_ids, f->depths,
-                                        f->gaussian_ids_sorted, f->splats, f->background, f->out_img,
-                                        planes ? f->out_depth : nullptr, f->final_Ts, f->final_index, f->clamp_mask,
-                                        survivors(f) ? f->survivors : nullptr, stream);
-    return ts_raster_fwd_planes(f->channels, raster_flags(f), &f->cam, f->tile_bins, f->gaussian_ids_sorted, f->splats,
-                                f->background, f->out_img, planes ? f->out_depth : nullptr, f->final_Ts,
-                                f->final_index, f->clamp_mask, stream);
+        return TS_ENTRY("ts_raster_fwd",
+                        ts_surv::raster_fwd_sort(f->channels, raster_flags(f), &f->cam, f->tile_bins, f->bucket_ids,
+                                                 f->depths, f->gaussian_ids_sorted, f->splats, f->background,
+                                                 f->out_img, planes ? f->out_depth : nullptr, f->final_Ts,
+                                                 f->final_index, f->clamp_mask, survivors(f) ? f->survivors : nullptr,
+                                                 stream));
+    return TS_ENTRY("ts_raster_fwd",
+                    ts_raster_fwd_planes(f->channels, raster_flags(f), &f->cam, f->tile_bins, f->gaussian_ids_sorted,
+                                         f->splats, f->background, f->out_img, planes ? f->out_depth : nullptr,
+                                         f->final_Ts, f->final_index, f->clamp_mask, stream));
 }
 
 int ts_frame_bwd_composite(const ts_frame* f, void* stream) {
@@ -177,42 +226,52 @@ int ts_frame_bwd_composite(const ts_frame* f, void* stream) {
     if (bad(f) || f->num_intersects < 0) return TS_E_BADARG;
     const bool planes = (f->flags & TS_FRAME_PLANES) != 0;
     const bool surv = survivors(f);
-    TS_TRY(ts_surv::raster_bwd(f->channels,
-                               ((raster_flags(f) & ~(TS_RASTER_CLAMP_RGB | TS_RASTER_SPLIT_BLOCKS)) | bwd_split(f)) |
-                                   TS_RASTER_FLAG_GEN(f->flag_gen),
-                               f->num_intersects, &f->cam, f->tile_bins, f->gaussian_ids_sorted, f->splats,
-                               f->background, f->final_Ts, f->final_index, f->v_out_img,
-                               planes ? f->v_out_depth : nullptr, planes ? 1 : 0, nullptr, f->clamp_mask, f->partials,
-                               f->row_flags, surv ? f->bucket_ids : nullptr, surv ? f->survivors : nullptr, stream));
+    TS_TRY(TS_ENTRY("ts_raster_bwd",
+                    ts_surv::raster_bwd(f->channels,
+                                        ((raster_flags(f) & ~(TS_RASTER_CLAMP_RGB | TS_RASTER_SPLIT_BLOCKS)) | bwd_split(f)) |
+                                            TS_RASTER_FLAG_GEN(f->flag_gen),
+                                        f->num_intersects, &f->cam, f->tile_bins, f->gaussian_ids_sorted, f->splats,
+                                        f->background, f->final_Ts, f->final_index, f->v_out_img,
+                                        planes ? f->v_out_depth : nullptr, planes ? 1 : 0, nullptr, f->clamp_mask,
+                                        f->partials, f->row_flags, surv ? f->bucket_ids : nullptr,
+                                        surv ? f->survivors : nullptr, stream)));
     const bool stripe = (f->flags & TS_FRAME_STRIPE) != 0;
-    return ts_reduce_partials(f->n, f->channels,
-                              TS_RASTER_LOGIT_OPACITY | bwd_split(f) | TS_RASTER_FLAG_GEN(f->flag_gen),
-                              f->num_tiles_hit, f->cum_tiles_hit, f->partials, f->row_flags, f->splats, f->v_xy,
-                              f->v_conic, f->v_colors, f->v_opacity, f->channels == 4 ? f->v_depth : nullptr,
-                              stripe ? f->sh_mask : nullptr, stream);
+    return TS_ENTRY("ts_reduce_partials",
+                    ts_reduce_partials(f->n, f->channels,
+                                       TS_RASTER_LOGIT_OPACITY | bwd_split(f) | TS_RASTER_FLAG_GEN(f->flag_gen),
+                                       f->num_tiles_hit, f->cum_tiles_hit, f->partials, f->row_flags, f->splats,
+                                       f->v_xy, f->v_conic, f->v_colors, f->v_opacity,
+                                       f->channels == 4 ? f->v_depth : nullptr, stripe ? f->sh_mask : nullptr, stream));
 }
 
 int ts_frame_bwd_params(const ts_frame* f, void* stream) {
     TsRange range_("ts_frame_bwd_params");
     if (bad(f)) return TS_E_BADARG;
-    TS_TRY(ts_sh_colors_bwd(f->n, f->sh_degree, f->num_bases, f->means, f->origin,
-                            (f->flags & TS_FRAME_STRIPE) ? nullptr : f->sh_mask, f->v_colors,
-                            f->v_colors_dc, f->num_bases > 1 ? f->v_colors_rest : nullptr, stream));
-    return ts_project_bwd(f->n, f->means, f->scales, f->quats, f->view34, f->projview, &f->cam, 3, f->radii,
-                          f->v_xy, f->v_depth, f->v_conic, nullptr, f->v_means, f->v_scales, f->v_quats, stream);
+    TS_TRY(TS_ENTRY("ts_sh_colors_bwd",
+                    ts_sh_colors_bwd(f->n, f->sh_degree, f->num_bases, f->means, f->origin,
+                                     (f->flags & TS_FRAME_STRIPE) ? nullptr : f->sh_mask, f->v_colors, f->v_colors_dc,
+                                     f->num_bases > 1 ? f->v_colors_rest : nullptr, stream)));
+    return TS_ENTRY("ts_project_bwd",
+                    ts_project_bwd(f->n, f->means, f->scales, f->quats, f->view34, f->projview, &f->cam, 3, f->radii,
+                                   f->v_xy, f->v_depth, f->v_conic, nullptr, f->v_means, f->v_scales, f->v_quats,
+                                   stream));
 }
 
 int ts_frame_bwd_params_adam(const ts_frame* f, const ts_adam* adam, void* stream) {
     TsRange range_("ts_frame_bwd_params_adam");
     if (bad(f) || !adam) return TS_E_BADARG;
     // (the colour stage reads the means for its view directions: it runs BEFORE the projection's pass moves them)
-    TS_TRY(ts_sh_colors_bwd_adam(f->n, f->sh_degree, f->num_bases, f->means, f->origin,
-                                 (f->flags & TS_FRAME_STRIPE) ? nullptr : f->sh_mask, f->v_colors,
-                                 const_cast<float*>(f->colors_dc), f->num_bases > 1 ? const_cast<float*>(f->colors_rest) : nullptr,
-                                 adam, stream));
-    return ts_project_bwd_adam(f->n, const_cast<float*>(f->means), const_cast<float*>(f->scales), const_cast<float*>(f->quats),
-                               f->view34, f->projview, &f->cam, 3, f->radii, f->v_xy, f->v_depth, f->v_conic,
-                               const_cast<float*>(f->opacities), f->v_opacity, adam, stream);
+    TS_TRY(TS_ENTRY("ts_sh_colors_bwd_adam",
+                    ts_sh_colors_bwd_adam(f->n, f->sh_degree, f->num_bases, f->means, f->origin,
+                                          (f->flags & TS_FRAME_STRIPE) ? nullptr : f->sh_mask, f->v_colors,
+                                          const_cast<float*>(f->colors_dc),
+                                          f->num_bases > 1 ? const_cast<float*>(f->colors_rest) : nullptr, adam,
+                                          stream)));
+    return TS_ENTRY("ts_project_bwd_adam",
+                    ts_project_bwd_adam(f->n, const_cast<float*>(f->means), const_cast<float*>(f->scales),
+                                        const_cast<float*>(f->quats), f->view34, f->projview, &f->cam, 3, f->radii,
+                                        f->v_xy, f->v_depth, f->v_conic, const_cast<float*>(f->opacities), f->v_opacity,
+                                        adam, stream));
 }
 
 // ---- Gaussian-sharded frame (csrc/shard.hip, tinysplat_amd/sharded.py): the same executor idea -----------------
@@ -230,56 +289,68 @@ int ts_shard_owner_fwd_padded(const ts_frame* fo, const ts_stripes* stripes, con
     TsRange range_("ts_shard_owner_fwd");
     if (bad(fo) || !stripes) return TS_E_BADARG;
     if (fo->n > 0 && fo->n <= small_n_fused())          // a small shard: one launch instead of three (shard.hip)
-        return ts_shard_owner_fwd_fused(fo->n, fo->sh_degree, fo->num_bases, fo->means, fo->scales, fo->quats, fo->view34,
-                                        fo->projview, &fo->cam, 3, fo->origin, fo->colors_dc,
-                                        fo->num_bases > 1 ? fo->colors_rest : nullptr, fo->opacities, fo->channels,
-                                        TS_RASTER_LOGIT_OPACITY, fo->xys, fo->depths, fo->radii, fo->conics,
-                                        fo->num_tiles_hit, fo->sh_mask, fo->splats, stripes, group_base, route_ws, counts,
-                                        stream);
-    TS_TRY(ts_project_fwd(fo->n, fo->means, fo->scales, fo->quats, fo->view34, fo->projview, &fo->cam, 3, fo->xys,
-                          fo->depths, fo->radii, fo->conics, fo->num_tiles_hit, nullptr, stream));
+        return TS_ENTRY("ts_owner_fwd_fused",
+                        ts_shard_owner_fwd_fused(fo->n, fo->sh_degree, fo->num_bases, fo->means, fo->scales, fo->quats,
+                                                 fo->view34, fo->projview, &fo->cam, 3, fo->origin, fo->colors_dc,
+                                                 fo->num_bases > 1 ? fo->colors_rest : nullptr, fo->opacities,
+                                                 fo->channels, TS_RASTER_LOGIT_OPACITY, fo->xys, fo->depths, fo->radii,
+                                                 fo->conics, fo->num_tiles_hit, fo->sh_mask, fo->splats, stripes,
+                                                 group_base, route_ws, counts, stream));
+    TS_TRY(TS_ENTRY("ts_project_fwd",
+                    ts_project_fwd(fo->n, fo->means, fo->scales, fo->quats, fo->view34, fo->projview, &fo->cam, 3,
+                                   fo->xys, fo->depths, fo->radii, fo->conics, fo->num_tiles_hit, nullptr, stream)));
     // colour stage + packed records of the owned Gaussians; the slot fields are rewritten by the importing rank,
     // so any int array serves as cum_tiles_hit
-    TS_TRY(ts_colors_pack_fwd(fo->n, fo->sh_degree, fo->num_bases, fo->means, fo->origin, fo->colors_dc,
-                              fo->num_bases > 1 ? fo->colors_rest : nullptr, fo->sh_mask, nullptr, fo->channels,
-                              TS_RASTER_LOGIT_OPACITY, fo->xys, fo->radii, fo->conics, fo->opacities,
-                              fo->num_tiles_hit, &fo->cam, fo->channels == 4 ? fo->depths : nullptr, fo->splats,
-                              stream));
-    return ts_route_count_padded(fo->n, fo->xys, fo->radii, &fo->cam, stripes, group_base, route_ws, counts, stream);
+    TS_TRY(TS_ENTRY("ts_colors_pack_fwd",
+                    ts_colors_pack_fwd(fo->n, fo->sh_degree, fo->num_bases, fo->means, fo->origin, fo->colors_dc,
+                                       fo->num_bases > 1 ? fo->colors_rest : nullptr, fo->sh_mask, nullptr,
+                                       fo->channels, TS_RASTER_LOGIT_OPACITY, fo->xys, fo->radii, fo->conics,
+                                       fo->opacities, fo->num_tiles_hit, &fo->cam,
+                                       fo->channels == 4 ? fo->depths : nullptr, fo->splats, stream)));
+    return TS_ENTRY("ts_route_count",
+                    ts_route_count_padded(fo->n, fo->xys, fo->radii, &fo->cam, stripes, group_base, route_ws, counts,
+                                          stream));
 }
 
 int ts_shard_stripe_fwd_import(const ts_frame* fs, const float* records, void* stream) {
     TsRange range_("ts_shard_stripe_fwd_import");
     if (bad(fs)) return TS_E_BADARG;
     if (fs->n > 0) {
-        TS_TRY(ts_import_records(fs->n, records, &fs->cam, fs->xys, fs->depths, fs->radii, fs->num_tiles_hit, stream));
+        TS_TRY(TS_ENTRY("ts_import_records",
+                        ts_import_records(fs->n, records, &fs->cam, fs->xys, fs->depths, fs->radii, fs->num_tiles_hit,
+                                          stream)));
         int32_t* total_dev = fs->total_host ? mapped_pointer(fs->total_host) : nullptr;
-        TS_TRY(ts_scan_tiles(fs->n, fs->num_tiles_hit, fs->cum_tiles_hit, fs->scan_ws, total_dev, stream));
+        TS_TRY(TS_ENTRY("ts_scan_tiles",
+                        ts_scan_tiles(fs->n, fs->num_tiles_hit, fs->cum_tiles_hit, fs->scan_ws, total_dev, stream)));
         if (fs->total_host && !total_dev) {
             const hipError_t e = hipMemcpyAsync(fs->total_host, fs->cum_tiles_hit + (fs->n - 1), sizeof(int32_t),
                                                 hipMemcpyDeviceToHost, (hipStream_t)stream);
             if (e != hipSuccess) return (int)e;
         }
-        TS_TRY(ts_import_pack(fs->n, records, fs->cum_tiles_hit, &fs->cam, fs->splats, stream));
+        TS_TRY(TS_ENTRY("ts_import_pack",
+                        ts_import_pack(fs->n, records, fs->cum_tiles_hit, &fs->cam, fs->splats, stream)));
     }
     const float* tight = (fs->flags & TS_FRAME_TIGHT) ? fs->splats : nullptr;
-    TS_TRY(ts_bin_count(fs->n, fs->xys, fs->radii, tight, &fs->cam, fs->bin_ws, stream));
-    return ts_tile_offsets(fs->n, num_tiles(fs), fs->bin_ws, fs->tile_bins, fs->cum_tiles_hit, fs->capacity, stream);
+    TS_TRY(TS_ENTRY("ts_bin_count", ts_bin_count(fs->n, fs->xys, fs->radii, tight, &fs->cam, fs->bin_ws, stream)));
+    return TS_ENTRY("ts_tile_offsets",
+                    ts_tile_offsets(fs->n, num_tiles(fs), fs->bin_ws, fs->tile_bins, fs->cum_tiles_hit, fs->capacity,
+                                    stream));
 }
 
 int ts_shard_stripe_bwd(const ts_frame* fs, float* grad_rows, void* stream) {
     TsRange range_("ts_shard_stripe_bwd");
     if (bad(fs) || fs->num_intersects < 0) return TS_E_BADARG;
-    TS_TRY(ts_raster_bwd(fs->channels,
-                         ((raster_flags(fs) & ~(TS_RASTER_CLAMP_RGB | TS_RASTER_SPLIT_BLOCKS)) | bwd_split(fs)) |
-                             TS_RASTER_FLAG_GEN(fs->flag_gen),
-                         fs->num_intersects, &fs->cam, fs->tile_bins, fs->gaussian_ids_sorted, fs->splats,
-                         fs->background, fs->final_Ts, fs->final_index, fs->v_out_img, nullptr, fs->clamp_mask,
-                         fs->partials, fs->row_flags, stream));
-    return ts_reduce_partials_rows(fs->n, fs->channels,
-                                   bwd_split(fs) | TS_RASTER_FLAG_GEN(fs->flag_gen),
-                                   fs->num_tiles_hit, fs->cum_tiles_hit, fs->partials, fs->row_flags, fs->splats,
-                                   grad_rows, stream);
+    TS_TRY(TS_ENTRY("ts_raster_bwd",
+                    ts_raster_bwd(fs->channels,
+                                  ((raster_flags(fs) & ~(TS_RASTER_CLAMP_RGB | TS_RASTER_SPLIT_BLOCKS)) | bwd_split(fs)) |
+                                      TS_RASTER_FLAG_GEN(fs->flag_gen),
+                                  fs->num_intersects, &fs->cam, fs->tile_bins, fs->gaussian_ids_sorted, fs->splats,
+                                  fs->background, fs->final_Ts, fs->final_index, fs->v_out_img, nullptr, fs->clamp_mask,
+                                  fs->partials, fs->row_flags, stream)));
+    return TS_ENTRY("ts_reduce_partials_rows",
+                    ts_reduce_partials_rows(fs->n, fs->channels, bwd_split(fs) | TS_RASTER_FLAG_GEN(fs->flag_gen),
+                                            fs->num_tiles_hit, fs->cum_tiles_hit, fs->partials, fs->row_flags,
+                                            fs->splats, grad_rows, stream));
 }
 
 int ts_shard_owner_bwd(const ts_frame* fo, const ts_stripes* stripes, const int32_t* route_ws,
@@ -287,20 +358,25 @@ int ts_shard_owner_bwd(const ts_frame* fo, const ts_stripes* stripes, const int3
     TsRange range_("ts_shard_owner_bwd");
     if (bad(fo) || !stripes) return TS_E_BADARG;
     if (fo->n > 0 && fo->n <= small_n_fused())          // a small shard: one launch instead of three (shard.hip)
-        return ts_shard_owner_bwd_fused(fo->n, fo->channels, fo->sh_degree, fo->num_bases, fo->means, fo->scales, fo->quats,
-                                        fo->view34, fo->projview, fo->origin, fo->xys, fo->radii, fo->splats, fo->sh_mask,
-                                        &fo->cam, stripes, route_ws, grad_rows, fo->v_xy, fo->v_conic, fo->v_colors,
-                                        fo->channels == 4 ? fo->v_depth : nullptr, fo->v_opacity, fo->v_colors_dc,
-                                        fo->num_bases > 1 ? fo->v_colors_rest : nullptr, fo->v_means, fo->v_scales,
-                                        fo->v_quats, stream);
-    TS_TRY(ts_route_accumulate(fo->n, fo->channels, fo->xys, fo->radii, fo->splats, fo->sh_mask, &fo->cam, stripes,
-                               route_ws, grad_rows, fo->v_xy, fo->v_conic, fo->v_colors,
-                               fo->channels == 4 ? fo->v_depth : nullptr, fo->v_opacity, stream));
-    TS_TRY(ts_sh_colors_bwd(fo->n, fo->sh_degree, fo->num_bases, fo->means, fo->origin, nullptr, fo->v_colors,
-                            fo->v_colors_dc, fo->num_bases > 1 ? fo->v_colors_rest : nullptr, stream));
-    return ts_project_bwd(fo->n, fo->means, fo->scales, fo->quats, fo->view34, fo->projview, &fo->cam, 3, fo->radii,
-                          fo->v_xy, fo->channels == 4 ? fo->v_depth : nullptr, fo->v_conic, nullptr, fo->v_means,
-                          fo->v_scales, fo->v_quats, stream);
+        return TS_ENTRY("ts_owner_bwd_fused",
+                        ts_shard_owner_bwd_fused(fo->n, fo->channels, fo->sh_degree, fo->num_bases, fo->means,
+                                                 fo->scales, fo->quats, fo->view34, fo->projview, fo->origin, fo->xys,
+                                                 fo->radii, fo->splats, fo->sh_mask, &fo->cam, stripes, route_ws,
+                                                 grad_rows, fo->v_xy, fo->v_conic, fo->v_colors,
+                                                 fo->channels == 4 ? fo->v_depth : nullptr, fo->v_opacity,
+                                                 fo->v_colors_dc, fo->num_bases > 1 ? fo->v_colors_rest : nullptr,
+                                                 fo->v_means, fo->v_scales, fo->v_quats, stream));
+    TS_TRY(TS_ENTRY("ts_route_accumulate",
+                    ts_route_accumulate(fo->n, fo->channels, fo->xys, fo->radii, fo->splats, fo->sh_mask, &fo->cam,
+                                        stripes, route_ws, grad_rows, fo->v_xy, fo->v_conic, fo->v_colors,
+                                        fo->channels == 4 ? fo->v_depth : nullptr, fo->v_opacity, stream)));
+    TS_TRY(TS_ENTRY("ts_sh_colors_bwd",
+                    ts_sh_colors_bwd(fo->n, fo->sh_degree, fo->num_bases, fo->means, fo->origin, nullptr, fo->v_colors,
+                                     fo->v_colors_dc, fo->num_bases > 1 ? fo->v_colors_rest : nullptr, stream)));
+    return TS_ENTRY("ts_project_bwd",
+                    ts_project_bwd(fo->n, fo->means, fo->scales, fo->quats, fo->view34, fo->projview, &fo->cam, 3,
+                                   fo->radii, fo->v_xy, fo->channels == 4 ? fo->v_depth : nullptr, fo->v_conic, nullptr,
+                                   fo->v_means, fo->v_scales, fo->v_quats, stream));
 }
 
 // ---- the whole step of one rank in four calls (ts_rank_step): the entries above composed, nothing new -------------
@@ -317,8 +393,9 @@ int ts_shard_rank_fwd_a(const ts_frame* fo, const ts_rank_step* r, void* stream)
         if (e != hipSuccess) return (int)e;
     }
     TsRange range_("ts_route_pack");
-    return ts_route_pack(fo->n, r->gid_base, fo->xys, fo->radii, fo->depths, fo->splats, &fo->cam, &r->stripes,
-                         r->route_ws, r->send, stream);
+    return TS_ENTRY("ts_route_pack",
+                    ts_route_pack(fo->n, r->gid_base, fo->xys, fo->radii, fo->depths, fo->splats, &fo->cam, &r->stripes,
+                                  r->route_ws, r->send, stream));
 }
 
 int ts_shard_rank_fwd_b(const ts_frame* fs, const ts_rank_step* r, void* stream) {

@@ -13,8 +13,9 @@ tight tile lists, the adapter's clamp(max=1) inside the compositing kernels, and
 node.  Results are bitwise those of the op-by-op path
 (tests/test_gpu_parity.py: test_one_node_frame_is_bitwise_the_fused_op_recipe).
 
-While ``ops.kernel_timer`` is recording (bench.py's per-entry table) the same kernels are issued one
-C-ABI entry at a time from Python on the same buffers, so that each entry can be bracketed by events.
+``csrc/frame.hip`` is the only description of a frame's launches.  While ``ops.kernel_timer`` is recording (bench.py's
+per-entry table) the executor reports every entry it issues through the library's entry probe and the timer brackets it
+with events: the frame that is timed is the frame that runs.
 """
 from __future__ import annotations
 
@@ -30,8 +31,7 @@ from torch import Tensor
 from ._comm import collective_timer
 from . import _lib
 from ._lib import TsFrame
-from .ops import (TileBinning, _call, _camera, _f32c, _need_hip, _ptr, _stream, _stripe_rows, _tile_bounds,
-                  deg_from_sh, kernel_timer)
+from .ops import TileBinning, _camera, _f32c, _need_hip, _stream, _stripe_rows, _tile_bounds, deg_from_sh
 
 # Tight tile lists (see ts_bin_count): (Gaussian, tile) pairs that provably cannot reach alpha >= 1/255
 # anywhere in the tile are dropped at binning time.  Results are bit-identical either way
@@ -292,7 +292,6 @@ DIRECT_GRADS = os.environ.get("TS_DIRECT_GRADS", "1") != "0"      # A/B switch (
 # that keeps what the backward pass needs - the forward compositing pass writes the entries it staged (ids into the dead
 # bucket_ids, one word per entry + per-tile counts behind gaussian_ids_sorted) and the backward pass replays those instead
 # of gathering and culling every listed entry again.  Same rows, same gradients.  TS_SURVIVORS=0: the re-culling replay.
-# (Frames timed per C-ABI entry - kernel_timer - keep the re-culling replay: the entries take no survivor lists.)
 SURVIVORS = os.environ.get("TS_SURVIVORS", "1") != "0"
 
 # CAPACITY ALLOCATION (option, off by default): the per-intersection buffers (bucket_ids | gaussian_ids_sorted;
@@ -448,7 +447,6 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
         F.cum = view(7, torch.int32, n, (n,))
         F.tile_bins = view(10, torch.int32, 2 * max(num_tiles, 1), (max(num_tiles, 1), 2))
         host, event, count_lock = _total_slot(dev)
-        timed_ = kernel_timer.enabled        # (per-entry timing issues ts_tile_offsets itself: no statistic in those frames)
         fr = TsFrame()
         fr.n, fr.num_bases, fr.sh_degree, fr.channels = n, nb, int(sh_degree), ch
         # a proper stripe of the frame (one rank of a multi-GPU frame): TS_FRAME_STRIPE
@@ -456,11 +454,11 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
         full = cam.tile_rows == cam.tile_bounds_y
         fr.flags = ((1 if TIGHT_BINNING else 0) | (2 if F.split else 0) | (8 if mode == 2 else 0) | (16 if stripe else 0)
                     | (0 if TWO_HOP_SCATTER else 32) | (64 if F.planes else 0) | (0 if INLINE_SORT else 128)
-                    | (256 if (full and not timed_) else 0))            # TS_FRAME_LIST_STATS (the slot holds four words)
-        surv = SURVIVORS and keep and full and mode == 0 and not F.split and INLINE_SORT and not timed_
+                    | (256 if full else 0))                             # TS_FRAME_LIST_STATS (the slot holds four words)
+        surv = SURVIVORS and keep and full and mode == 0 and not F.split and INLINE_SORT
         if surv:
             fr.flags |= 512                                               # TS_FRAME_SURVIVORS
-        if full and not timed_:
+        if full:
             _stats_mode[dev.index] = mode
         fr.cam = cam
         fr.means, fr.scales, fr.quats, fr.opacities = means.data_ptr(), scales.data_ptr(), quats.data_ptr(), opacities.data_ptr()
@@ -477,7 +475,6 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
             fr.sh_mask, fr.final_Ts, fr.final_index, fr.clamp_mask = ptr[11], ptr[12], ptr[13], ptr[14]
         F.fr = fr
         _mark("fwd:allocated + struct")
-        timed = kernel_timer.enabled
         spin = COUNT_WAIT == "spin" and n > 0
         cap_key = (dev.index, n, w, h, cam.tile_row0, cam.tile_rows)
         est = _capacity.get(cap_key) if (CAPACITY_ALLOC and n > 0) else None
@@ -493,16 +490,10 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
             return cap
 
         def prepare():
-            if timed:
-                _steps_prepare(lib, fr, s)
-            else:
-                _lib.check(lib.ts_frame_fwd_prepare(ctypes.byref(fr), s), "ts_frame_fwd_prepare")
+            _lib.check(lib.ts_frame_fwd_prepare(ctypes.byref(fr), s), "ts_frame_fwd_prepare")
 
         def composite():
-            if timed:
-                _steps_composite(lib, fr, s)
-            else:
-                _lib.check(lib.ts_frame_fwd_composite(ctypes.byref(fr), s), "ts_frame_fwd_composite")
+            _lib.check(lib.ts_frame_fwd_composite(ctypes.byref(fr), s), "ts_frame_fwd_composite")
 
         count_lock.acquire()
         issued = consumed = False
@@ -510,12 +501,7 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
             if spin:
                 word = ctypes.c_int32.from_address(host.data_ptr())
                 word.value = -(1 << 31)                  # sentinel: no int32 prefix sum ends here (overflow wraps past it)
-            if timed:
-                _steps_project(lib, fr, s)
-                if n > 0:
-                    host[:1].copy_(F.cum[-1:], non_blocking=True)
-            else:
-                _lib.check(lib.ts_frame_fwd_project(ctypes.byref(fr), s), "ts_frame_fwd_project")
+            _lib.check(lib.ts_frame_fwd_project(ctypes.byref(fr), s), "ts_frame_fwd_project")
             issued = n > 0
             _mark("fwd:call project")
             event.record()                               # (torch's current stream of the current device = dev, set above)
@@ -590,70 +576,6 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
     return F
 
 
-# ---- the executor's calls, one C-ABI entry at a time (per-entry timing only; mirrors csrc/frame.hip) ----
-def _steps_project(lib, fr, s):
-    _call("ts_project_fwd", lib.ts_project_fwd, fr.n, fr.means, fr.scales, fr.quats, fr.view34, fr.projview,
-          fr.cam, 3, fr.xys, fr.depths, fr.radii, fr.conics, fr.num_tiles_hit, None, s)
-    _call("ts_scan_tiles", lib.ts_scan_tiles, fr.n, fr.num_tiles_hit, fr.cum_tiles_hit, fr.scan_ws, None, s)
-
-
-def _steps_prepare(lib, fr, s):
-    _call("ts_colors_pack_fwd", lib.ts_colors_pack_fwd, fr.n, fr.sh_degree, fr.num_bases, fr.means, fr.origin,
-          fr.colors_dc, fr.colors_rest if fr.num_bases > 1 else None, fr.sh_mask,
-          fr.num_tiles_hit if fr.flags & 16 else None, fr.channels, 1, fr.xys, fr.radii, fr.conics, fr.opacities,
-          fr.cum_tiles_hit, fr.cam, fr.depths if fr.channels == 4 else None, fr.splats, s)
-    tight = fr.splats if fr.flags & 1 else None
-    _call("ts_bin_count", lib.ts_bin_count, fr.n, fr.xys, fr.radii, tight, fr.cam, fr.bin_ws, s)
-    _call("ts_tile_offsets", lib.ts_tile_offsets, fr.n, int(lib.ts_num_tiles(ctypes.byref(fr.cam))), fr.bin_ws,
-          fr.tile_bins, fr.cum_tiles_hit, fr.capacity, s)
-
-
-def _steps_composite(lib, fr, s):
-    tight = fr.splats if fr.flags & 1 else None
-    nt = int(lib.ts_num_tiles(ctypes.byref(fr.cam)))
-    fused = fr.num_intersects > 0 and fr.cam.wide_tiles == 0 and not fr.flags & (8 | 128)
-    if fr.num_intersects > 0:
-        _call("ts_bin_scatter", lib.ts_bin_scatter, fr.n, fr.xys, fr.radii, tight, fr.cam, fr.bin_ws,
-              fr.bucket_ids, None if fr.flags & 32 else fr.gaussian_ids_sorted, s)
-        _call("ts_sort_tiles", lib.ts_sort_tiles_above if fused else lib.ts_sort_tiles, nt, fr.tile_bins, fr.depths,
-              fr.bucket_ids, fr.gaussian_ids_sorted, fr.bin_ws,
-              fr.bin_ws + 4 * (int(lib.ts_bin_ws_ints(fr.n, nt)) - 1), s)
-    if fused:
-        _call("ts_raster_fwd", lib.ts_raster_fwd_sort, fr.channels, 2 | (4 if fr.flags & 2 else 0), fr.cam, fr.tile_bins,
-              fr.bucket_ids, fr.depths,
-              fr.gaussian_ids_sorted, fr.splats, fr.background, fr.out_img, fr.out_depth if fr.flags & 64 else None,
-              fr.final_Ts, fr.final_index, fr.clamp_mask, s)
-        return
-    _call("ts_raster_fwd", lib.ts_raster_fwd_planes, fr.channels, 2 | (4 if fr.flags & 2 else 0) | (fr.flags & 8), fr.cam,
-          fr.tile_bins, fr.gaussian_ids_sorted, fr.splats, fr.background, fr.out_img,
-          fr.out_depth if fr.flags & 64 else None, fr.final_Ts, fr.final_index, fr.clamp_mask, s)
-
-
-def segmented(cam) -> bool:
-    """list segments replace the split blocks in the backward pass (csrc/frame.hip: segmented)"""
-    return ((cam.hints >> 8) & 15) > 1 and not cam.wide_tiles
-
-
-def _steps_bwd_composite(lib, fr, s):
-    split = 4 if (fr.flags & 2 and not segmented(fr.cam)) else 0
-    gen = (fr.flag_gen & 0xff) << 8
-    planes = 1 if fr.flags & 64 else 0
-    _call("ts_raster_bwd", lib.ts_raster_bwd_planes, fr.channels, split | (fr.flags & 8) | gen, fr.num_intersects, fr.cam,
-          fr.tile_bins, fr.gaussian_ids_sorted, fr.splats, fr.background, fr.final_Ts, fr.final_index, fr.v_out_img,
-          fr.v_out_depth if planes else None, planes, None, fr.clamp_mask, fr.partials, fr.row_flags, s)
-    _call("ts_reduce_partials", lib.ts_reduce_partials, fr.n, fr.channels, 1 | split | gen, fr.num_tiles_hit,
-          fr.cum_tiles_hit, fr.partials, fr.row_flags, fr.splats, fr.v_xy, fr.v_conic, fr.v_colors,
-          fr.v_opacity, fr.v_depth if fr.channels == 4 else None, fr.sh_mask if fr.flags & 16 else None, s)
-
-
-def _steps_bwd_params(lib, fr, s):
-    _call("ts_sh_colors_bwd", lib.ts_sh_colors_bwd, fr.n, fr.sh_degree, fr.num_bases, fr.means, fr.origin,
-          None if fr.flags & 16 else fr.sh_mask, fr.v_colors, fr.v_colors_dc,
-          fr.v_colors_rest if fr.num_bases > 1 else None, s)
-    _call("ts_project_bwd", lib.ts_project_bwd, fr.n, fr.means, fr.scales, fr.quats, fr.view34, fr.projview,
-          fr.cam, 3, fr.radii, fr.v_xy, fr.v_depth, fr.v_conic, None, fr.v_means, fr.v_scales, fr.v_quats, s)
-
-
 # FUSED ADAM (training.TrainStep; csrc/project.hip: FUSED ADAM): inside ``with fused_adam(optimizer):`` the backward pass of
 # a single-GPU frame hands the optimiser's state to ts_frame_bwd_params_adam - the parameter-stage kernels update the
 # six tensors from the gradients they hold in registers - and returns no parameter gradients (xys.grad is still set).
@@ -676,14 +598,6 @@ class fused_adam:
     def __exit__(self, *exc):
         _adam_hook.opt = self.prev
         return False
-
-
-def _steps_bwd_params_adam(lib, fr, adam, s):
-    _call("ts_sh_colors_bwd_adam", lib.ts_sh_colors_bwd_adam, fr.n, fr.sh_degree, fr.num_bases, fr.means, fr.origin,
-          None if fr.flags & 16 else fr.sh_mask, fr.v_colors, fr.colors_dc,
-          fr.colors_rest if fr.num_bases > 1 else None, ctypes.byref(adam), s)
-    _call("ts_project_bwd_adam", lib.ts_project_bwd_adam, fr.n, fr.means, fr.scales, fr.quats, fr.view34, fr.projview,
-          fr.cam, 3, fr.radii, fr.v_xy, fr.v_depth, fr.v_conic, fr.opacities, fr.v_opacity, ctypes.byref(adam), s)
 
 
 class _RenderFrame(torch.autograd.Function):
@@ -763,23 +677,14 @@ class _RenderFrame(torch.autograd.Function):
                 fr.v_means, fr.v_scales, fr.v_quats = v_means.data_ptr(), v_scales.data_ptr(), v_quats.data_ptr()
                 fr.v_colors_dc, fr.v_colors_rest = v_dc.data_ptr(), v_rest.data_ptr()
             _mark("bwd:allocated")
-            timed = kernel_timer.enabled
-            if timed:
-                _steps_bwd_composite(lib, fr, s)
-            else:
-                _lib.check(lib.ts_frame_bwd_composite(ctypes.byref(fr), s), "ts_frame_bwd_composite")
+            _lib.check(lib.ts_frame_bwd_composite(ctypes.byref(fr), s), "ts_frame_bwd_composite")
             if ctx.group is not None:                          # tile-stripe sharding: sum over ranks
                 with collective_timer.span(on_device=flat.is_cuda and dist.get_backend(ctx.group) != "gloo",
                                            label="all_reduce(2-D gradients)", nbytes=flat.numel() * flat.element_size()):
                     dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=ctx.group)
             if adam is not None:
-                if timed:
-                    _steps_bwd_params_adam(lib, fr, adam, s)
-                else:
-                    _lib.check(lib.ts_frame_bwd_params_adam(ctypes.byref(fr), ctypes.byref(adam), s),
-                               "ts_frame_bwd_params_adam")
-            elif timed:
-                _steps_bwd_params(lib, fr, s)
+                _lib.check(lib.ts_frame_bwd_params_adam(ctypes.byref(fr), ctypes.byref(adam), s),
+                           "ts_frame_bwd_params_adam")
             else:
                 _lib.check(lib.ts_frame_bwd_params(ctypes.byref(fr), s), "ts_frame_bwd_params")
         _mark("bwd:calls")

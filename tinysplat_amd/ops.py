@@ -14,6 +14,7 @@ missing libtinysplat_hip.so raises at the first call.
 from __future__ import annotations
 
 import os
+import threading
 from typing import Optional, Tuple
 
 import torch
@@ -58,19 +59,38 @@ def deg_from_sh(num_bases: int) -> int:
 
 class _KernelTimer:
     """Optional per-entry timing with events recorded on the stream the kernels are launched on
-    (torch's current stream).  Used by bench.py for the live roofline numbers; off by default."""
+    (torch's current stream).  Used by bench.py for the live roofline numbers; off by default.
+
+    Entries that Python issues itself are bracketed by ``_call``; those of the native executors (csrc/frame.hip) by the
+    library's entry probe, which calls ``_probe`` before and after each of them - a timed frame is the frame that runs."""
 
     def __init__(self):
         self.enabled = False
         self.records = {}
+        self._open = {}         # thread -> event recorded when the executor entered the entry it is in (they do not nest)
+        self._probe_c = _lib.ENTRY_PROBE(self._probe)       # (kept alive here: the library holds the bare pointer)
+
+    def _probe(self, entry, end, _user):
+        try:                    # called from native code: nothing may propagate
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            if not end:
+                self._open[threading.get_ident()] = ev
+            else:
+                self.records.setdefault(entry.decode(), []).append((self._open.pop(threading.get_ident()), ev))
+        except Exception:
+            pass
 
     def start(self):
         self.enabled = True
         self.records = {}
+        self._open = {}
+        _lib.load().ts_set_entry_probe(self._probe_c, None)
 
     def stop(self):
         """-> {entry: (launches, mean_ms)}; synchronises."""
         self.enabled = False
+        _lib.load().ts_set_entry_probe(None, None)
         torch.cuda.synchronize()
         out = {}
         for name, evs in self.records.items():

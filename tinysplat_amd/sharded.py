@@ -54,9 +54,6 @@ from .synthetic import SplatModel
 RECORD_FLOATS = 16       # TS_EXPORT_RECORD_FLOATS
 ROW_FLOATS = 12          # TS_PARTIAL_ROW_FLOATS
 
-# Gaussians up to which a rank's owner stage runs as its small-N fusion (csrc/shard.hip: FUSED OWNER FORWARD; the
-# library reads the same variable: 0 = never)
-SMALL_N_FUSED = int(os.environ.get("TS_SMALL_N_FUSED", "262144"))
 # PADDED EXCHANGE (an option: TS_PADDED_EXCHANGE=1 switches it on): how many records a rank sends to every other rank
 # is known only after its owner stage has run, and sizing the all_to_all from it costs a host read in the middle of
 # the frame - where the GPU is what bounds a rank's step, it idles while the host waits for the counts, allocates and
@@ -480,23 +477,8 @@ def _owner_stage(lib, s, dev, layout: ShardLayout, exchange: Exchange, means, sc
         for c in O.caps[me].tolist():
             base.append(base[-1] + c)
         gb = (ctypes.c_int32 * (world + 1))(*base)
-    if kernel_timer.enabled and 0 < n <= SMALL_N_FUSED:      # (what ts_shard_owner_fwd_padded issues for a small shard)
-        _call("ts_owner_fwd_fused", lib.ts_shard_owner_fwd_fused, n, int(sh_degree), nb, fr.means, fr.scales, fr.quats,
-              fr.view34, fr.projview, O.cam, 3, fr.origin, fr.colors_dc, fr.colors_rest if nb > 1 else None, fr.opacities,
-              ch, 1, fr.xys, fr.depths, fr.radii, fr.conics, fr.num_tiles_hit, fr.sh_mask, fr.splats, layout.c_stripes,
-              gb, O.p_route_ws, counts.data_ptr(), s)
-    elif kernel_timer.enabled:
-        _call("ts_project_fwd", lib.ts_project_fwd, n, fr.means, fr.scales, fr.quats, fr.view34, fr.projview, O.cam, 3,
-              fr.xys, fr.depths, fr.radii, fr.conics, fr.num_tiles_hit, None, s)
-        # colour stage + packed records of the owned Gaussians (slot fields are rewritten by the importing rank)
-        _call("ts_colors_pack_fwd", lib.ts_colors_pack_fwd, n, int(sh_degree), nb, fr.means, fr.origin, fr.colors_dc,
-              fr.colors_rest if nb > 1 else None, fr.sh_mask, None, ch, 1, fr.xys, fr.radii, fr.conics,
-              fr.opacities, fr.num_tiles_hit, O.cam, fr.depths if ch == 4 else None, fr.splats, s)
-        _call("ts_route_count", lib.ts_route_count_padded, n, fr.xys, fr.radii, O.cam, layout.c_stripes, gb, O.p_route_ws,
-              counts.data_ptr(), s)
-    else:
-        _lib.check(lib.ts_shard_owner_fwd_padded(ctypes.byref(fr), layout.c_stripes, gb, O.p_route_ws,
-                                                 counts.data_ptr(), s), "ts_shard_owner_fwd")
+    _lib.check(lib.ts_shard_owner_fwd_padded(ctypes.byref(fr), layout.c_stripes, gb, O.p_route_ws, counts.data_ptr(), s),
+               "ts_shard_owner_fwd")
     if O.caps is not None:
         # nothing of this frame's counts is looked at here: they are gathered, copied to the host behind the launches
         # already enqueued, and checked where the frame waits for the stripe's pair count (_ShardedFrame.forward)
@@ -570,8 +552,6 @@ def _stripe_stage(lib, s, dev, layout: ShardLayout, records: Tensor, background:
     if keep:
         fr.final_Ts, fr.final_index, fr.clamp_mask = ptr[9], ptr[10], ptr[11]
     S.fr = fr
-    timed = kernel_timer.enabled
-    tight = fr.splats if _frame.TIGHT_BINNING else None
     cap_key = (dev.index, "stripe", layout.world, w, h, cam.tile_row0, cam.tile_rows)
     est = _frame._capacity.get(cap_key) if (_frame.CAPACITY_ALLOC and m > 0) else None
 
@@ -582,28 +562,14 @@ def _stripe_stage(lib, s, dev, layout: ShardLayout, records: Tensor, background:
         return cap
 
     def stage_import():
-        if not timed:
-            _lib.check(lib.ts_shard_stripe_fwd_import(ctypes.byref(fr), records.data_ptr() if m > 0 else None, s),
-                       "ts_shard_stripe_fwd_import")
-            return
-        if m > 0:
-            _call("ts_import_records", lib.ts_import_records, m, records.data_ptr(), cam, fr.xys, fr.depths, fr.radii,
-                  fr.num_tiles_hit, s)
-            _call("ts_scan_tiles", lib.ts_scan_tiles, m, fr.num_tiles_hit, fr.cum_tiles_hit, fr.scan_ws, None, s)
-            host.copy_(_view(S.ws, offs[4], torch.int32, m, (m,))[m - 1:m], non_blocking=True)
-            _call("ts_import_pack", lib.ts_import_pack, m, records.data_ptr(), fr.cum_tiles_hit, cam, fr.splats, s)
-        _call("ts_bin_count", lib.ts_bin_count, m, fr.xys, fr.radii, tight, cam, fr.bin_ws, s)
-        _call("ts_tile_offsets", lib.ts_tile_offsets, m, num_tiles, fr.bin_ws, fr.tile_bins, fr.cum_tiles_hit,
-              fr.capacity, s)
+        _lib.check(lib.ts_shard_stripe_fwd_import(ctypes.byref(fr), records.data_ptr() if m > 0 else None, s),
+                   "ts_shard_stripe_fwd_import")
 
     def composite():
-        if timed:
-            _frame._steps_composite(lib, fr, s)
-        else:
-            _lib.check(lib.ts_frame_fwd_composite(ctypes.byref(fr), s), "ts_frame_fwd_composite")
+        _lib.check(lib.ts_frame_fwd_composite(ctypes.byref(fr), s), "ts_frame_fwd_composite")
 
     cap = None
-    spin = _frame.COUNT_WAIT == "spin" and m > 0 and not timed
+    spin = _frame.COUNT_WAIT == "spin" and m > 0
     with lock:
         if spin:
             word = ctypes.c_int32.from_address(host.data_ptr())
@@ -663,16 +629,7 @@ def _stripe_backward(lib, s, dev, S: _Stripe, ch: int, v_img: Tensor) -> Tensor:
     row_flags, fr.flag_gen = _frame.row_flags_for(dev, rows_n)
     grad_rows = torch.empty((m, ROW_FLOATS), **f32) if m > 0 else torch.empty((1, ROW_FLOATS), **f32)[:0]
     fr.v_out_img, fr.partials, fr.row_flags = v_img.data_ptr(), partials.data_ptr(), row_flags.data_ptr()
-    if kernel_timer.enabled:
-        gen = (fr.flag_gen & 0xff) << 8
-        rflags = (4 if bwd_split else 0) | (8 if S.mode == 2 else 0) | gen
-        _call("ts_raster_bwd", lib.ts_raster_bwd, ch, rflags, S.total, S.cam, fr.tile_bins, fr.gaussian_ids_sorted,
-              fr.splats, fr.background, fr.final_Ts, fr.final_index, fr.v_out_img, None, fr.clamp_mask, fr.partials,
-              fr.row_flags, s)
-        _call("ts_reduce_partials_rows", lib.ts_reduce_partials_rows, m, ch, (4 if bwd_split else 0) | gen, fr.num_tiles_hit,
-              fr.cum_tiles_hit, fr.partials, fr.row_flags, fr.splats, grad_rows.data_ptr(), s)
-    else:
-        _lib.check(lib.ts_shard_stripe_bwd(ctypes.byref(fr), grad_rows.data_ptr(), s), "ts_shard_stripe_bwd")
+    _lib.check(lib.ts_shard_stripe_bwd(ctypes.byref(fr), grad_rows.data_ptr(), s), "ts_shard_stripe_bwd")
     S.records = None
     return grad_rows
 
@@ -697,23 +654,8 @@ def _owner_backward(lib, s, dev, layout: ShardLayout, O: _Owner, back: Tensor, s
     fr.v_conic, fr.v_colors, fr.v_depth = tmp.data_ptr(), tmp.data_ptr() + 12 * nn, tmp.data_ptr() + 24 * nn
     fr.v_means, fr.v_scales, fr.v_quats = v_means.data_ptr(), v_scales.data_ptr(), v_quats.data_ptr()
     fr.v_colors_dc, fr.v_colors_rest = v_dc.data_ptr(), v_rest.data_ptr()
-    if kernel_timer.enabled and 0 < n <= SMALL_N_FUSED:      # (what ts_shard_owner_bwd issues for a small shard)
-        _call("ts_owner_bwd_fused", lib.ts_shard_owner_bwd_fused, n, ch, sh_degree, O.nb, fr.means, fr.scales, fr.quats,
-              fr.view34, fr.projview, fr.origin, fr.xys, fr.radii, fr.splats, fr.sh_mask, O.cam, layout.c_stripes,
-              O.p_route_ws, back.data_ptr(), fr.v_xy, fr.v_conic, fr.v_colors, fr.v_depth if ch == 4 else None,
-              fr.v_opacity, fr.v_colors_dc, fr.v_colors_rest if O.nb > 1 else None, fr.v_means, fr.v_scales, fr.v_quats, s)
-    elif kernel_timer.enabled:
-        _call("ts_route_accumulate", lib.ts_route_accumulate, n, ch, fr.xys, fr.radii, fr.splats, fr.sh_mask, O.cam,
-              layout.c_stripes, O.p_route_ws, back.data_ptr(), fr.v_xy, fr.v_conic, fr.v_colors,
-              fr.v_depth if ch == 4 else None, fr.v_opacity, s)
-        _call("ts_sh_colors_bwd", lib.ts_sh_colors_bwd, n, sh_degree, O.nb, fr.means, fr.origin, None, fr.v_colors,
-              fr.v_colors_dc, fr.v_colors_rest if O.nb > 1 else None, s)
-        _call("ts_project_bwd", lib.ts_project_bwd, n, fr.means, fr.scales, fr.quats, fr.view34, fr.projview, O.cam, 3,
-              fr.radii, fr.v_xy, fr.v_depth if ch == 4 else None, fr.v_conic, None, fr.v_means, fr.v_scales,
-              fr.v_quats, s)
-    else:
-        _lib.check(lib.ts_shard_owner_bwd(ctypes.byref(fr), layout.c_stripes, O.p_route_ws, back.data_ptr(), s),
-                   "ts_shard_owner_bwd")
+    _lib.check(lib.ts_shard_owner_bwd(ctypes.byref(fr), layout.c_stripes, O.p_route_ws, back.data_ptr(), s),
+               "ts_shard_owner_bwd")
     return (v_means, v_scales, v_quats, v_opac, v_dc, v_rest), v_xy
 
 
