@@ -808,6 +808,47 @@ int ts_extract_normals(int32_t n, int32_t m, const float* points, const int32_t*
                        float* normals, void* stream);
 int64_t ts_extract_chunk_bytes(int32_t n, int32_t rays, int32_t steps);
 
+/* Sparse-grid iso-surface mesh of the same density (marching tetrahedra; DESIGN.md section 6g, csrc/mesh_cells.h).
+ * Additive entries: the ABI version is unchanged.  None allocates or synchronises; all are deterministic (plain
+ * stores).  The grid: grid_host = host float[4] {lo x y z, cell edge h > 0}, cells_host = host int32[3], the cells per
+ * axis (>= 1; (nx + 1)(ny + 1)(nz + 1) * 8 must fit int64).  Corner (i, j, k) sits at lo + (i, j, k) * h (float32, product
+ * and sum rounded separately) and has the id (k (ny + 1) + j)(nx + 1) + i; bricks are 8^3 cells, brick (bx, by, bz) has
+ * the id (bz nby + by) nbx + bx with nb = ceil(n / 8); a brick has 9^3 = TS_MESH_BRICK_CORNERS corners, x fastest.
+ * ts_mesh_boxes: boxes float32 [n,6] <- {lo xyz, hi xyz} = mean -+ extent_sigmas * sqrt(Sigma_aa), Sigma = R diag(exp(2 s))
+ * R^T in double, rounded outwards.  TS_E_BADARG: n < 1, extent_sigmas not positive and finite, a NULL pointer.
+ * ts_mesh_mark: flags uint8 [number of bricks] (zeroed by the caller) <- 1 for every brick holding a cell with a corner
+ * inside a Gaussian's box.  TS_E_BADARG: n < 1, a bad grid, a NULL pointer.
+ * ts_mesh_chunk_bytes: the bytes of one chunk of `bricks` bricks: ts_knn's workspace for bricks * 729 queries, then
+ * 256-byte aligned corner positions, k-NN distances and indices, densities, and per brick a count (int32), an offset
+ * (int64) and a k-NN stats pair (int32[2]).  TS_E_BADARG: n < TS_EXTRACT_K, bricks < 1 or bricks * 729 * 16 >= 2^31.
+ * ts_mesh_corners: corners float32 [bricks * 729, 3] <- the positions of the listed bricks' corners (brick_ids int64
+ * [bricks]); a corner beyond the grid's last cell takes the last corner's coordinate on that axis.
+ * ts_mesh_density: density float32 [bricks * 729] <- d of ts_extract_march at every corner over its neighbours knn
+ * int32 [bricks * 729, TS_EXTRACT_K]; 0 at a corner beyond the grid's last cell.  TS_E_BADARG: also n < TS_EXTRACT_K.
+ * ts_mesh_count: counts int32 [bricks] <- the triangles of every brick (a corner is above when d > level).
+ * ts_mesh_emit: with offsets int64 [bricks] (the exclusive prefix sums of counts): keys int64 [T,3] <- per triangle
+ * vertex the edge key id(lower corner) * 8 + direction (1..7: bit 0 x, bit 1 y, bit 2 z), positions float32 [T,3,3] <-
+ * the vertex, interpolated from the lower corner to the higher; cells: NULL, or int64 [T] <- the triangle's cell
+ * (k ny + j) nx + i.  Triangles in (brick, cell, tetrahedron, triangle) order, wound so that the normal points towards
+ * falling density.  count / emit run one workgroup of 512 threads per brick.  TS_E_BADARG (all four): bricks out of
+ * range, a bad grid, a non-finite level, a NULL pointer (cells may be). */
+#define TS_MESH_BRICK_CORNERS 729
+int ts_mesh_boxes(int32_t n, const float* means, const float* scales, const float* quats, float extent_sigmas,
+                  float* boxes, void* stream);
+int ts_mesh_mark(int32_t n, const float* boxes, const float* grid_host, const int32_t* cells_host, uint8_t* flags,
+                 void* stream);
+int64_t ts_mesh_chunk_bytes(int32_t n, int32_t bricks);
+int ts_mesh_corners(int32_t bricks, const int64_t* brick_ids, const float* grid_host, const int32_t* cells_host,
+                    float* corners, void* stream);
+int ts_mesh_density(int32_t n, int32_t bricks, const int64_t* brick_ids, const float* grid_host,
+                    const int32_t* cells_host, const float* corners, const int32_t* knn, const float* records,
+                    float* density, void* stream);
+int ts_mesh_count(int32_t bricks, const int64_t* brick_ids, const float* grid_host, const int32_t* cells_host,
+                  float level, const float* density, int32_t* counts, void* stream);
+int ts_mesh_emit(int32_t bricks, const int64_t* brick_ids, const float* grid_host, const int32_t* cells_host,
+                 float level, const float* density, const int64_t* offsets, int64_t* keys, float* positions,
+                 int64_t* cells, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

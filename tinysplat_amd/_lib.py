@@ -196,6 +196,13 @@ SIGNATURES = {
                                    _P, _P, _P]),
     "ts_extract_normals": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P]),
     "ts_extract_chunk_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "ts_mesh_boxes": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P]),
+    "ts_mesh_mark": (c_int32, [c_int32, _P, _P, _P, _P, _P]),
+    "ts_mesh_chunk_bytes": (c_int64, [c_int32, c_int32]),
+    "ts_mesh_corners": (c_int32, [c_int32, _P, _P, _P, _P, _P]),
+    "ts_mesh_density": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_mesh_count": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P, _P]),
+    "ts_mesh_emit": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

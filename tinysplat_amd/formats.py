@@ -182,3 +182,42 @@ def read_points_ply(path):
     rows = np.frombuffer(blob, dtype="<f4", count=n * 6, offset=at + len(marker)).reshape(n, 6)
     t = torch.from_numpy(rows.astype(np.float32))
     return t[:, :3].contiguous(), t[:, 3:].contiguous()
+
+
+def _mesh_arrays(mesh):
+    """``(vertices float32 [V,3], normals float32 [V,3] (zeros without), faces int32 [F,3])`` of a
+    ``mesh.TriangleMesh`` (or anything with those attributes) as little-endian arrays on the CPU."""
+    xyz = torch.as_tensor(mesh.vertices).detach().to("cpu", torch.float32)
+    nrm = getattr(mesh, "normals", None)
+    nrm = torch.zeros_like(xyz) if nrm is None else torch.as_tensor(nrm).detach().to("cpu", torch.float32)
+    faces = torch.as_tensor(mesh.faces).detach().to("cpu", torch.int32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or nrm.shape != xyz.shape or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("vertices [V,3], normals [V,3] and faces [F,3] expected")
+    if faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= xyz.shape[0]):
+        raise ValueError("a face refers to a vertex that does not exist")
+    return xyz.numpy().astype("<f4"), nrm.numpy().astype("<f4"), faces.numpy().astype("<i4")
+
+
+def export_mesh_ply(mesh, path) -> None:
+    """A triangle mesh as a binary little-endian PLY: ``x y z nx ny nz`` (float) per vertex, then per face a
+    ``uchar`` count (3) and ``int`` vertex indices.  ``mesh``: a ``mesh.TriangleMesh``, on any device."""
+    xyz, nrm, faces = _mesh_arrays(mesh)
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {xyz.shape[0]}",
+              *(f"property float {name}" for name in _POINT_FIELDS), f"element face {faces.shape[0]}",
+              "property list uchar int vertex_indices", "end_header"]
+    rows = np.empty((faces.shape[0],), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    rows["n"], rows["v"] = 3, faces
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(np.ascontiguousarray(np.concatenate((xyz, nrm), 1)).tobytes())
+        f.write(rows.tobytes())
+
+
+def export_mesh_obj(mesh, path) -> None:
+    """A triangle mesh as a Wavefront OBJ: ``v x y z``, ``vn x y z`` and ``f a//a b//b c//c`` with 1-based indices.
+    Floats are written with nine significant digits, which a float32 survives.  ``mesh`` on any device."""
+    xyz, nrm, faces = _mesh_arrays(mesh)
+    with open(path, "w", encoding="ascii") as f:
+        f.writelines("v %.9g %.9g %.9g\n" % tuple(r) for r in xyz.tolist())
+        f.writelines("vn %.9g %.9g %.9g\n" % tuple(r) for r in nrm.tolist())
+        f.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in (faces + 1).tolist())

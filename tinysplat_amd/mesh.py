@@ -1,0 +1,323 @@
+"""Iso-surface triangle mesh of the SuGaR density: ``model -> mesh``, DESIGN.md section 6g.
+
+The surface is the level set ``density_function = surface_level`` (model_gaussian.py:257-274, level 0.3) that the
+density regulariser trains towards and ``extract.level_set_points`` samples, meshed by marching tetrahedra (the
+Freudenthal split of every cell, csrc/mesh_cells.h) on a regular grid of cubes.  It stands in for the reference's
+``export_mesh(..., 'marching_cubes')`` (model_gaussian.py:482-531), which cannot run as written; parity with mcubes is
+not a goal.
+
+Only the bricks (8^3 cells) near a Gaussian are evaluated.  **The sparsity condition**: a point outside every
+Gaussian's axis-aligned box of half-size ``extent_sigmas * sqrt(Sigma_aa)`` has Mahalanobis ``q > extent_sigmas^2`` to
+every Gaussian, so its 16-neighbour density is at most ``16 exp(-extent_sigmas^2 / 2)`` (0.178 at 3 sigma).
+``MeshConfig`` refuses a ``surface_level`` at or below that bound; above it no corner outside all boxes is above the
+level, every cell the surface crosses has a corner inside some box, and the bricks holding such cells give the mesh of
+the dense grid bit for bit (``sparse=False`` evaluates every brick, to show it).  This is a condition, not a tuning knob.
+
+The hot path is csrc/mesh.hip on top of ``ts_knn``, ``ts_extract_pack`` and ``ts_extract_normals``; there is no CPU
+fallback: tensors must be on the GPU.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
+
+import torch
+from torch import Tensor
+
+from . import _lib
+from .extract import EXTRACT_K, PackedModel, _al, pack_model
+from .ops import _call, _f32c, _need_hip, _ptr, _stream
+
+BRICK = 8                       # TS_MESH_BRICK
+BRICK_CORNERS = 729             # TS_MESH_BRICK_CORNERS
+_MAX_BRICKS = (2 ** 31 - 1) // (BRICK_CORNERS * EXTRACT_K)
+
+
+def level_floor(extent_sigmas: float) -> float:
+    """``16 exp(-extent_sigmas^2 / 2)``: the most the density reaches outside every Gaussian's box."""
+    return EXTRACT_K * math.exp(-0.5 * float(extent_sigmas) ** 2)
+
+
+@dataclass
+class MeshConfig:
+    """``surface_level`` as ``ExtractConfig``; ``resolution``: cells along the longest axis of the bounds (256, the
+    reference's literal); ``bounds``: ``(lo, hi)``, or None for the union of the Gaussians' boxes; ``extent_sigmas``:
+    the half-size of a Gaussian's box in standard deviations per world axis; ``sparse=False`` evaluates every brick (a
+    test and timing yardstick); ``max_workspace_bytes`` bounds the brick flags and every transient buffer of a chunk
+    of bricks (the emitted triangles, the packed records and the returned tensors come on top)."""
+    surface_level: float = 0.3
+    resolution: int = 256
+    bounds: Optional[Tuple[Sequence[float], Sequence[float]]] = None
+    extent_sigmas: float = 3.0
+    sparse: bool = True
+    normals: bool = True
+    max_workspace_bytes: int = 256 << 20
+
+    def __post_init__(self):
+        if not (isinstance(self.extent_sigmas, (int, float)) and math.isfinite(self.extent_sigmas)
+                and self.extent_sigmas > 0):
+            raise ValueError("extent_sigmas must be positive and finite")
+        if not math.isfinite(float(self.surface_level)):
+            raise ValueError("surface_level must be finite")
+        if not float(self.surface_level) > level_floor(self.extent_sigmas):
+            raise ValueError(f"surface_level = {self.surface_level} is not above 16 exp(-extent_sigmas^2 / 2) = "
+                             f"{level_floor(self.extent_sigmas):.4f}: the density may reach it outside every Gaussian's "
+                             "box and the sparse grid would miss surface")
+        if int(self.resolution) < 1:
+            raise ValueError("resolution must be at least 1")
+        if int(self.max_workspace_bytes) < 1:
+            raise ValueError("max_workspace_bytes must be positive")
+        if self.bounds is not None:
+            _check_bounds(*self.bounds)
+
+
+@dataclass
+class TriangleMesh:
+    """``vertices`` float32 [V,3] in ascending order of their edge keys; ``faces`` int32 [F,3], wound so that the
+    geometric normal points towards falling density; ``normals`` float32 [V,3], ``-grad d / |grad d|`` at the vertices
+    (zero where undefined), or None."""
+    vertices: Tensor
+    faces: Tensor
+    normals: Optional[Tensor]
+
+
+def _check_bounds(lo, hi):
+    lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("bounds must be (lo [3], hi [3])")
+    if not all(math.isfinite(v) for v in lo + hi):
+        raise ValueError("bounds must be finite")
+    if not all(b > a for a, b in zip(lo, hi)):
+        raise ValueError("bounds must be non-empty on every axis")
+    return lo, hi
+
+
+def make_grid(lo, hi, resolution: int):
+    """-> ``(lo float32 x 3, h float32, cells per axis)``: cubes of edge ``h = max(hi - lo) / resolution`` and
+    ``ceil((hi_a - lo_a) / h)`` cells on axis a (``resolution`` on the longest).  ``lo`` and ``hi`` are rounded to
+    float32 first; corner (i, j, k) sits at the float32 ``lo + (i, j, k) * h``."""
+    lo, hi = _check_bounds(lo, hi)
+    res = int(resolution)
+    if res < 1:
+        raise ValueError("resolution must be at least 1")
+    f32 = lambda v: ctypes.c_float(v).value
+    lo, hi = [f32(v) for v in lo], [f32(v) for v in hi]
+    ext = [b - a for a, b in zip(lo, hi)]
+    longest = max(ext)
+    h = f32(longest / res)
+    if not (longest > 0 and h > 0 and math.isfinite(h)):
+        raise ValueError("bounds must be non-empty on every axis")
+    # (hi_a - lo_a) / h with h = longest / res, taken as a ratio so that the longest axis has exactly `res` cells
+    cells = [max(1, math.ceil(e / longest * res - 1e-9)) for e in ext]
+    return lo, h, cells
+
+
+class _Chunk:
+    """One workspace tensor carved in the order of ``ts_mesh_chunk_bytes``."""
+
+    def __init__(self, lib, n: int, bricks: int, dev):
+        total = int(lib.ts_mesh_chunk_bytes(n, bricks))
+        self.buf = torch.empty((total,), dtype=torch.uint8, device=dev)
+        self.bytes = total
+        q = bricks * BRICK_CORNERS
+        at = [0]
+
+        def take(nbytes, dtype, shape):
+            view = self.buf[at[0]:at[0] + nbytes].view(dtype).view(shape)
+            at[0] += _al(nbytes)
+            return view
+        knn_ws = int(lib.ts_knn_ws_bytes(n, q, EXTRACT_K))
+        self.knn_ws = take(knn_ws, torch.uint8, (knn_ws,))
+        self.corners = take(q * 12, torch.float32, (q, 3))
+        self.knn_dist = take(q * EXTRACT_K * 4, torch.float32, (q, EXTRACT_K))
+        self.knn_idx = take(q * EXTRACT_K * 4, torch.int32, (q, EXTRACT_K))
+        self.density = take(q * 4, torch.float32, (q,))
+        self.counts = take(bricks * 4, torch.int32, (bricks,))
+        self.offsets = take(bricks * 8, torch.int64, (bricks,))
+        self.stats = take(bricks * 8, torch.int32, (bricks, 2))
+        assert at[0] == total, (at[0], total)
+
+
+def _largest(fits, limit: int) -> int:
+    """The largest count in 1..limit that ``fits`` (monotone), 0 if none."""
+    if fits(limit):
+        return limit
+    lo, hi = 0, limit
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if fits(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+@torch.no_grad()
+def gaussian_boxes(model, extent_sigmas: float = 3.0) -> Tensor:
+    """``ts_mesh_boxes``: float32 [N,6], ``{lo, hi}`` of every Gaussian's axis-aligned box of half-size
+    ``extent_sigmas * sqrt(Sigma_aa)``."""
+    means, scales, quats = (_f32c(t.detach()) for t in (model.means, model.scales, model.quats))
+    dev = _need_hip(means, scales, quats)
+    n = means.shape[0]
+    boxes = torch.empty((n, 6), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _call("ts_mesh_boxes", _lib.load().ts_mesh_boxes, n, _ptr(means), _ptr(scales), _ptr(quats),
+              float(extent_sigmas), _ptr(boxes), _stream(dev))
+    return boxes
+
+
+@torch.no_grad()
+def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool = False,
+                 packed: Optional[PackedModel] = None):
+    """The level set ``d = config.surface_level`` of ``model`` as a ``TriangleMesh`` on the model's device.
+
+    Stages: the Gaussians' boxes and (by default) the bounds as their union; the flags of the bricks a box reaches and
+    their ascending list; per chunk of listed bricks (sized so that one chunk's buffers fit
+    ``config.max_workspace_bytes``) the 9^3 corner positions, their 16 neighbours (``ts_knn``), the densities, the
+    triangle counts and the triangles as edge keys and positions; then the vertices are welded by key
+    (``torch.unique``: ascending key order, the first occurrence's position - all occurrences are bit-identical) and the
+    normals evaluated at them.  The mesh is a fixed function of (model, config): the same for any chunk size and for
+    ``sparse`` on or off.  A surface that leaves the bounds is cut there (an open boundary).
+
+    ``return_debug``: also a dict of ``active_bricks`` int64 [A], ``cell`` int64 [T] and ``keys`` int64 [T,3] per
+    triangle before welding, ``corners`` float32 [A,729,3], ``knn`` int32 [A,729,16] and ``density`` float32 [A,729] of
+    the active bricks, ``knn_fallback`` int32 [A] (the corner queries of each brick that took ``ts_knn``'s brute-force
+    pass: the search then runs brick by brick, with the same result), ``chunks``, ``total_bricks`` and ``grid``
+    (``lo``, ``h``, ``cells``).  ``packed``: a ``pack_model`` result to reuse."""
+    cfg = config if config is not None else MeshConfig()
+    pk = packed if packed is not None else pack_model(model)            # refuses fewer than 16 Gaussians
+    dev = _need_hip(pk.means, pk.records)
+    n = pk.means.shape[0]
+    lib = _lib.load()
+    cap = int(cfg.max_workspace_bytes)
+    level = float(cfg.surface_level)
+    boxes = gaussian_boxes(model, cfg.extent_sigmas)
+    if cfg.bounds is None:
+        lo_t, hi_t = boxes[:, :3].amin(0).tolist(), boxes[:, 3:].amax(0).tolist()
+        try:
+            lo_hi = _check_bounds(lo_t, hi_t)
+        except ValueError as e:
+            raise ValueError(f"the union of the Gaussians' boxes is no usable bound ({e}); give bounds") from None
+    else:
+        lo_hi = _check_bounds(*cfg.bounds)
+    glo, h, cells = make_grid(*lo_hi, cfg.resolution)
+    nb = [-(-c // BRICK) for c in cells]
+    total_bricks = nb[0] * nb[1] * nb[2]
+    if total_bricks > cap:
+        raise ValueError(f"the flags of {total_bricks} bricks do not fit max_workspace_bytes = {cap}")
+    one = int(lib.ts_mesh_chunk_bytes(n, 1))
+    if one > cap:
+        raise ValueError(f"max_workspace_bytes = {cap} is below the {one} bytes one brick over {n} Gaussians needs")
+    grid_host = (ctypes.c_float * 4)(*glo, h)
+    cells_host = (ctypes.c_int32 * 3)(*cells)
+    f32 = dict(dtype=torch.float32, device=dev)
+    tri_keys, tri_pos, tri_cell = [], [], []
+    dbg = {k: [] for k in ("corners", "knn", "density", "knn_fallback")} if return_debug else None
+    chunks = 0
+    with torch.cuda.device(dev):
+        s = _stream(dev)
+        if cfg.sparse:
+            flags = torch.zeros((total_bricks,), dtype=torch.uint8, device=dev)
+            _call("ts_mesh_mark", lib.ts_mesh_mark, n, _ptr(boxes), grid_host, cells_host, _ptr(flags), s)
+            active = torch.nonzero(flags).view(-1)                      # ascending, as the survivors of section 6f
+            del flags
+        else:
+            active = torch.arange(total_bricks, dtype=torch.int64, device=dev)
+        a = int(active.shape[0])
+        if a:
+            per = _largest(lambda b: int(lib.ts_mesh_chunk_bytes(n, b)) <= cap, min(a, _MAX_BRICKS))
+            ck = _Chunk(lib, n, per, dev)
+            for b0 in range(0, a, per):
+                b = min(per, a - b0)
+                q = b * BRICK_CORNERS
+                chunks += 1
+                ids = active[b0:b0 + b]
+                _call("ts_mesh_corners", lib.ts_mesh_corners, b, _ptr(ids), grid_host, cells_host, _ptr(ck.corners), s)
+                if return_debug:
+                    # brick by brick, for the per-brick share of brute-force queries; the lists are the same
+                    for i in range(b):
+                        r = slice(i * BRICK_CORNERS, (i + 1) * BRICK_CORNERS)
+                        _call("ts_knn", lib.ts_knn, n, _ptr(pk.means), BRICK_CORNERS, _ptr(ck.corners[r]), EXTRACT_K,
+                              _ptr(ck.knn_dist[r]), _ptr(ck.knn_idx[r]), _ptr(ck.knn_ws), _ptr(ck.stats[i]), s)
+                else:
+                    _call("ts_knn", lib.ts_knn, n, _ptr(pk.means), q, _ptr(ck.corners), EXTRACT_K, _ptr(ck.knn_dist),
+                          _ptr(ck.knn_idx), _ptr(ck.knn_ws), None, s)
+                _call("ts_mesh_density", lib.ts_mesh_density, n, b, _ptr(ids), grid_host, cells_host, _ptr(ck.corners),
+                      _ptr(ck.knn_idx), _ptr(pk.records), _ptr(ck.density), s)
+                if return_debug:
+                    dbg["corners"].append(ck.corners[:q].view(b, BRICK_CORNERS, 3).clone())
+                    dbg["knn"].append(ck.knn_idx[:q].view(b, BRICK_CORNERS, EXTRACT_K).clone())
+                    dbg["density"].append(ck.density[:q].view(b, BRICK_CORNERS).clone())
+                    dbg["knn_fallback"].append(ck.stats[:b, 0].clone())
+                # no corner above the level: no triangle, and nothing to launch
+                if not bool((ck.density[:q] > level).any()):
+                    continue
+                _call("ts_mesh_count", lib.ts_mesh_count, b, _ptr(ids), grid_host, cells_host, level, _ptr(ck.density),
+                      _ptr(ck.counts), s)
+                ends = torch.cumsum(ck.counts[:b], 0, dtype=torch.int64)
+                t = int(ends[-1])
+                if t == 0:
+                    continue
+                ck.offsets[:b] = ends - ck.counts[:b]
+                keys = torch.empty((t, 3), dtype=torch.int64, device=dev)
+                pos = torch.empty((t, 3, 3), **f32)
+                cell = torch.empty((t,), dtype=torch.int64, device=dev) if return_debug else None
+                _call("ts_mesh_emit", lib.ts_mesh_emit, b, _ptr(ids), grid_host, cells_host, level, _ptr(ck.density),
+                      _ptr(ck.offsets), _ptr(keys), _ptr(pos), _ptr(cell), s)
+                tri_keys.append(keys)
+                tri_pos.append(pos)
+                if return_debug:
+                    tri_cell.append(cell)
+            del ck
+
+        def cat(parts, shape, dtype):
+            return torch.cat(parts) if parts else torch.empty(shape, dtype=dtype, device=dev)
+        keys = cat(tri_keys, (0, 3), torch.int64)
+        pos = cat(tri_pos, (0, 3, 3), torch.float32)
+        del tri_keys, tri_pos
+        if keys.shape[0]:
+            uniq, inv = torch.unique(keys.view(-1), sorted=True, return_inverse=True)
+            v = int(uniq.shape[0])
+            if v >= 2 ** 31:
+                raise ValueError(f"{v} vertices do not fit int32 faces; lower the resolution")
+            occ = torch.arange(inv.shape[0], dtype=torch.int64, device=dev)
+            first = torch.full((v,), inv.shape[0], dtype=torch.int64, device=dev).scatter_reduce_(
+                0, inv, occ, reduce="amin", include_self=True)
+            vertices = pos.view(-1, 3).index_select(0, first)
+            faces = inv.view(-1, 3).to(torch.int32)
+            del uniq, inv, occ, first
+        else:
+            vertices = torch.empty((0, 3), **f32)
+            faces = torch.empty((0, 3), dtype=torch.int32, device=dev)
+        del pos
+        normals = None
+        if cfg.normals:
+            v = int(vertices.shape[0])
+            normals = torch.empty((v, 3), **f32)
+            if v:
+                def fits(p):
+                    return int(lib.ts_knn_ws_bytes(n, p, EXTRACT_K)) + 2 * _al(p * EXTRACT_K * 4) <= cap
+                per = _largest(fits, min(v, (2 ** 31 - 2) // EXTRACT_K))
+                if per < 1:
+                    raise ValueError(f"max_workspace_bytes = {cap} is too small for the normals of one vertex")
+                ws = torch.empty((int(lib.ts_knn_ws_bytes(n, per, EXTRACT_K)),), dtype=torch.uint8, device=dev)
+                dist = torch.empty((per, EXTRACT_K), **f32)
+                idx = torch.empty((per, EXTRACT_K), dtype=torch.int32, device=dev)
+                for v0 in range(0, v, per):
+                    p = min(per, v - v0)
+                    pts = vertices[v0:v0 + p]
+                    _call("ts_knn", lib.ts_knn, n, _ptr(pk.means), p, _ptr(pts), EXTRACT_K, _ptr(dist), _ptr(idx),
+                          _ptr(ws), None, s)
+                    _call("ts_extract_normals", lib.ts_extract_normals, n, p, _ptr(pts), _ptr(idx), _ptr(pk.records),
+                          _ptr(normals[v0:v0 + p]), s)
+    mesh = TriangleMesh(vertices, faces, normals)
+    if not return_debug:
+        return mesh
+    shapes = {"corners": ((0, BRICK_CORNERS, 3), torch.float32), "knn": ((0, BRICK_CORNERS, EXTRACT_K), torch.int32),
+              "density": ((0, BRICK_CORNERS), torch.float32), "knn_fallback": ((0,), torch.int32)}
+    debug = {k: cat(v, *shapes[k]) for k, v in dbg.items()}
+    debug.update(active_bricks=active, keys=keys, cell=cat(tri_cell, (0,), torch.int64), chunks=chunks,
+                 total_bricks=total_bricks, grid={"lo": tuple(glo), "h": h, "cells": tuple(cells)})
+    return mesh, debug

@@ -1,0 +1,132 @@
+#!/usr/bin/env python
+"""Times the iso-surface mesh extraction (tinysplat_amd.mesh) with device events after a warm-up; prints one JSON line
+per measurement (ms).
+
+  * ``extract_mesh``: the whole call on N Gaussians at one resolution, with the vertex and face counts, the active
+    brick share, the chunks and the peak memory over the model against the workspace cap;
+  * its parts, per entry of the C ABI (``ops.kernel_timer``: events around every launch); what remains of the whole is
+    torch (nonzero, scans, ``unique``) and host time;
+  * ``fallback share``: the corner queries that took ``ts_knn``'s brute-force pass, from a separate run that asks every
+    chunk's search for its statistics;
+  * ``--dense``: the same call with ``sparse=False`` (every brick), the baseline of the sparse grid.
+
+    python tools/time_mesh.py [--scene sheet|volume] [--n 1000000] [--resolution 256] [--dense] [--reps 3] [--out f.jsonl]
+"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
+
+from tinysplat_amd import _lib  # noqa: E402
+from tinysplat_amd.extract import EXTRACT_K, pack_model  # noqa: E402
+from tinysplat_amd.mesh import BRICK_CORNERS, MeshConfig, extract_mesh  # noqa: E402
+from tinysplat_amd.ops import _ptr, _stream, kernel_timer  # noqa: E402
+from tinysplat_amd.synthetic import make_scene  # noqa: E402
+from time_extract import sheet_scene, timed  # noqa: E402
+
+DEV = "cuda:0"
+
+
+@torch.no_grad()
+def fallback_share(model, pk, cfg, active, grid, chunk_bricks=1024):
+    """The share of the active bricks' corner queries that take ``ts_knn``'s brute-force pass."""
+    import ctypes
+    lib = _lib.load()
+    dev = torch.device(DEV)
+    n = pk.means.shape[0]
+    grid_host = (ctypes.c_float * 4)(*grid["lo"], grid["h"])
+    cells_host = (ctypes.c_int32 * 3)(*grid["cells"])
+    q = chunk_bricks * BRICK_CORNERS
+    ws = torch.empty(int(lib.ts_knn_ws_bytes(n, q, EXTRACT_K)), dtype=torch.uint8, device=dev)
+    corners = torch.empty((q, 3), device=dev)
+    dist = torch.empty((q, EXTRACT_K), device=dev)
+    idx = torch.empty((q, EXTRACT_K), dtype=torch.int32, device=dev)
+    stats = torch.zeros((2,), dtype=torch.int32, device=dev)
+    took = 0
+    s = _stream(dev)
+    for b0 in range(0, active.shape[0], chunk_bricks):
+        ids = active[b0:b0 + chunk_bricks]
+        b = int(ids.shape[0])
+        assert lib.ts_mesh_corners(b, _ptr(ids), grid_host, cells_host, _ptr(corners), s) == 0
+        assert lib.ts_knn(n, _ptr(pk.means), b * BRICK_CORNERS, _ptr(corners), EXTRACT_K, _ptr(dist), _ptr(idx),
+                          _ptr(ws), _ptr(stats), s) == 0
+        took += int(stats[0])
+    return took / max(1, active.shape[0] * BRICK_CORNERS)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--resolution", type=int, default=256)
+    ap.add_argument("--scene", choices=("volume", "sheet"), default="sheet")
+    ap.add_argument("--dense", action="store_true")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: nothing to time")
+    rows = []
+
+    def emit(call, ms, **kw):
+        rows.append({"call": call, "ms": round(ms, 4), **kw})
+        print(json.dumps(rows[-1]), flush=True)
+
+    w, h = 1920, 1080
+    if args.scene == "volume":
+        model, _ = make_scene(args.n, 0, w, h, seed=0, scale_mult=4.0, opacity_logit_mean=2.0)
+    else:
+        model = sheet_scene(args.n, w, h)
+    model = model.to(DEV)
+    pk = pack_model(model)
+    cfg = MeshConfig(resolution=args.resolution, sparse=not args.dense)
+    shape = dict(scene=args.scene, n=args.n, resolution=args.resolution, sparse=cfg.sparse)
+
+    def run():
+        return extract_mesh(model, cfg, packed=pk)
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    total = timed(run, args.reps)
+    peak = torch.cuda.max_memory_allocated() - base
+    mesh = run()
+    # the bricks, from a run of the marking stage alone
+    from tinysplat_amd.mesh import BRICK, gaussian_boxes, make_grid
+    import ctypes
+    boxes = gaussian_boxes(model, cfg.extent_sigmas)
+    glo, gh, cells = make_grid(boxes[:, :3].amin(0).tolist(), boxes[:, 3:].amax(0).tolist(), cfg.resolution)
+    nb = [-(-c // BRICK) for c in cells]
+    bricks = nb[0] * nb[1] * nb[2]
+    flags = torch.zeros((bricks,), dtype=torch.uint8, device=DEV)
+    lib = _lib.load()
+    assert lib.ts_mesh_mark(args.n, _ptr(boxes), (ctypes.c_float * 4)(*glo, gh), (ctypes.c_int32 * 3)(*cells),
+                            _ptr(flags), _stream(torch.device(DEV))) == 0
+    marked = torch.nonzero(flags).view(-1)
+    active = marked if cfg.sparse else torch.arange(bricks, dtype=torch.int64, device=DEV)
+    emit("extract_mesh", total, vertices=int(mesh.vertices.shape[0]), faces=int(mesh.faces.shape[0]), cells=cells,
+         bricks=bricks, marked_bricks=int(marked.shape[0]), evaluated_bricks=int(active.shape[0]),
+         active_share=round(int(marked.shape[0]) / bricks, 5), peak_mib=round(peak / 2 ** 20, 1),
+         cap_mib=cfg.max_workspace_bytes >> 20, **shape)
+    kernel_timer.start()
+    run()
+    parts = kernel_timer.stop()
+    inside = 0.0
+    for name, (launches, mean_ms) in sorted(parts.items()):
+        inside += launches * mean_ms
+        emit("part " + name, launches * mean_ms, launches=launches, **shape)
+    emit("part torch and host (the rest)", total - inside, **shape)
+    grid = {"lo": glo, "h": gh, "cells": cells}
+    emit("fallback share", 0.0, share=round(fallback_share(model, pk, cfg, active, grid), 5),
+         corner_queries=int(active.shape[0]) * BRICK_CORNERS, **shape)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text("\n".join(json.dumps(r) for r in rows) + "\n")
+
+
+if __name__ == "__main__":
+    main()
