@@ -291,3 +291,39 @@ def test_ply_of_a_gpu_mesh_reads_back(tmp_path):
         v, n, f = read(tmp_path / name)
         assert np.array_equal(v, mesh.vertices.cpu().numpy()) and np.array_equal(n, mesh.normals.cpu().numpy())
         assert np.array_equal(f, mesh.faces.cpu().numpy())
+
+
+def test_mesh_and_march_evaluate_one_density():
+    """``ts_mesh_density`` and ``ts_extract_march`` are handed the same positions, neighbour lists and records: their
+    densities are equal bit for bit (one ``density_at``, csrc/density_field.h).  One brick of 8 x 8 x 7 cells; the
+    float64 oracle gives 648 corners inside the grid, 32 above the level and 51 in (1e-6, 0.3)."""
+    from tinysplat_amd import _lib
+    from tinysplat_amd.extract import pack_model
+    from tinysplat_amd.mesh import MeshConfig, extract_mesh
+    from tinysplat_amd.ops import _call, _ptr, _stream
+    model = _model(MO.sheet_scene(SEED))
+    pk = pack_model(model)
+    _, dbg = extract_mesh(model, MeshConfig(resolution=8, bounds=BOUNDS), return_debug=True, packed=pk)
+    assert dbg["grid"]["cells"] == (8, 8, 7) and dbg["active_bricks"].tolist() == [0]
+    # the brick's 729 corners as 243 rays of 3 samples; what the march reads besides is arbitrary and finite
+    m, steps = 243, 3
+    corners, knn = dbg["corners"].view(m * steps, 3), dbg["knn"].view(m * steps, 16)
+    dev = corners.device
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    p_world, dirs, p_std, valid = torch.zeros((m, 3), **f32), torch.zeros((m, 3), **f32), torch.ones((m,), **f32), \
+        torch.ones((m,), **i32)
+    keep, first, t, points = torch.empty((m,), **i32), torch.empty((m,), **i32), torch.empty((m,), **f32), \
+        torch.empty((m, 3), **f32)
+    march = torch.empty((m * steps,), **f32)
+    with torch.cuda.device(dev):
+        _call("ts_extract_march", _lib.load().ts_extract_march, pk.means.shape[0], m, steps, 3.0, LEVEL, _ptr(corners),
+              _ptr(knn), _ptr(pk.records), _ptr(p_world), _ptr(dirs), _ptr(p_std), _ptr(valid), _ptr(keep), _ptr(first),
+              _ptr(t), _ptr(points), _ptr(march), _stream(dev))
+    torch.cuda.synchronize()
+    _, inside = _brick_corner_index(np.zeros(1, dtype=np.int64), dbg["grid"]["cells"])
+    sel = torch.from_numpy(inside.reshape(-1)).to(dev)
+    mesh_d, march_d = dbg["density"].view(-1)[sel], march[sel]
+    above, below = int((mesh_d > LEVEL).sum()), int(((mesh_d > 1e-6) & (mesh_d < LEVEL)).sum())
+    print(f"\n{int(sel.sum())} corners compared, {above} above the level, {below} in (1e-6, level)")
+    assert int(sel.sum()) >= 600 and above >= 20 and below >= 20
+    assert torch.equal(march_d, mesh_d)

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tinysplat_hip.h"
+#include "host_util.h"
 #include "pack.h"
 #include "splat_math.h"
 
@@ -897,8 +898,6 @@ __global__ __launch_bounds__(kThreads) void pack_splats_kernel(int n, const ts::
     }
     ts::pack_one(a, i, c0, c1, c2, c3);
 }
-
-inline int launch_status() { return (int)hipGetLastError(); }
 
 }  // namespace
 

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tinysplat_hip.h"
+#include "host_util.h"
 
 namespace {
 
@@ -30,7 +31,6 @@ constexpr int kFieldBits = 21;                    // so they are scanned togethe
 constexpr long long kFieldMask = (1ll << kFieldBits) - 1;
 typedef long long packed_t;
 
-inline int launch_status() { return (int)hipGetLastError(); }
 inline int num_blocks(int n) { return (n + kBlockItems - 1) / kBlockItems; }
 
 __global__ __launch_bounds__(kThreads) void grad_accum_kernel(int n, const float2* __restrict__ v_xy,

@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "../../include/tinysplat_hip.h"
+#include "host_util.h"
 
 #ifndef TS_PIX_OFF
 #define TS_PIX_OFF 0.0f
@@ -33,8 +34,6 @@ constexpr int kK = TS_DENSITY_K;
 constexpr int kRow = TS_DENSITY_ROW;                // gradient row: mu xyz | s xyz | q wxyz | opacity
 constexpr int kFrozen = TS_DENSITY_FROZEN;          // per sample: xi xyz | exp(s) xyz | q wxyz
 constexpr int kChunk = 128;
-
-inline int launch_status() { return (int)hipGetLastError(); }
 
 struct Mats {
     float v[16];    // world -> camera, row-major
@@ -517,16 +516,15 @@ __global__ __launch_bounds__(kThreads) void segment_join_kernel(int64_t T, const
     for (int d = 0; d < D; ++d) out[(int64_t)key * D + d] = (float)(acc[d] * (double)sc);
 }
 
-inline int64_t nblocks(int64_t n) { return (n + kThreads - 1) / kThreads; }
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 inline int64_t scan_blocks(int64_t n) { return (n + kThreads * kScanItems - 1) / (kThreads * kScanItems); }
-inline int loss_blocks(int32_t m) { return (int)nblocks(m < 1 ? 1 : m); }
+inline int loss_blocks(int32_t m) { return (int)nblocks(m < 1 ? 1 : m, kThreads); }
 
 void scan(int64_t n, const double* in, double* out, double* totals, hipStream_t s) {
     const int64_t nb = scan_blocks(n);
     hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, n, in, out, totals);
     hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(kThreads), 0, s, nb, totals);
-    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nblocks(n)), dim3(kThreads), 0, s, n, (const double*)totals, out);
+    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nblocks(n, kThreads)), dim3(kThreads), 0, s, n,
+                       (const double*)totals, out);
 }
 
 }  // namespace
@@ -551,7 +549,8 @@ int ts_density_sample(int32_t n, int32_t m, int32_t weights, const float* means,
     double* totals = (double*)((char*)ws + 2 * align256((int64_t)n * 8));
     const double* cdf = nullptr;
     if (!rows_in) {
-        hipLaunchKernelGGL(weights_kernel, dim3((unsigned)nblocks(n)), dim3(kThreads), 0, s, (int)n, scales, a);
+        hipLaunchKernelGGL(weights_kernel, dim3((unsigned)nblocks(n, kThreads)), dim3(kThreads), 0, s, (int)n, scales,
+                           a);
         scan(n, a, c, totals, s);                  // C_i = a_0 + ... + a_i
         if (weights == TS_DENSITY_WEIGHTS_REFERENCE) {
             scan(n, c, a, totals, s);              // the reference draws row i with weight C_i
@@ -560,8 +559,8 @@ int ts_density_sample(int32_t n, int32_t m, int32_t weights, const float* means,
             cdf = c;
         }
     }
-    hipLaunchKernelGGL(sample_kernel, dim3((unsigned)nblocks(m)), dim3(kThreads), 0, s, (int)n, (int)m, cdf, uniforms,
-                       rows_in, normals, means, scales, quats, rows, points, frozen);
+    hipLaunchKernelGGL(sample_kernel, dim3((unsigned)nblocks(m, kThreads)), dim3(kThreads), 0, s, (int)n, (int)m, cdf,
+                       uniforms, rows_in, normals, means, scales, quats, rows, points, frozen);
     return launch_status();
 }
 
@@ -615,7 +614,7 @@ int ts_segment_sum(int64_t entries, int32_t width, int32_t num_keys, const int32
     int32_t* flags = (int32_t*)((char*)ws + 2 * align256(nchunks * width * 8));
     hipError_t e = hipMemsetAsync(out, 0, (size_t)num_keys * (size_t)width * sizeof(float), s);
     if (e != hipSuccess) return (int)e;
-    const dim3 grid((unsigned)nblocks(nchunks));
+    const dim3 grid((unsigned)nblocks(nchunks, kThreads));
     if (width == 1) {
         hipLaunchKernelGGL(segment_local_kernel<1>, grid, dim3(kThreads), 0, s, entries, num_keys, keys_sorted, perm, vals,
                            scale, out, head, tail, flags);

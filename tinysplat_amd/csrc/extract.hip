@@ -15,11 +15,14 @@
 //             sample over its 16 neighbours; one ballot of d > level gives every ray's first crossing from its S-bit
 //             field, the two bracketing densities come by lane shuffle (no LDS, no second pass)
 //   normals   one thread per surviving point: -grad d / |grad d| over the point's own 16 neighbours
-// Plain stores, no atomics: every output is a fixed function of the inputs.
+// Plain stores, no atomics: every output is a fixed function of the inputs.  The record layout, pack's rotation and the
+// march's density_at live in density_field.h, which mesh.hip shares.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "../../include/tinysplat_hip.h"
+#include "density_field.h"
+#include "host_util.h"
 
 #ifndef TS_PIX_OFF
 #define TS_PIX_OFF 0.0f
@@ -28,11 +31,6 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kK = TS_EXTRACT_K;
-constexpr int kRec = TS_EXTRACT_RECORD;             // mean xyz | U00 U01 U02 U11 U12 U22 | sigmoid(o)
-
-inline int launch_status() { return (int)hipGetLastError(); }
-inline int64_t nblocks(int64_t n) { return (n + kThreads - 1) / kThreads; }
 
 struct RayCam {
     float inv[16];      // inverse(P V), row-major
@@ -46,16 +44,8 @@ __global__ __launch_bounds__(kThreads) void pack_kernel(int n, const float* __re
                                                         float* __restrict__ records, float* __restrict__ pstd) {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
-    // quat_to_rot_tensor (utils.py:42-64) of q / max(|q|, 1e-12), from the float32 parameters, in double
-    double q[4];
-    for (int c = 0; c < 4; ++c) q[c] = (double)quats[i * 4 + c];
-    const double nrm = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    const double den = fmax(nrm, 1e-12);
-    const double w = q[0] / den, x = q[1] / den, y = q[2] / den, z = q[3] / den;
     double R[3][3];
-    R[0][0] = 1. - 2. * (y * y + z * z); R[0][1] = 2. * (x * y - w * z); R[0][2] = 2. * (x * z + w * y);
-    R[1][0] = 2. * (x * y + w * z); R[1][1] = 1. - 2. * (x * x + z * z); R[1][2] = 2. * (y * z - w * x);
-    R[2][0] = 2. * (x * z - w * y); R[2][1] = 2. * (y * z + w * x); R[2][2] = 1. - 2. * (x * x + y * y);
+    quat_rotation(quats[i * 4], quats[i * 4 + 1], quats[i * 4 + 2], quats[i * 4 + 3], R);
     double iv[3];
     float es[3];
     for (int c = 0; c < 3; ++c) {
@@ -166,35 +156,6 @@ __global__ __launch_bounds__(kThreads) void samples_kernel(int n, int m, int S, 
     for (int c = 0; c < 3; ++c) samples[e * 3 + c] = p_world[i * 3 + c] + t * dirs[i * 3 + c];
 }
 
-// the density of one point over K neighbour records: sum sigmoid(o) exp(-clamp(q, 0, 1e8) / 2), q = |U (p - mu)|^2
-__device__ __forceinline__ float density_at(int n, const float* p, const int32_t* __restrict__ nbr,
-                                            const float* __restrict__ records) {
-    float dsum = 0.f;
-    const int4* nb4 = reinterpret_cast<const int4*>(nbr);        // rows of 16 int32: 64-byte aligned
-#pragma unroll
-    for (int g = 0; g < kK / 4; ++g) {
-        const int4 v = nb4[g];
-        const int js[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int j = js[t];
-            if (j < 0 || j >= n) continue;
-            const float2* r2 = reinterpret_cast<const float2*>(records + (int64_t)j * kRec);   // 40-byte records
-            const float2 a = r2[0], b = r2[1], c = r2[2], d = r2[3], e = r2[4];
-            const float dx = p[0] - a.x, dy = p[1] - a.y, dz = p[2] - b.x;
-            const float y0 = (b.y * dx + c.x * dy) + c.y * dz;
-            const float y1 = d.x * dy + d.y * dz;
-            const float y2 = e.x * dz;
-            const float qq = (y0 * y0 + y1 * y1) + y2 * y2;
-            // a q that is not a number (an infinite entry of U times a zero offset) counts as the clamp's upper end:
-            // the neighbour contributes nothing; fminf / fmaxf alone would turn it into 0 and a full sigmoid(o)
-            const float q = qq == qq ? fminf(fmaxf(qq, 0.f), 1e8f) : 1e8f;
-            dsum += e.y * expf(-0.5f * q);
-        }
-    }
-    return dsum > 1.f ? 1.f : dsum;                 // d[d > 1] = 1 + 1e-12, which is 1.0 in float32
-}
-
 __global__ __launch_bounds__(kThreads) void march_kernel(int n, int m, int S, int rpw, float extent, float level,
                                                          const float* __restrict__ samples,
                                                          const int32_t* __restrict__ knn,
@@ -281,8 +242,8 @@ extern "C" {
 int ts_extract_pack(int32_t n, const float* means, const float* scales, const float* quats, const float* opacities,
                     float* records, float* p_std, void* stream) {
     if (n < 1 || !means || !scales || !quats || !opacities || !records || !p_std) return TS_E_BADARG;
-    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)nblocks(n)), dim3(kThreads), 0, (hipStream_t)stream, (int)n, means,
-                       scales, quats, opacities, records, p_std);
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)nblocks(n, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                       (int)n, means, scales, quats, opacities, records, p_std);
     return launch_status();
 }
 
@@ -299,8 +260,9 @@ int ts_extract_rays(int32_t m, const int64_t* pixel_ids, int32_t height, int32_t
     cam.p23 = camera_host[20];
     for (int c = 0; c < TS_EXTRACT_CAMERA_FLOATS; ++c)
         if (!isfinite(camera_host[c])) return TS_E_BADARG;
-    hipLaunchKernelGGL(rays_kernel, dim3((unsigned)nblocks(m)), dim3(kThreads), 0, (hipStream_t)stream, (int)m,
-                       (int)height, (int)width, (int)convention, cam, pixel_ids, depth, anchor, p_world, dirs, valid);
+    hipLaunchKernelGGL(rays_kernel, dim3((unsigned)nblocks(m, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                       (int)m, (int)height, (int)width, (int)convention, cam, pixel_ids, depth, anchor, p_world, dirs,
+                       valid);
     return launch_status();
 }
 
@@ -309,7 +271,7 @@ int ts_extract_samples(int32_t n, int32_t m, int32_t steps, float extent_sigmas,
     if (n < 1 || m < 1 || !steps_ok(steps) || (int64_t)m * steps >= INT32_MAX) return TS_E_BADARG;
     if (!(extent_sigmas > 0.f) || !isfinite(extent_sigmas)) return TS_E_BADARG;
     if (!p_world || !dirs || !nearest || !p_std_table || !p_std || !samples) return TS_E_BADARG;
-    hipLaunchKernelGGL(samples_kernel, dim3((unsigned)nblocks((int64_t)m * steps)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(samples_kernel, dim3((unsigned)nblocks((int64_t)m * steps, kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, (int)n, (int)m, (int)steps, extent_sigmas, p_world, dirs, nearest, p_std_table,
                        p_std, samples);
     return launch_status();
@@ -335,8 +297,8 @@ int ts_extract_march(int32_t n, int32_t m, int32_t steps, float extent_sigmas, f
 int ts_extract_normals(int32_t n, int32_t m, const float* points, const int32_t* knn, const float* records,
                        float* normals, void* stream) {
     if (n < 1 || m < 1 || !points || !knn || !records || !normals) return TS_E_BADARG;
-    hipLaunchKernelGGL(normals_kernel, dim3((unsigned)nblocks(m)), dim3(kThreads), 0, (hipStream_t)stream, (int)n,
-                       (int)m, points, knn, records, normals);
+    hipLaunchKernelGGL(normals_kernel, dim3((unsigned)nblocks(m, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                       (int)n, (int)m, points, knn, records, normals);
     return launch_status();
 }
 
@@ -344,10 +306,10 @@ int64_t ts_extract_chunk_bytes(int32_t n, int32_t rays, int32_t steps) {
     if (n < TS_EXTRACT_K || rays < 1 || !steps_ok(steps) || (int64_t)rays * steps >= INT32_MAX) return TS_E_BADARG;
     const int64_t knn_ws = ts_knn_ws_bytes(n, (int32_t)((int64_t)rays * steps), TS_EXTRACT_K);
     if (knn_ws < 0) return TS_E_BADARG;
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
     const int64_t r = rays, e = (int64_t)rays * steps;
     // p_world, dirs, points | valid, keep, first, nearest, p_std, t, nearest's distance | samples | knn dist, idx
-    return knn_ws + 3 * al(r * 12) + 7 * al(r * 4) + al(e * 12) + 2 * al(e * TS_EXTRACT_K * 4);
+    return knn_ws + 3 * align256(r * 12) + 7 * align256(r * 4) + align256(e * 12) +
+           2 * align256(e * TS_EXTRACT_K * 4);
 }
 
 }  // extern "C"

@@ -11,11 +11,11 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tinysplat_hip.h"
+#include "host_util.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-inline int launch_status() { return (int)hipGetLastError(); }
 
 struct PlyTensors {
     float* means; float* dc; float* rest; float* opac; float* scales; float* quats;

@@ -39,6 +39,7 @@
 #include <climits>
 
 #include "../../include/tinysplat_hip.h"
+#include "host_util.h"
 
 namespace {
 
@@ -56,8 +57,6 @@ constexpr int kFallbackBlocks = 2048;
 constexpr int kMaxPoints = 1 << 28;
 constexpr unsigned long long kEmpty = ~0ull;           // never a key: keys use 63 bits
 constexpr double kInf = __builtin_huge_val();
-
-inline int launch_status() { return (int)hipGetLastError(); }
 
 struct KnnHeader {
     int bbox[6];                  // ordered-int min x y z, max x y z

@@ -2,14 +2,15 @@
 // bricks (8^3 cells) that a Gaussian's box reaches, on top of ts_knn and ts_extract_pack's records.
 //
 //   boxes     one thread per Gaussian: mean -+ extent * sqrt(Sigma_aa) per world axis, Sigma = R diag(exp(2 s)) R^T in
-//             double, rounded outwards.  A point outside the box has Mahalanobis q > extent^2 to that Gaussian
-//             ((e_a . x)^2 <= Sigma_aa x^T Sigma^-1 x), so outside every box d <= 16 exp(-extent^2 / 2).
+//             double (quat_rotation of density_field.h: the R the records are packed from), rounded outwards.  A point
+//             outside the box has Mahalanobis q > extent^2 to that Gaussian ((e_a . x)^2 <= Sigma_aa x^T Sigma^-1 x),
+//             so outside every box d <= 16 exp(-extent^2 / 2).
 //   mark      one thread per Gaussian: the flag of every brick holding a cell with a corner inside the box.  The corner
 //             range is found on the float32 corner positions themselves (ts_mesh_corner_pos), starting two corners
 //             wide and narrowing: never too small.  Plain byte stores of 1: idempotent, no atomics.
 //   corners   one thread per corner of a listed brick (9^3 each): its position.  A corner beyond the grid's last cell
 //             takes the position of the last corner of its axis: a finite query next to real ones, d = 0 regardless.
-//   density   one thread per corner: the 16-neighbour density (density_at of extract.hip, the same expression).
+//   density   one thread per corner: the 16-neighbour density (density_at of density_field.h).
 //   count     one workgroup per brick, one thread per cell: the brick's 729 densities in LDS, the cell's triangle count
 //   emit      (mesh_cells.h), an exclusive prefix over the workgroup (ballots of the count's four bits inside a wave,
 //             LDS across the eight waves); count stores the brick total, emit the triangles at offsets[brick] + prefix:
@@ -19,20 +20,17 @@
 #include <math.h>
 
 #include "../../include/tinysplat_hip.h"
+#include "density_field.h"
+#include "host_util.h"
 #include "mesh_cells.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kK = TS_EXTRACT_K;
-constexpr int kRec = TS_EXTRACT_RECORD;
 constexpr int kBrick = TS_MESH_BRICK;
 constexpr int kCorners = TS_MESH_BRICK_CORNERS;
 constexpr int kCells = TS_MESH_BRICK_CELLS;
 constexpr int64_t kMaxBricks = (int64_t)INT32_MAX / ((int64_t)kCorners * kK);   // corners * 16 stays below 2^31
-
-inline int launch_status() { return (int)hipGetLastError(); }
-inline int64_t nblocks(int64_t n) { return (n + kThreads - 1) / kThreads; }
 
 struct Grid {
     float lo[3];
@@ -52,16 +50,8 @@ __global__ __launch_bounds__(kThreads) void boxes_kernel(int n, float extent, co
                                                          const float* __restrict__ quats, float* __restrict__ boxes) {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
-    // the rotation as ts_extract_pack takes it: q / max(|q|, 1e-12), from the float32 parameters, in double
-    double q[4];
-    for (int c = 0; c < 4; ++c) q[c] = (double)quats[i * 4 + c];
-    const double nrm = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    const double den = fmax(nrm, 1e-12);
-    const double w = q[0] / den, x = q[1] / den, y = q[2] / den, z = q[3] / den;
     double R[3][3];
-    R[0][0] = 1. - 2. * (y * y + z * z); R[0][1] = 2. * (x * y - w * z); R[0][2] = 2. * (x * z + w * y);
-    R[1][0] = 2. * (x * y + w * z); R[1][1] = 1. - 2. * (x * x + z * z); R[1][2] = 2. * (y * z - w * x);
-    R[2][0] = 2. * (x * z - w * y); R[2][1] = 2. * (y * z + w * x); R[2][2] = 1. - 2. * (x * x + y * y);
+    quat_rotation(quats[i * 4], quats[i * 4 + 1], quats[i * 4 + 2], quats[i * 4 + 3], R);
     double var[3];
     for (int c = 0; c < 3; ++c) var[c] = exp(2.0 * (double)scales[i * 3 + c]);
     for (int a = 0; a < 3; ++a) {
@@ -121,33 +111,6 @@ __global__ __launch_bounds__(kThreads) void corners_kernel(int64_t total, Grid g
         if (i > g.n[a]) i = g.n[a];
         corners[e * 3 + a] = ts_mesh_corner_pos(g.lo[a], g.h, i);
     }
-}
-
-// density_at of extract.hip: sum sigmoid(o) exp(-clamp(q, 0, 1e8) / 2), q = |U (p - mu)|^2, the same expression
-__device__ __forceinline__ float density_at(int n, const float* p, const int32_t* __restrict__ nbr,
-                                            const float* __restrict__ records) {
-    float dsum = 0.f;
-    const int4* nb4 = reinterpret_cast<const int4*>(nbr);        // rows of 16 int32: 64-byte aligned
-#pragma unroll
-    for (int g = 0; g < kK / 4; ++g) {
-        const int4 v = nb4[g];
-        const int js[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int j = js[t];
-            if (j < 0 || j >= n) continue;
-            const float2* r2 = reinterpret_cast<const float2*>(records + (int64_t)j * kRec);   // 40-byte records
-            const float2 a = r2[0], b = r2[1], c = r2[2], d = r2[3], e = r2[4];
-            const float dx = p[0] - a.x, dy = p[1] - a.y, dz = p[2] - b.x;
-            const float y0 = (b.y * dx + c.x * dy) + c.y * dz;
-            const float y1 = d.x * dy + d.y * dz;
-            const float y2 = e.x * dz;
-            const float qq = (y0 * y0 + y1 * y1) + y2 * y2;
-            const float q = qq == qq ? fminf(fmaxf(qq, 0.f), 1e8f) : 1e8f;     // NaN: no contribution (extract.hip)
-            dsum += e.y * expf(-0.5f * q);
-        }
-    }
-    return dsum > 1.f ? 1.f : dsum;
 }
 
 __global__ __launch_bounds__(kThreads) void density_kernel(int n, int64_t total, Grid g,
@@ -274,8 +237,8 @@ int ts_mesh_boxes(int32_t n, const float* means, const float* scales, const floa
                   float* boxes, void* stream) {
     if (n < 1 || !means || !scales || !quats || !boxes) return TS_E_BADARG;
     if (!(extent_sigmas > 0.f) || !isfinite(extent_sigmas)) return TS_E_BADARG;
-    hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)nblocks(n)), dim3(kThreads), 0, (hipStream_t)stream, (int)n,
-                       extent_sigmas, means, scales, quats, boxes);
+    hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)nblocks(n, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                       (int)n, extent_sigmas, means, scales, quats, boxes);
     return launch_status();
 }
 
@@ -283,8 +246,8 @@ int ts_mesh_mark(int32_t n, const float* boxes, const float* grid_host, const in
                  void* stream) {
     Grid g;
     if (n < 1 || !boxes || !flags || !read_grid(grid_host, cells_host, &g)) return TS_E_BADARG;
-    hipLaunchKernelGGL(mark_kernel, dim3((unsigned)nblocks(n)), dim3(kThreads), 0, (hipStream_t)stream, (int)n, g, boxes,
-                       flags);
+    hipLaunchKernelGGL(mark_kernel, dim3((unsigned)nblocks(n, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                       (int)n, g, boxes, flags);
     return launch_status();
 }
 
@@ -293,10 +256,9 @@ int64_t ts_mesh_chunk_bytes(int32_t n, int32_t bricks) {
     const int64_t q = (int64_t)bricks * kCorners;
     const int64_t knn_ws = ts_knn_ws_bytes(n, (int32_t)q, TS_EXTRACT_K);
     if (knn_ws < 0) return TS_E_BADARG;
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
     // corners | k-NN distances, indices | densities | per brick: count (int32), offset (int64), k-NN stats (int32[2])
-    return knn_ws + al(q * 12) + 2 * al(q * TS_EXTRACT_K * 4) + al(q * 4) + al((int64_t)bricks * 4) +
-           2 * al((int64_t)bricks * 8);
+    return knn_ws + align256(q * 12) + 2 * align256(q * TS_EXTRACT_K * 4) + align256(q * 4) +
+           align256((int64_t)bricks * 4) + 2 * align256((int64_t)bricks * 8);
 }
 
 int ts_mesh_corners(int32_t bricks, const int64_t* brick_ids, const float* grid_host, const int32_t* cells_host,
@@ -304,8 +266,8 @@ int ts_mesh_corners(int32_t bricks, const int64_t* brick_ids, const float* grid_
     Grid g;
     if (!bricks_ok(bricks) || !brick_ids || !corners || !read_grid(grid_host, cells_host, &g)) return TS_E_BADARG;
     const int64_t total = (int64_t)bricks * kCorners;
-    hipLaunchKernelGGL(corners_kernel, dim3((unsigned)nblocks(total)), dim3(kThreads), 0, (hipStream_t)stream, total, g,
-                       brick_ids, corners);
+    hipLaunchKernelGGL(corners_kernel, dim3((unsigned)nblocks(total, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                       total, g, brick_ids, corners);
     return launch_status();
 }
 
@@ -316,8 +278,8 @@ int ts_mesh_density(int32_t n, int32_t bricks, const int64_t* brick_ids, const f
     if (n < TS_EXTRACT_K || !bricks_ok(bricks) || !read_grid(grid_host, cells_host, &g)) return TS_E_BADARG;
     if (!brick_ids || !corners || !knn || !records || !density) return TS_E_BADARG;
     const int64_t total = (int64_t)bricks * kCorners;
-    hipLaunchKernelGGL(density_kernel, dim3((unsigned)nblocks(total)), dim3(kThreads), 0, (hipStream_t)stream, (int)n,
-                       total, g, brick_ids, corners, knn, records, density);
+    hipLaunchKernelGGL(density_kernel, dim3((unsigned)nblocks(total, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                       (int)n, total, g, brick_ids, corners, knn, records, density);
     return launch_status();
 }
 

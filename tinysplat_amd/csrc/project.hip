@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tinysplat_hip.h"
+#include "host_util.h"
 #include "pack.h"
 #include "splat_math.h"
 #include "adam_math.h"
@@ -502,8 +503,6 @@ __global__ __launch_bounds__(kThreads) void gather48_kernel(const float4* __rest
     }
     if ((a.x + a.y) + (a.z + a.w) == 123456.789f) sink[0] = a.x;
 }
-
-inline int launch_status() { return (int)hipGetLastError(); }
 
 }  // namespace
 

@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "../../include/tinysplat_hip.h"
+#include "host_util.h"
 #include "raster_survivors.h"
 #include "splat_math.h"
 
@@ -2017,8 +2018,6 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
         v_colors[3 * i] = a1.z; v_colors[3 * i + 1] = a1.w; v_colors[3 * i + 2] = a2.x;
     }
 }
-
-inline int launch_status() { return (int)hipGetLastError(); }
 
 }  // namespace
 

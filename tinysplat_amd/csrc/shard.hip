@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tinysplat_hip.h"
+#include "host_util.h"
 #include "splat_math.h"
 
 namespace {
@@ -446,8 +447,6 @@ __global__ __launch_bounds__(kThreads) void import_pack_kernel(int m, const floa
     splats[3 * (size_t)j + 1] = q1;
     splats[3 * (size_t)j + 2] = make_float4(q2.x, q2.y, __int_as_float(slot_base), __int_as_float(w | (b.minx << 16)));
 }
-
-inline int launch_status() { return (int)hipGetLastError(); }
 
 inline bool bad_stripes(const ts_stripes* st, const ts_camera* cam) {
     if (!st || !cam || st->num < 1 || st->num > TS_MAX_RANKS) return true;

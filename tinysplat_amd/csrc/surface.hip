@@ -14,14 +14,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tinysplat_hip.h"
+#include "host_util.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 1024;
 constexpr float kEps = 1e-10f;
-
-inline int launch_status() { return (int)hipGetLastError(); }
 
 inline int entropy_blocks(int32_t n) {
     const int64_t b = ((int64_t)n + kThreads * 4 - 1) / (kThreads * 4);      // int64: no overflow near INT32_MAX

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tinysplat_hip.h"
+#include "host_util.h"
 #include "adam_math.h"
 
 namespace {
@@ -435,8 +436,6 @@ __global__ __launch_bounds__(kThreads) void loss_reduce_kernel(int H, int W, int
         out[3] = (float)(part[2][0] / ((double)H * (double)W));
     }
 }
-
-inline int launch_status() { return (int)hipGetLastError(); }
 
 }  // namespace
 

@@ -20,11 +20,10 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._field import EXTRACT_K, PackedModel, Workspace, cat, knn, largest, normals_at, pack_model
 from .ops import _call, _f32c, _need_hip, _ptr, _stream
 
-EXTRACT_K = 16                  # knn_points(..., K=16) (model_gaussian.py:260, :425)
 MAX_STEPS = 64                  # TS_EXTRACT_MAX_STEPS
-_RECORD = 10                    # TS_EXTRACT_RECORD
 _CONVENTIONS = {"reference": 0, "screen": 1}
 
 
@@ -104,81 +103,30 @@ def _camera_host(camera):
     return (ctypes.c_float * 21)(*vals)
 
 
-def _al(b: int) -> int:
-    return (b + 255) // 256 * 256
-
-
 def _chunk_rays(lib, n: int, m: int, steps: int, cap: int) -> int:
     """The largest number of rays (at most ``m``) whose chunk fits ``cap`` bytes."""
-    limit = min(m, (2 ** 31 - 2) // steps)
-    if int(lib.ts_extract_chunk_bytes(n, limit, steps)) <= cap:
-        return limit
-    lo, hi = 0, limit                       # chunk_bytes(lo) <= cap < chunk_bytes(hi); it grows with the rays
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        if int(lib.ts_extract_chunk_bytes(n, mid, steps)) <= cap:
-            lo = mid
-        else:
-            hi = mid
-    if lo < 1:
+    rays = largest(lambda r: int(lib.ts_extract_chunk_bytes(n, r, steps)) <= cap, min(m, (2 ** 31 - 2) // steps))
+    if rays < 1:
         need = int(lib.ts_extract_chunk_bytes(n, 1, steps))
         raise ValueError(f"max_workspace_bytes = {cap} is below the {need} bytes one ray over {n} Gaussians needs")
-    return lo
+    return rays
 
 
 class _Chunk:
-    """One workspace tensor carved in the order of ``ts_extract_chunk_bytes``."""
+    """The buffers of one chunk of rays, carved in the order of ``ts_extract_chunk_bytes``."""
 
     def __init__(self, lib, n: int, rays: int, steps: int, dev):
-        total = int(lib.ts_extract_chunk_bytes(n, rays, steps))
-        self.buf = torch.empty((total,), dtype=torch.uint8, device=dev)
-        self.bytes = total
+        ws = Workspace(int(lib.ts_extract_chunk_bytes(n, rays, steps)), dev)
         e = rays * steps
-        at = [0]
-
-        def take(nbytes, dtype, shape):
-            view = self.buf[at[0]:at[0] + nbytes].view(dtype).view(shape)
-            at[0] += _al(nbytes)
-            return view
-        knn_ws = int(lib.ts_knn_ws_bytes(n, e, EXTRACT_K))
-        self.knn_ws = take(knn_ws, torch.uint8, (knn_ws,))
         f32, i32 = torch.float32, torch.int32
-        self.p_world, self.dirs, self.points = (take(rays * 12, f32, (rays, 3)) for _ in range(3))
-        self.valid, self.keep, self.first, self.nearest = (take(rays * 4, i32, (rays,)) for _ in range(4))
-        self.p_std, self.t, self.nearest_dist = (take(rays * 4, f32, (rays,)) for _ in range(3))
-        self.samples = take(e * 12, f32, (e, 3))
-        self.knn_dist = take(e * EXTRACT_K * 4, f32, (e, EXTRACT_K))
-        self.knn_idx = take(e * EXTRACT_K * 4, i32, (e, EXTRACT_K))
-        assert at[0] == total, (at[0], total)
-
-
-@dataclass
-class PackedModel:
-    """``ts_extract_pack`` of a model: ``records`` float32 [N,10], ``p_std`` float32 [N], and the contiguous means
-    the neighbour searches run on."""
-    means: Tensor
-    records: Tensor
-    p_std: Tensor
-
-
-@torch.no_grad()
-def pack_model(model) -> PackedModel:
-    """Once per extraction: per Gaussian {mean, the Cholesky factor of Sigma^-1, sigmoid(opacity)} and
-    ``|exp(scales)|``.  Needs at least 16 Gaussians with finite means (the reference's k-NN would fail)."""
-    means, scales, quats, opac = (_f32c(t.detach()) for t in (model.means, model.scales, model.quats, model.opacities))
-    dev = _need_hip(means, scales, quats, opac)
-    n = means.shape[0]
-    if n < EXTRACT_K:
-        raise ValueError(f"the level-set extraction needs at least {EXTRACT_K} Gaussians, got {n}")
-    if not bool(torch.isfinite(means).all()):
-        raise ValueError("the means must be finite")
-    lib = _lib.load()
-    records = torch.empty((n, _RECORD), dtype=torch.float32, device=dev)
-    p_std = torch.empty((n,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _call("ts_extract_pack", lib.ts_extract_pack, n, _ptr(means), _ptr(scales), _ptr(quats), _ptr(opac),
-              _ptr(records), _ptr(p_std), _stream(dev))
-    return PackedModel(means, records, p_std)
+        self.knn_ws = ws.take(torch.uint8, int(lib.ts_knn_ws_bytes(n, e, EXTRACT_K)))
+        self.p_world, self.dirs, self.points = (ws.take(f32, rays, 3) for _ in range(3))
+        self.valid, self.keep, self.first, self.nearest = (ws.take(i32, rays) for _ in range(4))
+        self.p_std, self.t, self.nearest_dist = (ws.take(f32, rays) for _ in range(3))
+        self.samples = ws.take(f32, e, 3)
+        self.knn_dist = ws.take(f32, e, EXTRACT_K)
+        self.knn_idx = ws.take(i32, e, EXTRACT_K)
+        ws.done()
 
 
 @torch.no_grad()
@@ -228,13 +176,11 @@ def level_set_points(model, camera, depth: Tensor, pixel_ids: Tensor, config: Op
                 cid = ids[r0:r0 + r]
                 _call("ts_extract_rays", lib.ts_extract_rays, r, _ptr(cid), h, w, _ptr(depth), conv, cam_host,
                       _ptr(pk.means), _ptr(ck.p_world), _ptr(ck.dirs), _ptr(ck.valid), s)
-                _call("ts_knn", lib.ts_knn, n, _ptr(pk.means), r, _ptr(ck.p_world), 1, _ptr(ck.nearest_dist),
-                      _ptr(ck.nearest), _ptr(ck.knn_ws), None, s)
+                knn(lib, pk, ck.p_world, r, 1, ck.nearest_dist, ck.nearest, ck.knn_ws, None, s)
                 _call("ts_extract_samples", lib.ts_extract_samples, n, r, steps, float(cfg.extent_sigmas),
                       _ptr(ck.p_world), _ptr(ck.dirs), _ptr(ck.nearest), _ptr(pk.p_std), _ptr(ck.p_std),
                       _ptr(ck.samples), s)
-                _call("ts_knn", lib.ts_knn, n, _ptr(pk.means), r * steps, _ptr(ck.samples), EXTRACT_K,
-                      _ptr(ck.knn_dist), _ptr(ck.knn_idx), _ptr(ck.knn_ws), None, s)
+                knn(lib, pk, ck.samples, r * steps, EXTRACT_K, ck.knn_dist, ck.knn_idx, ck.knn_ws, None, s)
                 dens = torch.empty((r, steps), **f32) if return_debug else None
                 _call("ts_extract_march", lib.ts_extract_march, n, r, steps, float(cfg.extent_sigmas),
                       float(cfg.surface_level), _ptr(ck.samples), _ptr(ck.knn_idx), _ptr(pk.records), _ptr(ck.p_world),
@@ -258,25 +204,19 @@ def level_set_points(model, camera, depth: Tensor, pixel_ids: Tensor, config: Op
                 out_pix.append(cid.index_select(0, sel))
                 if cfg.normals:
                     nrm = torch.empty((p, 3), **f32)
-                    _call("ts_knn", lib.ts_knn, n, _ptr(pk.means), p, _ptr(pts), EXTRACT_K, _ptr(ck.knn_dist),
-                          _ptr(ck.knn_idx), _ptr(ck.knn_ws), None, s)
-                    _call("ts_extract_normals", lib.ts_extract_normals, n, p, _ptr(pts), _ptr(ck.knn_idx),
-                          _ptr(pk.records), _ptr(nrm), s)
+                    normals_at(lib, pk, pts, p, nrm, ck.knn_dist, ck.knn_idx, ck.knn_ws, s)
                     out_nrm.append(nrm)
-
-    def cat(parts, shape, dtype):
-        return torch.cat(parts) if parts else torch.empty(shape, dtype=dtype, device=dev)
-    points = cat(out_pts, (0, 3), torch.float32)
-    res = SurfacePoints(points, cat(out_nrm, (0, 3), torch.float32) if cfg.normals else None,
+    points = cat(out_pts, (0, 3), torch.float32, dev)
+    res = SurfacePoints(points, cat(out_nrm, (0, 3), torch.float32, dev) if cfg.normals else None,
                         torch.full((points.shape[0],), int(camera_index), dtype=torch.int32, device=dev),
-                        cat(out_pix, (0,), torch.int64), cat(out_t, (0,), torch.float32))
+                        cat(out_pix, (0,), torch.int64, dev), cat(out_t, (0,), torch.float32, dev))
     if not return_debug:
         return res
     shapes = {"samples": ((0, steps, 3), torch.float32), "knn": ((0, steps, EXTRACT_K), torch.int32),
               "density": ((0, steps), torch.float32), "p_world": ((0, 3), torch.float32),
               "dirs": ((0, 3), torch.float32), "p_std": ((0,), torch.float32), "nearest": ((0,), torch.int32),
               "valid": ((0,), torch.int32), "keep": ((0,), torch.int32), "first": ((0,), torch.int32)}
-    debug = {k: cat(v, *shapes[k]) for k, v in dbg.items()}
+    debug = {k: cat(v, *shapes[k], dev) for k, v in dbg.items()}
     debug["valid"], debug["keep"] = debug["valid"].bool(), debug["keep"].bool()
     debug["chunks"] = chunks
     return res, debug

@@ -27,7 +27,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .extract import EXTRACT_K, PackedModel, _al, pack_model
+from ._field import EXTRACT_K, PackedModel, Workspace, align256, cat, knn, largest, normals_at, pack_model
 from .ops import _call, _f32c, _need_hip, _ptr, _stream
 
 BRICK = 8                       # TS_MESH_BRICK
@@ -115,43 +115,20 @@ def make_grid(lo, hi, resolution: int):
 
 
 class _Chunk:
-    """One workspace tensor carved in the order of ``ts_mesh_chunk_bytes``."""
+    """The buffers of one chunk of bricks, carved in the order of ``ts_mesh_chunk_bytes``."""
 
     def __init__(self, lib, n: int, bricks: int, dev):
-        total = int(lib.ts_mesh_chunk_bytes(n, bricks))
-        self.buf = torch.empty((total,), dtype=torch.uint8, device=dev)
-        self.bytes = total
+        ws = Workspace(int(lib.ts_mesh_chunk_bytes(n, bricks)), dev)
         q = bricks * BRICK_CORNERS
-        at = [0]
-
-        def take(nbytes, dtype, shape):
-            view = self.buf[at[0]:at[0] + nbytes].view(dtype).view(shape)
-            at[0] += _al(nbytes)
-            return view
-        knn_ws = int(lib.ts_knn_ws_bytes(n, q, EXTRACT_K))
-        self.knn_ws = take(knn_ws, torch.uint8, (knn_ws,))
-        self.corners = take(q * 12, torch.float32, (q, 3))
-        self.knn_dist = take(q * EXTRACT_K * 4, torch.float32, (q, EXTRACT_K))
-        self.knn_idx = take(q * EXTRACT_K * 4, torch.int32, (q, EXTRACT_K))
-        self.density = take(q * 4, torch.float32, (q,))
-        self.counts = take(bricks * 4, torch.int32, (bricks,))
-        self.offsets = take(bricks * 8, torch.int64, (bricks,))
-        self.stats = take(bricks * 8, torch.int32, (bricks, 2))
-        assert at[0] == total, (at[0], total)
-
-
-def _largest(fits, limit: int) -> int:
-    """The largest count in 1..limit that ``fits`` (monotone), 0 if none."""
-    if fits(limit):
-        return limit
-    lo, hi = 0, limit
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        if fits(mid):
-            lo = mid
-        else:
-            hi = mid
-    return lo
+        self.knn_ws = ws.take(torch.uint8, int(lib.ts_knn_ws_bytes(n, q, EXTRACT_K)))
+        self.corners = ws.take(torch.float32, q, 3)
+        self.knn_dist = ws.take(torch.float32, q, EXTRACT_K)
+        self.knn_idx = ws.take(torch.int32, q, EXTRACT_K)
+        self.density = ws.take(torch.float32, q)
+        self.counts = ws.take(torch.int32, bricks)
+        self.offsets = ws.take(torch.int64, bricks)
+        self.stats = ws.take(torch.int32, bricks, 2)
+        ws.done()
 
 
 @torch.no_grad()
@@ -227,7 +204,7 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
             active = torch.arange(total_bricks, dtype=torch.int64, device=dev)
         a = int(active.shape[0])
         if a:
-            per = _largest(lambda b: int(lib.ts_mesh_chunk_bytes(n, b)) <= cap, min(a, _MAX_BRICKS))
+            per = largest(lambda b: int(lib.ts_mesh_chunk_bytes(n, b)) <= cap, min(a, _MAX_BRICKS))
             ck = _Chunk(lib, n, per, dev)
             for b0 in range(0, a, per):
                 b = min(per, a - b0)
@@ -239,11 +216,10 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
                     # brick by brick, for the per-brick share of brute-force queries; the lists are the same
                     for i in range(b):
                         r = slice(i * BRICK_CORNERS, (i + 1) * BRICK_CORNERS)
-                        _call("ts_knn", lib.ts_knn, n, _ptr(pk.means), BRICK_CORNERS, _ptr(ck.corners[r]), EXTRACT_K,
-                              _ptr(ck.knn_dist[r]), _ptr(ck.knn_idx[r]), _ptr(ck.knn_ws), _ptr(ck.stats[i]), s)
+                        knn(lib, pk, ck.corners[r], BRICK_CORNERS, EXTRACT_K, ck.knn_dist[r], ck.knn_idx[r], ck.knn_ws,
+                            ck.stats[i], s)
                 else:
-                    _call("ts_knn", lib.ts_knn, n, _ptr(pk.means), q, _ptr(ck.corners), EXTRACT_K, _ptr(ck.knn_dist),
-                          _ptr(ck.knn_idx), _ptr(ck.knn_ws), None, s)
+                    knn(lib, pk, ck.corners, q, EXTRACT_K, ck.knn_dist, ck.knn_idx, ck.knn_ws, None, s)
                 _call("ts_mesh_density", lib.ts_mesh_density, n, b, _ptr(ids), grid_host, cells_host, _ptr(ck.corners),
                       _ptr(ck.knn_idx), _ptr(pk.records), _ptr(ck.density), s)
                 if return_debug:
@@ -271,11 +247,8 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
                 if return_debug:
                     tri_cell.append(cell)
             del ck
-
-        def cat(parts, shape, dtype):
-            return torch.cat(parts) if parts else torch.empty(shape, dtype=dtype, device=dev)
-        keys = cat(tri_keys, (0, 3), torch.int64)
-        pos = cat(tri_pos, (0, 3, 3), torch.float32)
+        keys = cat(tri_keys, (0, 3), torch.int64, dev)
+        pos = cat(tri_pos, (0, 3, 3), torch.float32, dev)
         del tri_keys, tri_pos
         if keys.shape[0]:
             uniq, inv = torch.unique(keys.view(-1), sorted=True, return_inverse=True)
@@ -298,8 +271,8 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
             normals = torch.empty((v, 3), **f32)
             if v:
                 def fits(p):
-                    return int(lib.ts_knn_ws_bytes(n, p, EXTRACT_K)) + 2 * _al(p * EXTRACT_K * 4) <= cap
-                per = _largest(fits, min(v, (2 ** 31 - 2) // EXTRACT_K))
+                    return int(lib.ts_knn_ws_bytes(n, p, EXTRACT_K)) + 2 * align256(p * EXTRACT_K * 4) <= cap
+                per = largest(fits, min(v, (2 ** 31 - 2) // EXTRACT_K))
                 if per < 1:
                     raise ValueError(f"max_workspace_bytes = {cap} is too small for the normals of one vertex")
                 ws = torch.empty((int(lib.ts_knn_ws_bytes(n, per, EXTRACT_K)),), dtype=torch.uint8, device=dev)
@@ -307,17 +280,13 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
                 idx = torch.empty((per, EXTRACT_K), dtype=torch.int32, device=dev)
                 for v0 in range(0, v, per):
                     p = min(per, v - v0)
-                    pts = vertices[v0:v0 + p]
-                    _call("ts_knn", lib.ts_knn, n, _ptr(pk.means), p, _ptr(pts), EXTRACT_K, _ptr(dist), _ptr(idx),
-                          _ptr(ws), None, s)
-                    _call("ts_extract_normals", lib.ts_extract_normals, n, p, _ptr(pts), _ptr(idx), _ptr(pk.records),
-                          _ptr(normals[v0:v0 + p]), s)
+                    normals_at(lib, pk, vertices[v0:v0 + p], p, normals[v0:v0 + p], dist, idx, ws, s)
     mesh = TriangleMesh(vertices, faces, normals)
     if not return_debug:
         return mesh
     shapes = {"corners": ((0, BRICK_CORNERS, 3), torch.float32), "knn": ((0, BRICK_CORNERS, EXTRACT_K), torch.int32),
               "density": ((0, BRICK_CORNERS), torch.float32), "knn_fallback": ((0,), torch.int32)}
-    debug = {k: cat(v, *shapes[k]) for k, v in dbg.items()}
-    debug.update(active_bricks=active, keys=keys, cell=cat(tri_cell, (0,), torch.int64), chunks=chunks,
+    debug = {k: cat(v, *shapes[k], dev) for k, v in dbg.items()}
+    debug.update(active_bricks=active, keys=keys, cell=cat(tri_cell, (0,), torch.int64, dev), chunks=chunks,
                  total_bricks=total_bricks, grid={"lo": tuple(glo), "h": h, "cells": tuple(cells)})
     return mesh, debug
