@@ -849,6 +849,21 @@ int ts_mesh_emit(int32_t bricks, const int64_t* brick_ids, const float* grid_hos
                  float level, const float* density, const int64_t* offsets, int64_t* keys, float* positions,
                  int64_t* cells, void* stream);
 
+/* The colour of points of the same density field from the Gaussians' spherical harmonics.  An
+ * additive entry: the ABI version is unchanged.  points float32 [m,3] with their own neighbours knn int32
+ * [m, TS_EXTRACT_K] (ts_knn's: ascending in distance), normals float32 [m,3] (unit, outward) or NULL, records as
+ * ts_extract_pack wrote them, colors_dc float32 [n,3], colors_rest float32 [n, k_rest, 3] (may be NULL at degree 0) ->
+ * colors float32 [m,3] <- min(sum_j w_j c_j / sum_j w_j, 1) over the neighbours, w_j the neighbour's term of d above,
+ * c_j = max(sum_k Y_k(-normal) coeffs[j, k, :] + 0.5, 0) over the bands <= degree.  Only band 0 where the normal is
+ * zero, not finite or absent; a neighbour outside [0, n) has weight 0 and colour 0; where sum_j w_j is not positive
+ * and finite, the colour c_j of the first listed neighbour.  One 16-lane row per point, a fixed reduction order:
+ * a point's colour does not depend on m or on its place in the call.  m == 0: returns 0, launches nothing.
+ * TS_E_BADARG: n < 1, m < 0, k_rest < 0, a NULL pointer with m > 0; TS_E_DEGREE: degree outside 0..3 or
+ * (degree + 1)^2 > k_rest + 1. */
+int ts_field_colors(int32_t n, int32_t m, const float* points, const float* normals, const int32_t* knn,
+                    const float* records, const float* colors_dc, const float* colors_rest, int32_t k_rest,
+                    int32_t degree, float* colors, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

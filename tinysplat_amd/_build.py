@@ -35,6 +35,9 @@ SOURCES = [
     # mesh.hip: corner positions and interpolated vertices must come out bit-identical in every cell sharing an edge,
     # and equal to the host build of mesh_cells.h; densities are compared with the same float64 restatement
     ("mesh.hip", ["-ffp-contract=off"]),
+    # field_color.hip: the neighbours' weights are density_field.h's term, whose bits extract.hip and mesh.hip pin, and the
+    # colours are compared with a float64 restatement whose float32 run rounds every product and sum on its own
+    ("field_color.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -1,5 +1,6 @@
-"""What ``extract.py`` and ``mesh.py`` (section 6g) share on the Python side of the packed-record
-density (csrc/density_field.h): the packed model, its neighbour search and normals, and a chunk's workspace."""
+"""What ``extract.py`` and ``mesh.py`` (sections 6g and 6h) share on the Python side of the
+packed-record density (csrc/density_field.h): the packed model, its neighbour search, normals and colours, and a chunk's
+workspace."""
 from dataclasses import dataclass
 
 import torch
@@ -89,6 +90,17 @@ def normals_at(lib, pk: PackedModel, points, p: int, out, dist, idx, ws, stream)
     knn(lib, pk, points, p, EXTRACT_K, dist, idx, ws, None, stream)
     _call("ts_extract_normals", lib.ts_extract_normals, pk.means.shape[0], p, _ptr(points), _ptr(idx),
           _ptr(pk.records), _ptr(out), stream)
+
+
+def colors_at(lib, pk: PackedModel, colors_dc, colors_rest, points, normals, p: int, degree: int, out, dist, idx, ws,
+              stream, search: bool = True):
+    """``ts_field_colors`` at the first ``p`` rows of ``points``: the SH colour seen along ``-normals`` (None: band 0
+    only), weighed over each point's own 16 neighbours.  ``search=False``: ``idx`` already holds these points'
+    neighbours (``normals_at`` on the same rows just ran) and is not searched for again."""
+    if search:
+        knn(lib, pk, points, p, EXTRACT_K, dist, idx, ws, None, stream)
+    _call("ts_field_colors", lib.ts_field_colors, pk.means.shape[0], p, _ptr(points), _ptr(normals), _ptr(idx),
+          _ptr(pk.records), _ptr(colors_dc), _ptr(colors_rest), colors_rest.shape[1], degree, _ptr(out), stream)
 
 
 def cat(parts, shape, dtype, dev) -> Tensor:

@@ -203,6 +203,7 @@ SIGNATURES = {
     "ts_mesh_density": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ts_mesh_count": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P, _P]),
     "ts_mesh_emit": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P]),
+    "ts_field_colors": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P]),
 }
 
 _lib = None

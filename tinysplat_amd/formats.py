@@ -142,23 +142,52 @@ def load_ply(path, device) -> SplatModel:
 
 
 _POINT_FIELDS = ("x", "y", "z", "nx", "ny", "nz")
+_COLOR_FIELDS = ("red", "green", "blue")
+
+
+def _colors_of(obj, rows: int):
+    """``obj.colors`` as float32 [rows,3] on the CPU, or None where the attribute is absent or None."""
+    col = getattr(obj, "colors", None)
+    if col is None:
+        return None
+    col = torch.as_tensor(col).detach().to("cpu", torch.float32)
+    if col.shape != (rows, 3):
+        raise ValueError(f"colors [{rows},3] expected")
+    return col
+
+
+def _color_bytes(col) -> np.ndarray:
+    """``round(clamp(c, 0, 1) * 255)`` as uint8 [P,3] (NaN as 0)."""
+    return torch.round(torch.nan_to_num(col, nan=0.0).clamp(0.0, 1.0) * 255.0).to(torch.uint8).numpy()
+
+
+def _vertex_rows(xyz, nrm, col) -> bytes:
+    """The vertex element's payload: six floats per vertex and, with colours, three ``uchar`` after them."""
+    floats = np.ascontiguousarray(np.concatenate((xyz, nrm), 1).astype("<f4"))
+    if col is None:
+        return floats.tobytes()
+    rows = np.empty((floats.shape[0],), dtype=[("f", "<f4", (6,)), ("c", "u1", (3,))])
+    rows["f"], rows["c"] = floats, _color_bytes(col)
+    return rows.tobytes()
 
 
 def export_points_ply(points, path) -> None:
     """An oriented point cloud as a binary little-endian PLY, ``x y z nx ny nz`` (float) per vertex: the input of
     Poisson reconstruction tools.  ``points``: an ``extract.SurfacePoints`` (or anything with ``points`` [P,3] and
-    ``normals`` [P,3] or None: zero normals are written then), on any device."""
+    ``normals`` [P,3] or None: zero normals are written then), on any device.  Where it has ``colors`` [P,3] (e.g.
+    ``mesh.vertex_colors``'), ``uchar red green blue`` follow as ``round(clamp(c, 0, 1) * 255)``."""
     xyz = torch.as_tensor(points.points).detach().to("cpu", torch.float32)
     nrm = getattr(points, "normals", None)
     nrm = torch.zeros_like(xyz) if nrm is None else torch.as_tensor(nrm).detach().to("cpu", torch.float32)
     if xyz.dim() != 2 or xyz.shape[1] != 3 or nrm.shape != xyz.shape:
         raise ValueError("points [P,3] and normals [P,3] expected")
+    col = _colors_of(points, xyz.shape[0])
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {xyz.shape[0]}",
-              *(f"property float {name}" for name in _POINT_FIELDS), "end_header"]
-    rows = np.ascontiguousarray(torch.cat((xyz, nrm), 1).numpy().astype("<f4"))
+              *(f"property float {name}" for name in _POINT_FIELDS),
+              *(f"property uchar {name}" for name in (_COLOR_FIELDS if col is not None else ())), "end_header"]
     with open(path, "wb") as f:
         f.write(("\n".join(header) + "\n").encode("ascii"))
-        f.write(rows.tobytes())
+        f.write(_vertex_rows(xyz.numpy(), nrm.numpy(), col))
 
 
 def read_points_ply(path):
@@ -185,8 +214,8 @@ def read_points_ply(path):
 
 
 def _mesh_arrays(mesh):
-    """``(vertices float32 [V,3], normals float32 [V,3] (zeros without), faces int32 [F,3])`` of a
-    ``mesh.TriangleMesh`` (or anything with those attributes) as little-endian arrays on the CPU."""
+    """``(vertices float32 [V,3], normals float32 [V,3] (zeros without), faces int32 [F,3], colors float32 tensor [V,3]
+    or None)`` of a ``mesh.TriangleMesh`` (or anything with those attributes) as little-endian arrays on the CPU."""
     xyz = torch.as_tensor(mesh.vertices).detach().to("cpu", torch.float32)
     nrm = getattr(mesh, "normals", None)
     nrm = torch.zeros_like(xyz) if nrm is None else torch.as_tensor(nrm).detach().to("cpu", torch.float32)
@@ -195,29 +224,37 @@ def _mesh_arrays(mesh):
         raise ValueError("vertices [V,3], normals [V,3] and faces [F,3] expected")
     if faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= xyz.shape[0]):
         raise ValueError("a face refers to a vertex that does not exist")
-    return xyz.numpy().astype("<f4"), nrm.numpy().astype("<f4"), faces.numpy().astype("<i4")
+    return xyz.numpy().astype("<f4"), nrm.numpy().astype("<f4"), faces.numpy().astype("<i4"), _colors_of(mesh, xyz.shape[0])
 
 
 def export_mesh_ply(mesh, path) -> None:
     """A triangle mesh as a binary little-endian PLY: ``x y z nx ny nz`` (float) per vertex, then per face a
-    ``uchar`` count (3) and ``int`` vertex indices.  ``mesh``: a ``mesh.TriangleMesh``, on any device."""
-    xyz, nrm, faces = _mesh_arrays(mesh)
+    ``uchar`` count (3) and ``int`` vertex indices.  ``mesh``: a ``mesh.TriangleMesh``, on any device.  With
+    ``mesh.colors``, ``uchar red green blue`` follow ``nz`` as ``round(clamp(c, 0, 1) * 255)``."""
+    xyz, nrm, faces, col = _mesh_arrays(mesh)
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {xyz.shape[0]}",
-              *(f"property float {name}" for name in _POINT_FIELDS), f"element face {faces.shape[0]}",
+              *(f"property float {name}" for name in _POINT_FIELDS),
+              *(f"property uchar {name}" for name in (_COLOR_FIELDS if col is not None else ())),
+              f"element face {faces.shape[0]}",
               "property list uchar int vertex_indices", "end_header"]
     rows = np.empty((faces.shape[0],), dtype=[("n", "u1"), ("v", "<i4", (3,))])
     rows["n"], rows["v"] = 3, faces
     with open(path, "wb") as f:
         f.write(("\n".join(header) + "\n").encode("ascii"))
-        f.write(np.ascontiguousarray(np.concatenate((xyz, nrm), 1)).tobytes())
+        f.write(_vertex_rows(xyz, nrm, col))
         f.write(rows.tobytes())
 
 
 def export_mesh_obj(mesh, path) -> None:
     """A triangle mesh as a Wavefront OBJ: ``v x y z``, ``vn x y z`` and ``f a//a b//b c//c`` with 1-based indices.
-    Floats are written with nine significant digits, which a float32 survives.  ``mesh`` on any device."""
-    xyz, nrm, faces = _mesh_arrays(mesh)
+    Floats are written with nine significant digits, which a float32 survives.  ``mesh`` on any device.  With
+    ``mesh.colors`` the vertex lines are ``v x y z r g b``, the colours as floats in [0, 1]."""
+    xyz, nrm, faces, col = _mesh_arrays(mesh)
     with open(path, "w", encoding="ascii") as f:
-        f.writelines("v %.9g %.9g %.9g\n" % tuple(r) for r in xyz.tolist())
+        if col is None:
+            f.writelines("v %.9g %.9g %.9g\n" % tuple(r) for r in xyz.tolist())
+        else:
+            rgb = torch.nan_to_num(col, nan=0.0).clamp(0.0, 1.0).tolist()
+            f.writelines("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % (*r, *c) for r, c in zip(xyz.tolist(), rgb))
         f.writelines("vn %.9g %.9g %.9g\n" % tuple(r) for r in nrm.tolist())
         f.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in (faces + 1).tolist())

@@ -13,6 +13,9 @@ every Gaussian, so its 16-neighbour density is at most ``16 exp(-extent_sigmas^2
 level, every cell the surface crosses has a corner inside some box, and the bricks holding such cells give the mesh of
 the dense grid bit for bit (``sparse=False`` evaluates every brick, to show it).  This is a condition, not a tuning knob.
 
+``MeshConfig(colors=True)`` also colours the vertices from the Gaussians' spherical harmonics, seen head-on along the
+normal (section 6h, csrc/field_color.hip); ``vertex_colors`` does the same for any points.
+
 The hot path is csrc/mesh.hip on top of ``ts_knn``, ``ts_extract_pack`` and ``ts_extract_normals``; there is no CPU
 fallback: tensors must be on the GPU.
 """
@@ -27,12 +30,14 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._field import EXTRACT_K, PackedModel, Workspace, align256, cat, knn, largest, normals_at, pack_model
+from ._field import (EXTRACT_K, PackedModel, Workspace, align256, cat, colors_at, knn, largest, normals_at,
+                     pack_model)
 from .ops import _call, _f32c, _need_hip, _ptr, _stream
 
 BRICK = 8                       # TS_MESH_BRICK
 BRICK_CORNERS = 729             # TS_MESH_BRICK_CORNERS
 _MAX_BRICKS = (2 ** 31 - 1) // (BRICK_CORNERS * EXTRACT_K)
+MAX_COLOR_DEGREE = 3            # ts_field_colors evaluates the bands 0..3
 
 
 def level_floor(extent_sigmas: float) -> float:
@@ -46,7 +51,9 @@ class MeshConfig:
     reference's literal); ``bounds``: ``(lo, hi)``, or None for the union of the Gaussians' boxes; ``extent_sigmas``:
     the half-size of a Gaussian's box in standard deviations per world axis; ``sparse=False`` evaluates every brick (a
     test and timing yardstick); ``max_workspace_bytes`` bounds the brick flags and every transient buffer of a chunk
-    of bricks (the emitted triangles, the packed records and the returned tensors come on top)."""
+    of bricks (the emitted triangles, the packed records and the returned tensors come on top); ``colors``: also the
+    vertices' colours (section 6h), with the bands up to ``color_sh_degree`` (None: the model's ``active_sh_degree``;
+    it may not exceed what the model stores)."""
     surface_level: float = 0.3
     resolution: int = 256
     bounds: Optional[Tuple[Sequence[float], Sequence[float]]] = None
@@ -54,6 +61,8 @@ class MeshConfig:
     sparse: bool = True
     normals: bool = True
     max_workspace_bytes: int = 256 << 20
+    colors: bool = False
+    color_sh_degree: Optional[int] = None
 
     def __post_init__(self):
         if not (isinstance(self.extent_sigmas, (int, float)) and math.isfinite(self.extent_sigmas)
@@ -71,16 +80,19 @@ class MeshConfig:
             raise ValueError("max_workspace_bytes must be positive")
         if self.bounds is not None:
             _check_bounds(*self.bounds)
+        if self.color_sh_degree is not None and not 0 <= int(self.color_sh_degree) <= MAX_COLOR_DEGREE:
+            raise ValueError(f"color_sh_degree must be in 0..{MAX_COLOR_DEGREE}")
 
 
 @dataclass
 class TriangleMesh:
     """``vertices`` float32 [V,3] in ascending order of their edge keys; ``faces`` int32 [F,3], wound so that the
     geometric normal points towards falling density; ``normals`` float32 [V,3], ``-grad d / |grad d|`` at the vertices
-    (zero where undefined), or None."""
+    (zero where undefined), or None; ``colors`` float32 [V,3] in [0, 1] (section 6h), or None."""
     vertices: Tensor
     faces: Tensor
     normals: Optional[Tensor]
+    colors: Optional[Tensor] = None
 
 
 def _check_bounds(lo, hi):
@@ -145,6 +157,85 @@ def gaussian_boxes(model, extent_sigmas: float = 3.0) -> Tensor:
     return boxes
 
 
+def _color_coeffs(model, n: int, sh_degree: Optional[int]):
+    """-> ``(colors_dc [N,3], colors_rest [N,K,3], degree)`` of ``model`` for ``ts_field_colors``: ``sh_degree``, or the
+    model's ``active_sh_degree``; refused when the model does not store its bands."""
+    dc, rest = _f32c(model.colors_dc.detach()), _f32c(model.colors_rest.detach())
+    _need_hip(dc, rest)
+    if dc.shape != (n, 3) or rest.dim() != 3 or rest.shape[0] != n or rest.shape[2] != 3:
+        raise ValueError(f"colors_dc [{n},3] and colors_rest [{n},K,3] expected")
+    degree = int(model.active_sh_degree if sh_degree is None else sh_degree)
+    if not 0 <= degree <= MAX_COLOR_DEGREE:
+        raise ValueError(f"the colours take an SH degree in 0..{MAX_COLOR_DEGREE}, got {degree}")
+    if (degree + 1) ** 2 > rest.shape[1] + 1:
+        raise ValueError(f"SH degree {degree} needs {(degree + 1) ** 2} coefficients, the model stores {rest.shape[1] + 1}")
+    return dc, rest, degree
+
+
+_OWN = "own"
+
+
+def _at_points(lib, pk: PackedModel, points: Tensor, cap: int, s, want_normals: bool, coeffs, along=_OWN):
+    """The normals and / or the colours of ``points`` [P,3] in chunks whose buffers fit ``cap`` bytes, one neighbour
+    search per chunk -> ``(normals or None, colors or None)``.  ``coeffs``: ``_color_coeffs``'s, or None for no colours.
+    The colours look along the normals evaluated here (``along=_OWN``), or along the caller's [P,3] (None: band 0)."""
+    dev = points.device
+    n, v = pk.means.shape[0], int(points.shape[0])
+    f32 = dict(dtype=torch.float32, device=dev)
+    evaluate = want_normals or (coeffs is not None and along is _OWN)
+    normals = torch.empty((v, 3), **f32) if want_normals else None
+    colors = torch.empty((v, 3), **f32) if coeffs is not None else None
+    if not v or not (evaluate or coeffs is not None):
+        return normals, colors
+    scratch = evaluate and not want_normals            # normals the colours need and the caller does not get
+
+    def fits(p):
+        return int(lib.ts_knn_ws_bytes(n, p, EXTRACT_K)) + 2 * align256(p * EXTRACT_K * 4) \
+            + (align256(p * 12) if scratch else 0) <= cap
+    per = largest(fits, min(v, (2 ** 31 - 2) // EXTRACT_K))
+    if per < 1:
+        raise ValueError(f"max_workspace_bytes = {cap} is too small for the normals of one vertex")
+    ws = torch.empty((int(lib.ts_knn_ws_bytes(n, per, EXTRACT_K)),), dtype=torch.uint8, device=dev)
+    dist = torch.empty((per, EXTRACT_K), **f32)
+    idx = torch.empty((per, EXTRACT_K), dtype=torch.int32, device=dev)
+    own = torch.empty((per, 3), **f32) if scratch else None
+    for v0 in range(0, v, per):
+        p = min(per, v - v0)
+        pts = points[v0:v0 + p]
+        nrm = None if along is _OWN or along is None else along[v0:v0 + p]
+        if evaluate:
+            nrm = normals[v0:v0 + p] if want_normals else own
+            normals_at(lib, pk, pts, p, nrm, dist, idx, ws, s)
+        if coeffs is not None:
+            colors_at(lib, pk, coeffs[0], coeffs[1], pts, nrm, p, coeffs[2], colors[v0:v0 + p], dist, idx, ws, s,
+                      search=not evaluate)
+    return normals, colors
+
+
+@torch.no_grad()
+def vertex_colors(model, points: Tensor, normals: Optional[Tensor] = None, sh_degree: Optional[int] = None,
+                  max_workspace_bytes: int = 256 << 20, packed: Optional[PackedModel] = None) -> Tensor:
+    """The colours (float32 [P,3] in [0, 1], section 6h) of any ``points`` float32 [P,3] on the model's device, e.g. an
+    ``extract.SurfacePoints``' points: each point's 16 nearest Gaussians, weighed as the density weighs them, seen along
+    ``-normals`` (unit, outward; None: band 0 only, as where a normal is zero).  ``sh_degree``: None for the model's
+    ``active_sh_degree``.  The same bits for any ``max_workspace_bytes``; ``packed``: a ``pack_model`` result to reuse."""
+    cap = int(max_workspace_bytes)
+    if cap < 1:
+        raise ValueError("max_workspace_bytes must be positive")
+    pk = packed if packed is not None else pack_model(model)
+    points = _f32c(points.detach())
+    dev = _need_hip(pk.means, pk.records, points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points [P,3] expected")
+    if normals is not None:
+        normals = _f32c(normals.detach())
+        if _need_hip(normals) != dev or normals.shape != points.shape:
+            raise ValueError("normals must match points in shape and device")
+    coeffs = _color_coeffs(model, pk.means.shape[0], sh_degree)
+    with torch.cuda.device(dev):
+        return _at_points(_lib.load(), pk, points, cap, _stream(dev), False, coeffs, along=normals)[1]
+
+
 @torch.no_grad()
 def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool = False,
                  packed: Optional[PackedModel] = None):
@@ -155,7 +246,8 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
     ``config.max_workspace_bytes``) the 9^3 corner positions, their 16 neighbours (``ts_knn``), the densities, the
     triangle counts and the triangles as edge keys and positions; then the vertices are welded by key
     (``torch.unique``: ascending key order, the first occurrence's position - all occurrences are bit-identical) and the
-    normals evaluated at them.  The mesh is a fixed function of (model, config): the same for any chunk size and for
+    normals (and, with ``config.colors``, the colours: from the same neighbour lists) evaluated at them in chunks of
+    vertices.  The mesh is a fixed function of (model, config): the same for any chunk size and for
     ``sparse`` on or off.  A surface that leaves the bounds is cut there (an open boundary).
 
     ``return_debug``: also a dict of ``active_bricks`` int64 [A], ``cell`` int64 [T] and ``keys`` int64 [T,3] per
@@ -168,6 +260,7 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
     dev = _need_hip(pk.means, pk.records)
     n = pk.means.shape[0]
     lib = _lib.load()
+    coeffs = _color_coeffs(model, n, cfg.color_sh_degree) if cfg.colors else None     # refused before any work
     cap = int(cfg.max_workspace_bytes)
     level = float(cfg.surface_level)
     boxes = gaussian_boxes(model, cfg.extent_sigmas)
@@ -265,23 +358,8 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
             vertices = torch.empty((0, 3), **f32)
             faces = torch.empty((0, 3), dtype=torch.int32, device=dev)
         del pos
-        normals = None
-        if cfg.normals:
-            v = int(vertices.shape[0])
-            normals = torch.empty((v, 3), **f32)
-            if v:
-                def fits(p):
-                    return int(lib.ts_knn_ws_bytes(n, p, EXTRACT_K)) + 2 * align256(p * EXTRACT_K * 4) <= cap
-                per = largest(fits, min(v, (2 ** 31 - 2) // EXTRACT_K))
-                if per < 1:
-                    raise ValueError(f"max_workspace_bytes = {cap} is too small for the normals of one vertex")
-                ws = torch.empty((int(lib.ts_knn_ws_bytes(n, per, EXTRACT_K)),), dtype=torch.uint8, device=dev)
-                dist = torch.empty((per, EXTRACT_K), **f32)
-                idx = torch.empty((per, EXTRACT_K), dtype=torch.int32, device=dev)
-                for v0 in range(0, v, per):
-                    p = min(per, v - v0)
-                    normals_at(lib, pk, vertices[v0:v0 + p], p, normals[v0:v0 + p], dist, idx, ws, s)
-    mesh = TriangleMesh(vertices, faces, normals)
+        normals, colors = _at_points(lib, pk, vertices, cap, s, cfg.normals, coeffs)
+    mesh = TriangleMesh(vertices, faces, normals, colors)
     if not return_debug:
         return mesh
     shapes = {"corners": ((0, BRICK_CORNERS, 3), torch.float32), "knn": ((0, BRICK_CORNERS, EXTRACT_K), torch.int32),

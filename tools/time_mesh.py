@@ -8,9 +8,13 @@ per measurement (ms).
     torch (nonzero, scans, ``unique``) and host time;
   * ``fallback share``: the corner queries that took ``ts_knn``'s brute-force pass, from a separate run that asks every
     chunk's search for its statistics;
-  * ``--dense``: the same call with ``sparse=False`` (every brick), the baseline of the sparse grid.
+  * ``--dense``: the same call with ``sparse=False`` (every brick), the baseline of the sparse grid;
+  * ``--colors``: the call with ``colors=True`` at ``--color-degree`` (seeded coefficients of 16 bands): the colour
+    stage (``ts_field_colors``) is listed beside the normals stage of the same run, with the bytes it must move
+    (``V x 16 x (40 + 12 (degree + 1)^2) + 12 V``, an upper bound before cache reuse) as a share of the HBM peak.
 
-    python tools/time_mesh.py [--scene sheet|volume] [--n 1000000] [--resolution 256] [--dense] [--reps 3] [--out f.jsonl]
+    python tools/time_mesh.py [--scene sheet|volume] [--n 1000000] [--resolution 256] [--dense] [--colors]
+                              [--color-degree 3] [--reps 3] [--out f.jsonl]
 """
 import argparse
 import json
@@ -31,6 +35,7 @@ from tinysplat_amd.synthetic import make_scene  # noqa: E402
 from time_extract import sheet_scene, timed  # noqa: E402
 
 DEV = "cuda:0"
+HBM_PEAK = 8.0e12               # bytes / s, the MI355X's HBM3E
 
 
 @torch.no_grad()
@@ -66,6 +71,8 @@ def main():
     ap.add_argument("--resolution", type=int, default=256)
     ap.add_argument("--scene", choices=("volume", "sheet"), default="sheet")
     ap.add_argument("--dense", action="store_true")
+    ap.add_argument("--colors", action="store_true")
+    ap.add_argument("--color-degree", type=int, default=3)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -83,9 +90,16 @@ def main():
     else:
         model = sheet_scene(args.n, w, h)
     model = model.to(DEV)
+    if args.colors:
+        g = torch.Generator(device=DEV).manual_seed(1)
+        model.colors_rest = 0.3 * torch.randn((args.n, 15, 3), generator=g, device=DEV)
+        model.active_sh_degree = 3
     pk = pack_model(model)
-    cfg = MeshConfig(resolution=args.resolution, sparse=not args.dense)
+    cfg = MeshConfig(resolution=args.resolution, sparse=not args.dense, colors=args.colors,
+                     color_sh_degree=args.color_degree if args.colors else None)
     shape = dict(scene=args.scene, n=args.n, resolution=args.resolution, sparse=cfg.sparse)
+    if args.colors:
+        shape["color_degree"] = args.color_degree
 
     def run():
         return extract_mesh(model, cfg, packed=pk)
@@ -120,6 +134,15 @@ def main():
         inside += launches * mean_ms
         emit("part " + name, launches * mean_ms, launches=launches, **shape)
     emit("part torch and host (the rest)", total - inside, **shape)
+    if args.colors:
+        v = int(mesh.vertices.shape[0])
+        launches, mean_ms = parts["ts_field_colors"]
+        ms = launches * mean_ms
+        nbytes = v * EXTRACT_K * (40 + 12 * (args.color_degree + 1) ** 2) + 12 * v
+        n_launches, n_mean = parts["ts_extract_normals"]
+        emit("colour stage", ms, vertices=v, bytes_upper_bound=nbytes, gbytes_per_s=round(nbytes / ms / 1e6, 1),
+             share_of_hbm_peak=round(nbytes / (ms * 1e-3) / HBM_PEAK, 4), normals_stage_ms=round(n_launches * n_mean, 4),
+             **shape)
     grid = {"lo": glo, "h": gh, "cells": cells}
     emit("fallback share", 0.0, share=round(fallback_share(model, pk, cfg, active, grid), 5),
          corner_queries=int(active.shape[0]) * BRICK_CORNERS, **shape)
