@@ -864,6 +864,62 @@ int ts_field_colors(int32_t n, int32_t m, const float* points, const float* norm
                     const float* records, const float* colors_dc, const float* colors_rest, int32_t k_rest,
                     int32_t degree, float* colors, void* stream);
 
+/* Triangle-budget simplification of a mesh by vertex clustering with quadric-optimal representatives (DESIGN.md section
+ * 6i, csrc/simplify_math.h).  Additive entries: the ABI version is unchanged.  None allocates or synchronises; all are
+ * deterministic (plain stores, no atomics).  vertices float32 [v,3], faces int32 [f,3] with every index in [0, v) (the
+ * caller's duty: the kernels gather through them unchecked).  The grid: grid_host = host float[4] {lo x y z, cell edge
+ * c > 0}, cells_host = host int32[3], the cells per axis (>= 1; nx ny nz must stay below 4.6e18).  A coordinate's cell
+ * is min(floor((p - lo) / c), n - 1) (float32, difference and quotient rounded separately; 0 below lo), a vertex's key
+ * the int64 (iz ny + iy) nx + ix, a cell's centre lo + (i + 0.5) c in double.
+ * ts_simplify_count: block_counts int32 [ceil(f / 256)] <- per workgroup of 256 faces, the faces whose three corner keys
+ * are pairwise distinct.  f == 0: returns 0, launches nothing.  TS_E_BADARG: v < 0, f < 0, a bad grid; with f > 0 also
+ * v < 1 or a NULL pointer.
+ * ts_simplify_keys: keys int64 [v] <- every vertex's key.  v == 0: returns 0, launches nothing.  TS_E_BADARG: v < 0, a
+ * bad grid, a NULL pointer with v > 0.
+ * ts_simplify_accumulate: sums over the entries of one cluster, in double.  what = TS_SIMPLIFY_FACE_CORNERS: the
+ * entries are the 3 f face corners (entry = face * 3 + corner) and sums is double [clusters, TS_SIMPLIFY_QUADRIC]: per
+ * corner, with g the centre of the corner's cell, n = (b - a) x (c - a) and d = -n . (a - g) of its face (a, b, c), the
+ * ten numbers n n^T (xx xy xz yy yz zz), n d, d^2.  what = TS_SIMPLIFY_VERTICES: the entries are the v vertices and sums
+ * is double [clusters, TS_SIMPLIFY_VSUM]: p - g and 1.  clusters_sorted int32 [entries] ascending and order int64
+ * [entries] (the entry at each sorted place) are a stable sort of the entries' clusters.  Chunks of TS_SIMPLIFY_CHUNK
+ * consecutive sorted entries are summed serially from zero; a cluster's run that crosses chunk ends is the sum, in chunk
+ * order, of its parts.  One call covers the chunks [chunk0, chunk0 + chunks) with a workspace of
+ * ts_simplify_ws_bytes(chunks) bytes and stores every cluster whose run starts in them; the sums of a cluster do not
+ * depend on how the chunks are spread over calls.  A cluster without entries keeps what sums held (zero it first); an
+ * entry whose cluster lies outside [0, clusters) is skipped.  entries == 0 or chunks == 0: returns 0, launches nothing.
+ * TS_E_BADARG: a negative size, a bad grid, an unknown `what`, entries != 3 f (or v), a chunk range outside
+ * [0, ceil(entries / TS_SIMPLIFY_CHUNK)]; with work to do also v < 1, clusters < 1 or a NULL pointer (faces may be NULL
+ * for the vertices).
+ * ts_simplify_ws_bytes: two partial rows of TS_SIMPLIFY_QUADRIC doubles and an int32 flag per chunk, 256-byte aligned.
+ * TS_E_BADARG: chunks < 1 or > 2^40.
+ * ts_simplify_solve: representatives float32 [clusters,3] <- float32(g + x) per cluster, cluster_keys int64 [clusters]
+ * its cell's key, x = ts_simplify_representative of its sums (csrc/simplify_math.h: the mean m of p - g moved along the
+ * eigen-directions of A with lambda > singular_threshold * lambda_max, cyclic Jacobi in double; m where A has no
+ * positive finite eigenvalue or the result is not finite or leaves the cell).  clusters == 0: returns 0.
+ * TS_E_BADARG: clusters < 0, a bad grid, singular_threshold outside (0, 1), a NULL pointer with clusters > 0.
+ * ts_simplify_faces: out_faces int32 [f,3] <- vertex_cluster int32 [v] at the face's corners, rotated so that the
+ * smallest comes first (the orientation stays); keep uint8 [f] <- 1 where the three differ.  f == 0: returns 0.
+ * TS_E_BADARG: v < 0, f < 0; with f > 0 also v < 1 or a NULL pointer. */
+#define TS_SIMPLIFY_CHUNK 128
+#define TS_SIMPLIFY_QUADRIC 10
+#define TS_SIMPLIFY_VSUM 4
+#define TS_SIMPLIFY_FACE_CORNERS 0
+#define TS_SIMPLIFY_VERTICES 1
+int ts_simplify_count(int32_t v, int32_t f, const float* vertices, const int32_t* faces, const float* grid_host,
+                      const int32_t* cells_host, int32_t* block_counts, void* stream);
+int ts_simplify_keys(int32_t v, const float* vertices, const float* grid_host, const int32_t* cells_host, int64_t* keys,
+                     void* stream);
+int64_t ts_simplify_ws_bytes(int64_t chunks);
+int ts_simplify_accumulate(int32_t v, int32_t f, int32_t clusters, const float* vertices, const int32_t* faces,
+                           const float* grid_host, const int32_t* cells_host, int32_t what, int64_t entries,
+                           const int32_t* clusters_sorted, const int64_t* order, int64_t chunk0, int64_t chunks,
+                           double* sums, void* ws, void* stream);
+int ts_simplify_solve(int32_t clusters, const int64_t* cluster_keys, const float* grid_host, const int32_t* cells_host,
+                      const double* quadrics, const double* vertex_sums, double singular_threshold,
+                      float* representatives, void* stream);
+int ts_simplify_faces(int32_t v, int32_t f, const int32_t* faces, const int32_t* vertex_cluster, int32_t* out_faces,
+                      uint8_t* keep, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

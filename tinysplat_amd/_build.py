@@ -38,6 +38,9 @@ SOURCES = [
     # field_color.hip: the neighbours' weights are density_field.h's term, whose bits extract.hip and mesh.hip pin, and the
     # colours are compared with a float64 restatement whose float32 run rounds every product and sum on its own
     ("field_color.hip", ["-ffp-contract=off"]),
+    # simplify.hip: a vertex's cell comes from a float32 difference and quotient that the host build of simplify_math.h
+    # and the oracle round separately, and the double sums and solves are compared with a float64 restatement
+    ("simplify.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_float, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_double, c_float, c_int32, c_int64, c_void_p
 from pathlib import Path
 
 # TS_LIB_PATH: another build of the library (tests/test_gpu_variants.py loads builds with the other settings of the
@@ -204,6 +204,13 @@ SIGNATURES = {
     "ts_mesh_count": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P, _P]),
     "ts_mesh_emit": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P]),
     "ts_field_colors": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P]),
+    "ts_simplify_count": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
+    "ts_simplify_keys": (c_int32, [c_int32, _P, _P, _P, _P, _P]),
+    "ts_simplify_ws_bytes": (c_int64, [c_int64]),
+    "ts_simplify_accumulate": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int64, _P, _P, c_int64,
+                                         c_int64, _P, _P, _P]),
+    "ts_simplify_solve": (c_int32, [c_int32, _P, _P, _P, _P, _P, c_double, _P, _P]),
+    "ts_simplify_faces": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

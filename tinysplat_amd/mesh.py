@@ -53,7 +53,8 @@ class MeshConfig:
     test and timing yardstick); ``max_workspace_bytes`` bounds the brick flags and every transient buffer of a chunk
     of bricks (the emitted triangles, the packed records and the returned tensors come on top); ``colors``: also the
     vertices' colours (section 6h), with the bands up to ``color_sh_degree`` (None: the model's ``active_sh_degree``;
-    it may not exceed what the model stores)."""
+    it may not exceed what the model stores); ``target_faces``: simplify the mesh to at most this many faces before the
+    normals and colours are evaluated (section 6i, ``simplify.simplify_mesh``; None: the mesh as the grid gives it)."""
     surface_level: float = 0.3
     resolution: int = 256
     bounds: Optional[Tuple[Sequence[float], Sequence[float]]] = None
@@ -63,6 +64,7 @@ class MeshConfig:
     max_workspace_bytes: int = 256 << 20
     colors: bool = False
     color_sh_degree: Optional[int] = None
+    target_faces: Optional[int] = None
 
     def __post_init__(self):
         if not (isinstance(self.extent_sigmas, (int, float)) and math.isfinite(self.extent_sigmas)
@@ -82,6 +84,8 @@ class MeshConfig:
             _check_bounds(*self.bounds)
         if self.color_sh_degree is not None and not 0 <= int(self.color_sh_degree) <= MAX_COLOR_DEGREE:
             raise ValueError(f"color_sh_degree must be in 0..{MAX_COLOR_DEGREE}")
+        if self.target_faces is not None and int(self.target_faces) < 1:
+            raise ValueError("target_faces must be at least 1")
 
 
 @dataclass
@@ -248,7 +252,10 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
     (``torch.unique``: ascending key order, the first occurrence's position - all occurrences are bit-identical) and the
     normals (and, with ``config.colors``, the colours: from the same neighbour lists) evaluated at them in chunks of
     vertices.  The mesh is a fixed function of (model, config): the same for any chunk size and for
-    ``sparse`` on or off.  A surface that leaves the bounds is cut there (an open boundary).
+    ``sparse`` on or off.  A surface that leaves the bounds is cut there (an open boundary).  With
+    ``config.target_faces`` the welded mesh is simplified to that budget (``simplify.simplify_mesh``, section 6i) before
+    the normals and colours are evaluated, at the simplified vertices; ``keys`` and ``cell`` below describe the mesh
+    before that, ``simplify`` (``simplify_mesh``'s debug dict) the step itself.
 
     ``return_debug``: also a dict of ``active_bricks`` int64 [A], ``cell`` int64 [T] and ``keys`` int64 [T,3] per
     triangle before welding, ``corners`` float32 [A,729,3], ``knn`` int32 [A,729,16] and ``density`` float32 [A,729] of
@@ -358,6 +365,11 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
             vertices = torch.empty((0, 3), **f32)
             faces = torch.empty((0, 3), dtype=torch.int32, device=dev)
         del pos
+        if cfg.target_faces is not None:
+            from .simplify import SimplifyConfig, _simplify
+            simplified = {}
+            vertices, faces = _simplify(lib, vertices, faces, SimplifyConfig(target_faces=int(cfg.target_faces),
+                                                                             max_workspace_bytes=cap), s, simplified)
         normals, colors = _at_points(lib, pk, vertices, cap, s, cfg.normals, coeffs)
     mesh = TriangleMesh(vertices, faces, normals, colors)
     if not return_debug:
@@ -367,4 +379,6 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
     debug = {k: cat(v, *shapes[k], dev) for k, v in dbg.items()}
     debug.update(active_bricks=active, keys=keys, cell=cat(tri_cell, (0,), torch.int64, dev), chunks=chunks,
                  total_bricks=total_bricks, grid={"lo": tuple(glo), "h": h, "cells": tuple(cells)})
+    if cfg.target_faces is not None:
+        debug["simplify"] = simplified
     return mesh, debug

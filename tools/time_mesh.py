@@ -11,10 +11,13 @@ per measurement (ms).
   * ``--dense``: the same call with ``sparse=False`` (every brick), the baseline of the sparse grid;
   * ``--colors``: the call with ``colors=True`` at ``--color-degree`` (seeded coefficients of 16 bands): the colour
     stage (``ts_field_colors``) is listed beside the normals stage of the same run, with the bytes it must move
-    (``V x 16 x (40 + 12 (degree + 1)^2) + 12 V``, an upper bound before cache reuse) as a share of the HBM peak.
+    (``V x 16 x (40 + 12 (degree + 1)^2) + 12 V``, an upper bound before cache reuse) as a share of the HBM peak;
+  * ``--target-faces N``: the call with ``target_faces=N`` (section 6i); the simplification is then also timed alone on
+    the unsimplified mesh (``simplify_mesh`` without a model), with its entries' times, the resolution ``r`` the budget
+    search chose, its probes, the clusters, the faces in and out and the stage's peak memory against the cap.
 
     python tools/time_mesh.py [--scene sheet|volume] [--n 1000000] [--resolution 256] [--dense] [--colors]
-                              [--color-degree 3] [--reps 3] [--out f.jsonl]
+                              [--color-degree 3] [--target-faces N] [--reps 3] [--out f.jsonl]
 """
 import argparse
 import json
@@ -73,6 +76,7 @@ def main():
     ap.add_argument("--dense", action="store_true")
     ap.add_argument("--colors", action="store_true")
     ap.add_argument("--color-degree", type=int, default=3)
+    ap.add_argument("--target-faces", type=int, default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -96,10 +100,12 @@ def main():
         model.active_sh_degree = 3
     pk = pack_model(model)
     cfg = MeshConfig(resolution=args.resolution, sparse=not args.dense, colors=args.colors,
-                     color_sh_degree=args.color_degree if args.colors else None)
+                     color_sh_degree=args.color_degree if args.colors else None, target_faces=args.target_faces)
     shape = dict(scene=args.scene, n=args.n, resolution=args.resolution, sparse=cfg.sparse)
     if args.colors:
         shape["color_degree"] = args.color_degree
+    if args.target_faces is not None:
+        shape["target_faces"] = args.target_faces
 
     def run():
         return extract_mesh(model, cfg, packed=pk)
@@ -143,6 +149,30 @@ def main():
         emit("colour stage", ms, vertices=v, bytes_upper_bound=nbytes, gbytes_per_s=round(nbytes / ms / 1e6, 1),
              share_of_hbm_peak=round(nbytes / (ms * 1e-3) / HBM_PEAK, 4), normals_stage_ms=round(n_launches * n_mean, 4),
              **shape)
+    if args.target_faces is not None:
+        import dataclasses
+        from tinysplat_amd.simplify import SimplifyConfig, simplify_mesh
+        plain = extract_mesh(model, dataclasses.replace(cfg, target_faces=None, normals=False, colors=False), packed=pk)
+        scfg = SimplifyConfig(target_faces=args.target_faces, max_workspace_bytes=cfg.max_workspace_bytes)
+
+        def stage():
+            return simplify_mesh(plain, scfg)
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        stage_ms = timed(stage, args.reps)
+        stage_peak = torch.cuda.max_memory_allocated() - base
+        kernel_timer.start()
+        out, info = simplify_mesh(plain, scfg, return_debug=True)
+        stage_parts = kernel_timer.stop()
+        kernels = {name: round(launches * mean_ms, 4) for name, (launches, mean_ms) in sorted(stage_parts.items())}
+        emit("simplify stage", stage_ms, faces_in=int(plain.faces.shape[0]), faces_out=int(out.faces.shape[0]),
+             vertices_in=int(plain.vertices.shape[0]), vertices_out=int(out.vertices.shape[0]), r=info["r"],
+             cell_size=info["cell_size"], probes=info["probes"], clusters=info.get("clusters"),
+             pieces=info.get("pieces"), kernels_ms=kernels,
+             torch_and_host_ms=round(stage_ms - sum(kernels.values()), 4), peak_mib=round(stage_peak / 2 ** 20, 1),
+             cap_mib=cfg.max_workspace_bytes >> 20, **shape)
+        del plain, out
     grid = {"lo": glo, "h": gh, "cells": cells}
     emit("fallback share", 0.0, share=round(fallback_share(model, pk, cfg, active, grid), 5),
          corner_queries=int(active.shape[0]) * BRICK_CORNERS, **shape)
