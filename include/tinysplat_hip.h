@@ -920,6 +920,36 @@ int ts_simplify_solve(int32_t clusters, const int64_t* cluster_keys, const float
 int ts_simplify_faces(int32_t v, int32_t f, const int32_t* faces, const int32_t* vertex_cluster, int32_t* out_faces,
                       uint8_t* keep, void* stream);
 
+/* Mesh clean-up: the faces at edges of valence above two, and the connected components (DESIGN.md section 6j,
+ * csrc/clean_math.h).  Additive entries: the ABI version is unchanged.  None allocates or synchronises; all are integer
+ * work (the face weights: fixed IEEE operations in double) and give the same bits on every run.  vertices float32 [v,3],
+ * faces int32 [f,3]; no entry reads or writes memory at an index a face names without checking it against v.
+ * ts_clean_degenerate: flags uint8 [f] <- 1 where two of the face's indices are equal, else 0.  f == 0: returns 0,
+ * launches nothing.  TS_E_BADARG: f < 0, a NULL pointer with f > 0.
+ * ts_clean_edge_keys: keys int64 [3 f] <- entry 3 face + k: min(a, b) v + max(a, b) of the edge from corner k to corner
+ * (k + 1) % 3.  f == 0: returns 0.  TS_E_BADARG: v < 0, f < 0; with f > 0 also v < 1 or a NULL pointer.
+ * ts_clean_face_weights: weights double [f] <- A2 = (n_x n_x + n_y n_y) + n_z n_z, n = (b - a) x (c - a) in double from
+ * the float32 positions, uncontracted (0 for a face with an index outside [0, v)).  f == 0: returns 0.  TS_E_BADARG as
+ * ts_clean_edge_keys.
+ * ts_clean_mark: sorted_keys int64 [entries] and order int64 [entries] (the entry at each sorted place) are the edge
+ * list sorted by (key, weight descending, face); marks uint8 [f] (zero it first) <- 1, by plain byte stores, for the face
+ * order[i] / 3 of every place i >= 2 with sorted_keys[i] == sorted_keys[i - 2]: the faces of rank two and above at an
+ * edge.  f == 0: returns 0.  TS_E_BADARG: f < 0, entries != 3 f, a NULL pointer with f > 0.
+ * ts_clean_components: labels int32 [v] <- the smallest vertex index of the vertex's connected component, two vertices
+ * being connected when a face holds both (a vertex in no face: itself; a face with an index outside [0, v) joins
+ * nothing).  parent int32 [v] is scratch: the union-find forest (set to the identity here; afterwards parent[x] <= x
+ * and lies in x's component).  Three launches: identity, one thread per face joining (a, b) and (b, c) with integer
+ * compare-and-swap at agent scope, the roots.  v == 0 (and f == 0): returns 0, launches nothing; f == 0: every vertex
+ * its own label.  TS_E_BADARG: v < 0, f < 0, f > 0 with v < 1, a NULL parent or labels with v > 0, NULL faces with
+ * f > 0. */
+int ts_clean_degenerate(int32_t f, const int32_t* faces, uint8_t* flags, void* stream);
+int ts_clean_edge_keys(int32_t v, int32_t f, const int32_t* faces, int64_t* keys, void* stream);
+int ts_clean_face_weights(int32_t v, int32_t f, const float* vertices, const int32_t* faces, double* weights,
+                          void* stream);
+int ts_clean_mark(int32_t f, int64_t entries, const int64_t* sorted_keys, const int64_t* order, uint8_t* marks,
+                  void* stream);
+int ts_clean_components(int32_t v, int32_t f, const int32_t* faces, int32_t* parent, int32_t* labels, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

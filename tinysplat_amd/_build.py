@@ -41,6 +41,8 @@ SOURCES = [
     # simplify.hip: a vertex's cell comes from a float32 difference and quotient that the host build of simplify_math.h
     # and the oracle round separately, and the double sums and solves are compared with a float64 restatement
     ("simplify.hip", ["-ffp-contract=off"]),
+    # clean.hip: a face's weight ranks the faces at an edge and must be numpy's double, product by product
+    ("clean.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -211,6 +211,11 @@ SIGNATURES = {
                                          c_int64, _P, _P, _P]),
     "ts_simplify_solve": (c_int32, [c_int32, _P, _P, _P, _P, _P, c_double, _P, _P]),
     "ts_simplify_faces": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "ts_clean_degenerate": (c_int32, [c_int32, _P, _P, _P]),
+    "ts_clean_edge_keys": (c_int32, [c_int32, c_int32, _P, _P, _P]),
+    "ts_clean_face_weights": (c_int32, [c_int32, c_int32, _P, _P, _P, _P]),
+    "ts_clean_mark": (c_int32, [c_int32, c_int64, _P, _P, _P, _P]),
+    "ts_clean_components": (c_int32, [c_int32, c_int32, _P, _P, _P, _P]),
 }
 
 _lib = None

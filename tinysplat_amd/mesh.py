@@ -54,7 +54,9 @@ class MeshConfig:
     of bricks (the emitted triangles, the packed records and the returned tensors come on top); ``colors``: also the
     vertices' colours (section 6h), with the bands up to ``color_sh_degree`` (None: the model's ``active_sh_degree``;
     it may not exceed what the model stores); ``target_faces``: simplify the mesh to at most this many faces before the
-    normals and colours are evaluated (section 6i, ``simplify.simplify_mesh``; None: the mesh as the grid gives it)."""
+    normals and colours are evaluated (section 6i, ``simplify.simplify_mesh``; None: the mesh as the grid gives it);
+    ``clean``: a ``clean.CleanConfig``: remove the faces at non-manifold edges and the small components (section 6j,
+    ``clean.clean_mesh``) after the simplification and before the normals and colours (None: no clean-up)."""
     surface_level: float = 0.3
     resolution: int = 256
     bounds: Optional[Tuple[Sequence[float], Sequence[float]]] = None
@@ -65,6 +67,7 @@ class MeshConfig:
     colors: bool = False
     color_sh_degree: Optional[int] = None
     target_faces: Optional[int] = None
+    clean: Optional["CleanConfig"] = None
 
     def __post_init__(self):
         if not (isinstance(self.extent_sigmas, (int, float)) and math.isfinite(self.extent_sigmas)
@@ -86,6 +89,10 @@ class MeshConfig:
             raise ValueError(f"color_sh_degree must be in 0..{MAX_COLOR_DEGREE}")
         if self.target_faces is not None and int(self.target_faces) < 1:
             raise ValueError("target_faces must be at least 1")
+        if self.clean is not None:
+            from .clean import CleanConfig
+            if not isinstance(self.clean, CleanConfig):
+                raise ValueError("clean must be a CleanConfig or None")
 
 
 @dataclass
@@ -255,7 +262,9 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
     ``sparse`` on or off.  A surface that leaves the bounds is cut there (an open boundary).  With
     ``config.target_faces`` the welded mesh is simplified to that budget (``simplify.simplify_mesh``, section 6i) before
     the normals and colours are evaluated, at the simplified vertices; ``keys`` and ``cell`` below describe the mesh
-    before that, ``simplify`` (``simplify_mesh``'s debug dict) the step itself.
+    before that, ``simplify`` (``simplify_mesh``'s debug dict) the step itself.  With ``config.clean`` the mesh is then
+    cleaned (``clean.clean_mesh``, section 6j; ``clean`` in the debug dict is its debug dict), again before the normals
+    and colours, which are evaluated at the vertices that stay.
 
     ``return_debug``: also a dict of ``active_bricks`` int64 [A], ``cell`` int64 [T] and ``keys`` int64 [T,3] per
     triangle before welding, ``corners`` float32 [A,729,3], ``knn`` int32 [A,729,16] and ``density`` float32 [A,729] of
@@ -370,6 +379,10 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
             simplified = {}
             vertices, faces = _simplify(lib, vertices, faces, SimplifyConfig(target_faces=int(cfg.target_faces),
                                                                              max_workspace_bytes=cap), s, simplified)
+        if cfg.clean is not None:
+            from .clean import _clean
+            cleaned = {}
+            vertices, faces, _ = _clean(lib, vertices, faces, cfg.clean, s, cleaned)
         normals, colors = _at_points(lib, pk, vertices, cap, s, cfg.normals, coeffs)
     mesh = TriangleMesh(vertices, faces, normals, colors)
     if not return_debug:
@@ -381,4 +394,6 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
                  total_bricks=total_bricks, grid={"lo": tuple(glo), "h": h, "cells": tuple(cells)})
     if cfg.target_faces is not None:
         debug["simplify"] = simplified
+    if cfg.clean is not None:
+        debug["clean"] = cleaned
     return mesh, debug

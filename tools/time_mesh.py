@@ -14,10 +14,14 @@ per measurement (ms).
     (``V x 16 x (40 + 12 (degree + 1)^2) + 12 V``, an upper bound before cache reuse) as a share of the HBM peak;
   * ``--target-faces N``: the call with ``target_faces=N`` (section 6i); the simplification is then also timed alone on
     the unsimplified mesh (``simplify_mesh`` without a model), with its entries' times, the resolution ``r`` the budget
-    search chose, its probes, the clusters, the faces in and out and the stage's peak memory against the cap.
+    search chose, its probes, the clusters, the faces in and out and the stage's peak memory against the cap;
+  * ``--clean``: the call with ``clean=CleanConfig(keep_largest=1)`` (section 6j: the edge step and the components); the
+    clean-up is then also timed alone on the mesh it meets in that call (simplified with ``--target-faces``, without
+    attributes), with its entries' times, torch's three sorts timed on the same keys, what it removed and its peak memory
+    over the input mesh; and ``mesh_components`` alone on the unsimplified mesh, the union-find at the largest size.
 
     python tools/time_mesh.py [--scene sheet|volume] [--n 1000000] [--resolution 256] [--dense] [--colors]
-                              [--color-degree 3] [--target-faces N] [--reps 3] [--out f.jsonl]
+                              [--color-degree 3] [--target-faces N] [--clean] [--reps 3] [--out f.jsonl]
 """
 import argparse
 import json
@@ -68,6 +72,65 @@ def fallback_share(model, pk, cfg, active, grid, chunk_bricks=1024):
     return took / max(1, active.shape[0] * BRICK_CORNERS)
 
 
+@torch.no_grad()
+def clean_stage(model, pk, cfg, ccfg, reps, emit, shape):
+    """The clean-up alone on the mesh ``extract_mesh`` hands it, and the components of the unsimplified mesh."""
+    import dataclasses
+    from tinysplat_amd.clean import clean_mesh, mesh_components
+    bare = dataclasses.replace(cfg, normals=False, colors=False, clean=None)
+    met = extract_mesh(model, bare, packed=pk)
+    v, f = int(met.vertices.shape[0]), int(met.faces.shape[0])
+    input_bytes = met.vertices.numel() * 4 + met.faces.numel() * 4
+
+    def stage():
+        return clean_mesh(met, ccfg)
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    stage_ms = timed(stage, reps)
+    peak = torch.cuda.max_memory_allocated() - base
+    kernel_timer.start()
+    stage()
+    parts = kernel_timer.stop()
+    kernels = {name: round(launches * mean_ms, 4) for name, (launches, mean_ms) in sorted(parts.items())}
+    out, info = clean_mesh(met, ccfg, return_debug=True)
+    # torch's sorts of the edge step, on the same keys: the keys alone, the weights, the keys again (stable)
+    lib = _lib.load()
+    keys = torch.empty((3 * f,), dtype=torch.int64, device=DEV)
+    weights = torch.empty((f,), dtype=torch.float64, device=DEV)
+    s = _stream(torch.device(DEV))
+    assert lib.ts_clean_edge_keys(v, f, _ptr(met.faces), _ptr(keys), s) == 0
+    assert lib.ts_clean_face_weights(v, f, _ptr(met.vertices), _ptr(met.faces), _ptr(weights), s) == 0
+    sorts = {"keys alone": round(timed(lambda: torch.sort(keys), reps), 4),
+             "weights, stable": round(timed(lambda: torch.sort(weights, descending=True, stable=True), reps), 4),
+             "keys, stable": round(timed(lambda: torch.sort(keys, stable=True), reps), 4)}
+    del keys, weights
+    inside = sum(kernels.values()) + sum(sorts.values())
+    emit("clean stage", stage_ms, faces_in=f, faces_out=int(out.faces.shape[0]), vertices_in=v,
+         vertices_out=int(out.vertices.shape[0]), nonmanifold_edges=info["nonmanifold_edges"],
+         removed_nonmanifold_faces=info["removed_nonmanifold_faces"], components=int(info["sizes"].shape[0]),
+         kept_components=int(info["kept_components"].shape[0]), kernels_ms=kernels, torch_sorts_ms=sorts,
+         other_torch_and_host_ms=round(stage_ms - inside, 4), peak_mib=round(peak / 2 ** 20, 1),
+         input_mesh_mib=round(input_bytes / 2 ** 20, 1), **shape)
+    del met, out
+    plain = extract_mesh(model, dataclasses.replace(bare, target_faces=None), packed=pk)
+
+    def comps():
+        return mesh_components(plain)
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    comps_ms = timed(comps, reps)
+    peak = torch.cuda.max_memory_allocated() - base
+    kernel_timer.start()
+    sizes = comps()[3]
+    parts = kernel_timer.stop()
+    launches, mean_ms = parts["ts_clean_components"]
+    emit("components, unsimplified", comps_ms, faces=int(plain.faces.shape[0]), vertices=int(plain.vertices.shape[0]),
+         components=int(sizes.shape[0]), largest=int(sizes.max()) if sizes.shape[0] else 0,
+         ts_clean_components_ms=round(launches * mean_ms, 4), peak_mib=round(peak / 2 ** 20, 1), **shape)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -77,6 +140,7 @@ def main():
     ap.add_argument("--colors", action="store_true")
     ap.add_argument("--color-degree", type=int, default=3)
     ap.add_argument("--target-faces", type=int, default=None)
+    ap.add_argument("--clean", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -99,13 +163,18 @@ def main():
         model.colors_rest = 0.3 * torch.randn((args.n, 15, 3), generator=g, device=DEV)
         model.active_sh_degree = 3
     pk = pack_model(model)
+    from tinysplat_amd.clean import CleanConfig
+    ccfg = CleanConfig(keep_largest=1) if args.clean else None
     cfg = MeshConfig(resolution=args.resolution, sparse=not args.dense, colors=args.colors,
-                     color_sh_degree=args.color_degree if args.colors else None, target_faces=args.target_faces)
+                     color_sh_degree=args.color_degree if args.colors else None, target_faces=args.target_faces,
+                     clean=ccfg)
     shape = dict(scene=args.scene, n=args.n, resolution=args.resolution, sparse=cfg.sparse)
     if args.colors:
         shape["color_degree"] = args.color_degree
     if args.target_faces is not None:
         shape["target_faces"] = args.target_faces
+    if args.clean:
+        shape["clean"] = "keep_largest=1"
 
     def run():
         return extract_mesh(model, cfg, packed=pk)
@@ -152,7 +221,8 @@ def main():
     if args.target_faces is not None:
         import dataclasses
         from tinysplat_amd.simplify import SimplifyConfig, simplify_mesh
-        plain = extract_mesh(model, dataclasses.replace(cfg, target_faces=None, normals=False, colors=False), packed=pk)
+        plain = extract_mesh(model, dataclasses.replace(cfg, target_faces=None, normals=False, colors=False, clean=None),
+                             packed=pk)
         scfg = SimplifyConfig(target_faces=args.target_faces, max_workspace_bytes=cfg.max_workspace_bytes)
 
         def stage():
@@ -173,6 +243,8 @@ def main():
              torch_and_host_ms=round(stage_ms - sum(kernels.values()), 4), peak_mib=round(stage_peak / 2 ** 20, 1),
              cap_mib=cfg.max_workspace_bytes >> 20, **shape)
         del plain, out
+    if args.clean:
+        clean_stage(model, pk, cfg, ccfg, args.reps, emit, shape)
     grid = {"lo": glo, "h": gh, "cells": cells}
     emit("fallback share", 0.0, share=round(fallback_share(model, pk, cfg, active, grid), 5),
          corner_queries=int(active.shape[0]) * BRICK_CORNERS, **shape)
