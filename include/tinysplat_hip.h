@@ -950,6 +950,23 @@ int ts_clean_mark(int32_t f, int64_t entries, const int64_t* sorted_keys, const 
                   void* stream);
 int ts_clean_components(int32_t v, int32_t f, const int32_t* faces, int32_t* parent, int32_t* labels, void* stream);
 
+/* The 32-byte .splat record (csrc/splat_record.h): x y z float32 | exp(scales) float32 x 3 |
+ * r g b a uint8 | rotation w x y z uint8.  Additive entries: the ABI version is unchanged.  None allocates or
+ * synchronises; one thread per record, no atomics.  means, scales, colors_dc float32 [n,3], opacities float32 [n],
+ * quats float32 [n,4]; records: 32 m bytes, 16-byte aligned.
+ * ts_splat_keys: keys float32 [n] <- exp((s0 + s1) + s2) sigmoid(opacity).  n == 0: returns 0, launches nothing.
+ * TS_E_BADARG: n < 0, a NULL pointer with n > 0.
+ * ts_splat_pack: record i of m <- the encoding of Gaussian order[i] (int64 [m]), or of Gaussian i where order is NULL; an
+ * order[i] outside [0, n) reads nothing and gives a record of zeros.  m == 0: returns 0.  TS_E_BADARG: n < 0, m < 0,
+ * m > n without an order; with m > 0 also a NULL pointer (order may be) or records not 16-byte aligned.
+ * ts_splat_unpack: the five tensors' rows <- the decoding of n records.  n == 0: returns 0.  TS_E_BADARG: n < 0; with
+ * n > 0 a NULL pointer or records not 16-byte aligned. */
+int ts_splat_keys(int32_t n, const float* scales, const float* opacities, float* keys, void* stream);
+int ts_splat_pack(int32_t n, int32_t m, const float* means, const float* scales, const float* colors_dc,
+                  const float* opacities, const float* quats, const int64_t* order, void* records, void* stream);
+int ts_splat_unpack(int32_t n, const void* records, float* means, float* scales, float* colors_dc, float* opacities,
+                    float* quats, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

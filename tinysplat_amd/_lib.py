@@ -216,6 +216,9 @@ SIGNATURES = {
     "ts_clean_face_weights": (c_int32, [c_int32, c_int32, _P, _P, _P, _P]),
     "ts_clean_mark": (c_int32, [c_int32, c_int64, _P, _P, _P, _P]),
     "ts_clean_components": (c_int32, [c_int32, c_int32, _P, _P, _P, _P]),
+    "ts_splat_keys": (c_int32, [c_int32, _P, _P, _P, _P]),
+    "ts_splat_pack": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_splat_unpack": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

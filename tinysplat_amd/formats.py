@@ -9,6 +9,9 @@ Host-side mirror of the reference's persistence code:
   * ``export_ply`` - model_gaussian.py:330-361: binary little-endian PLY, one float32 record per
     Gaussian (INRIA 3DGS attribute names).  ``load_ply`` is the inverse (the reference has none; it
     lets trained scenes from any 3DGS tool-chain stand in for the synthetic scene).
+  * ``export_splat`` / ``load_splat`` - the 32-byte-per-Gaussian ``.splat`` file of the WebGL viewers (the reference's
+    ``export_splat`` raises NotImplementedError): records packed and unpacked by csrc/splatfile.hip, ordered by
+    ``splat_order``.
 
 The record interleave / de-interleave runs on the GPU (csrc/formats.hip); the host moves one
 contiguous buffer and writes / parses the header.  No CPU fallback: tensors must be on the GPU.
@@ -258,3 +261,95 @@ def export_mesh_obj(mesh, path) -> None:
             f.writelines("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % (*r, *c) for r, c in zip(xyz.tolist(), rgb))
         f.writelines("vn %.9g %.9g %.9g\n" % tuple(r) for r in nrm.tolist())
         f.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in (faces + 1).tolist())
+
+
+# ------------------------------------------------------------------------------------------------ .splat
+SPLAT_RECORD_BYTES = 32          # TS_SPLAT_RECORD_BYTES of csrc/splat_record.h
+
+
+def _splat_tensors(model):
+    """means, scales, colors_dc, opacities, quats of a model as contiguous float32 on one HIP device (colors_rest is
+    not part of the format)."""
+    ts = [_f32c(getattr(model, f).detach()) for f in ("means", "scales", "colors_dc", "opacities", "quats")]
+    return ts, _need_hip(*ts)
+
+
+def _order_from_keys(keys: Tensor) -> Tensor:
+    """float32 keys [n] -> int64 [n]: descending, ties to the smaller index, NaN last.  One sort of unique int64 values:
+    the high word is the key's bits mapped so that unsigned order is descending float order (-0 counted as +0, every
+    NaN 0xFFFFFFFF, which no number maps to), the low word the index - so the tie rule needs no stable sort."""
+    n = keys.shape[0]
+    if n >= 1 << 32:
+        raise ValueError("splat_order: more than 2^32 keys")
+    bits = (keys + 0.0).view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    ascending = torch.where(bits >= 0x80000000, 0xFFFFFFFF - bits, bits + 0x80000000)
+    high = torch.where(torch.isnan(keys), torch.full_like(bits, 0xFFFFFFFF), 0xFFFFFFFF - ascending)
+    composed = (high << 32) | torch.arange(n, dtype=torch.int64, device=keys.device)
+    # the high word can set bit 63: those values are negative as int64 and would sort first, so the top bit is flipped
+    return torch.sort(composed ^ (-1 << 63)).values & 0xFFFFFFFF
+
+
+def _splat_keys(ts, dev) -> Tensor:
+    n = ts[0].shape[0]
+    keys = torch.empty((n,), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _call("ts_splat_keys", lib.ts_splat_keys, n, _ptr(ts[1]), _ptr(ts[3]), _ptr(keys), _stream(dev))
+    return keys
+
+
+def splat_order(model):
+    """``(keys float32 [n], order int64 [n])``: the importance ``exp(s0 + s1 + s2) sigmoid(opacity)`` of every Gaussian
+    (csrc/splatfile.hip) and the order a .splat file lists them in: descending, ties to the smaller index, NaN last."""
+    ts, dev = _splat_tensors(model)
+    keys = _splat_keys(ts, dev)
+    return keys, _order_from_keys(keys)
+
+
+def splat_records(model, order="importance", limit=None) -> Tensor:
+    """uint8 [m, 32] on the device: the records export_splat writes.  ``order``: "importance"
+    (``splat_order``) or None (model order); ``limit``: keep the first ``m = min(n, limit)`` records of that order."""
+    if order not in ("importance", None):
+        raise ValueError('order must be "importance" or None')
+    if limit is not None and int(limit) < 0:
+        raise ValueError("limit must not be negative")
+    ts, dev = _splat_tensors(model)
+    n = ts[0].shape[0]
+    m = n if limit is None else min(n, int(limit))
+    perm = _order_from_keys(_splat_keys(ts, dev))[:m].contiguous() if order == "importance" else None
+    records = torch.empty((m, SPLAT_RECORD_BYTES), dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _call("ts_splat_pack", lib.ts_splat_pack, n, m, *[_ptr(t) if t.numel() else None for t in ts],
+              _ptr(perm) if perm is not None and m else None, _ptr(records) if m else None, _stream(dev))
+    return records
+
+
+def export_splat(model, path, order="importance", limit=None) -> None:
+    """Writes the model as a .splat file: 32 bytes per Gaussian, little-endian, no header, most important first."""
+    blob = splat_records(model, order=order, limit=limit).cpu().numpy().tobytes()
+    with open(path, "wb") as f:
+        f.write(blob)
+
+
+def load_splat(path, device) -> SplatModel:
+    """Reads a .splat file as a degree-0 model: colors_rest is [n, 0, 3], quats are not renormalised (projection does),
+    opacities are finite (the alpha byte is clamped to 1..254 before the logit)."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    if len(blob) % SPLAT_RECORD_BYTES:
+        raise ValueError(f"a .splat file is a whole number of {SPLAT_RECORD_BYTES}-byte records; found {len(blob)} bytes")
+    n = len(blob) // SPLAT_RECORD_BYTES
+    dev = torch.device(device)
+    records = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).reshape(n, SPLAT_RECORD_BYTES).copy()).to(dev)
+    _need_hip(records)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {"means": torch.empty((n, 3), **f32), "scales": torch.empty((n, 3), **f32),
+           "colors_dc": torch.empty((n, 3), **f32), "opacities": torch.empty((n, 1), **f32),
+           "quats": torch.empty((n, 4), **f32)}
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _call("ts_splat_unpack", lib.ts_splat_unpack, n, _ptr(records) if n else None,
+              *[_ptr(t) if n else None for t in out.values()], _stream(dev))
+    return SplatModel(out["means"], out["colors_dc"], torch.empty((n, 0, 3), **f32), out["scales"], out["quats"],
+                      out["opacities"], active_sh_degree=0, background=torch.zeros(3, device=dev))

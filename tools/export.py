@@ -1,0 +1,81 @@
+#!/usr/bin/env python
+"""Exports a trained scene to a file other tools read.
+
+    python tools/export.py input_file output_file --filetype PLY|SPLAT|OBJ|MESH_PLY [options]
+
+``input_file``: a checkpoint (``.pth`` / ``.pt``, what training saves) or a 3DGS PLY (``.ply``), told apart by the
+extension.  File types:
+
+  PLY       the 3DGS point file (``formats.export_ply``): every tensor, 4 (17 + 3 (K - 1)) bytes per Gaussian
+  SPLAT     the 32-byte-per-Gaussian file the WebGL viewers stream (``formats.export_splat``): view-independent colour
+            only, most important Gaussians first; ``--limit N`` keeps the N most important
+  OBJ       the iso-surface mesh (``extract_mesh``) as a Wavefront OBJ
+  MESH_PLY  the same mesh as a binary PLY
+
+The mesh types take ``--resolution`` (cells along the longest axis), ``--target-faces`` (simplify to a budget) and
+``--colors`` (vertex colours from the spherical harmonics).  Needs a GPU: there is no CPU path.
+"""
+import argparse
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+FILETYPES = ("PLY", "SPLAT", "OBJ", "MESH_PLY")
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("input_file", help="checkpoint (.pth, .pt) or 3DGS PLY (.ply)")
+    ap.add_argument("output_file")
+    ap.add_argument("--filetype", choices=FILETYPES, required=True)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--limit", type=int, default=None, help="SPLAT: keep the N most important Gaussians")
+    ap.add_argument("--resolution", type=int, default=None, help="OBJ, MESH_PLY: cells along the longest axis")
+    ap.add_argument("--target-faces", type=int, default=None, help="OBJ, MESH_PLY: simplify to at most this many faces")
+    ap.add_argument("--colors", action="store_true", help="OBJ, MESH_PLY: vertex colours")
+    args = ap.parse_args(argv)
+    mesh = args.filetype in ("OBJ", "MESH_PLY")
+    if args.limit is not None and args.filetype != "SPLAT":
+        ap.error("--limit goes with --filetype SPLAT")
+    if args.limit is not None and args.limit < 0:
+        ap.error("--limit must not be negative")
+    if not mesh and (args.resolution is not None or args.target_faces is not None or args.colors):
+        ap.error("--resolution, --target-faces and --colors go with --filetype OBJ or MESH_PLY")
+    return args
+
+
+def load_model(path, device):
+    from tinysplat_amd import formats
+    ext = Path(path).suffix.lower()
+    if ext == ".ply":
+        return formats.load_ply(path, device)
+    if ext in (".pth", ".pt"):
+        return formats.load_checkpoint(path, device)
+    raise SystemExit(f"{path}: a checkpoint (.pth, .pt) or a 3DGS PLY (.ply) expected")
+
+
+def main(argv=None):
+    args = parse(argv)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: tinysplat_amd has no CPU path")
+    from tinysplat_amd import MeshConfig, extract_mesh, formats
+    model = load_model(args.input_file, args.device)
+    if args.filetype == "PLY":
+        formats.export_ply(model, args.output_file)
+    elif args.filetype == "SPLAT":
+        formats.export_splat(model, args.output_file, limit=args.limit)
+    else:
+        cfg = MeshConfig(colors=args.colors, target_faces=args.target_faces,
+                         **({} if args.resolution is None else {"resolution": args.resolution}))
+        mesh = extract_mesh(model, cfg)
+        write = formats.export_mesh_obj if args.filetype == "OBJ" else formats.export_mesh_ply
+        write(mesh, args.output_file)
+        print(f"{int(mesh.vertices.shape[0])} vertices, {int(mesh.faces.shape[0])} faces")
+    print(f"wrote {args.output_file}: {Path(args.output_file).stat().st_size} bytes from {model.num_points} Gaussians")
+
+
+if __name__ == "__main__":
+    main()
