@@ -234,6 +234,40 @@ int ts_sort_tiles_above(int32_t num_tiles, const int32_t* tile_bins, const float
  * no queue of oversized tiles.  ts_sort_tiles still uses them (its zeroed_counter: NULL, or a device word
  * known to be zero; ts_tile_offsets zeroes bin_ws[ts_bin_ws_ints(n, num_tiles) - 1] for this purpose). */
 
+/* GROUP FORM of ts_bin_count -> ts_tile_offsets_stats -> ts_bin_scatter (additive entries, ABI 8).  A frame whose
+ * scatter runs in two hops - ts_bin_group_form(n) != 0: n >= 2^18 and n < 2^27, scratch given - needs a base per
+ * (chunk, GROUP of 32 consecutive lists) for its coarse hop only, and the fine hop counts the lists of its group from
+ * the region it streams anyway.  bin_ws (same size, ts_bin_ws_ints) then holds a B x G count matrix instead of the
+ * B x T one; the tile starts, the guard word and the spare word stay where they are, with the same meaning.
+ *   ts_bin_count_groups    bin_ws[b][g] = pairs of chunk b in the lists of group g (same decisions as ts_bin_count)
+ *   ts_group_offsets       bases in place, the start of every group's region, the grand total (tile_start[T]), the
+ *                          capacity guard and the zeroed spare word; tile_bins is written here ONLY when the guard trips
+ *                          or nothing at all is listed (all lists empty; *longest_list = 0 in the latter case)
+ *   ts_bin_scatter_groups  both hops; the fine hop writes tile_bins and the remaining tile starts.  scratch as for
+ *                          ts_bin_scatter, not NULL
+ *   ts_sort_tiles_stats / ts_sort_tiles_above_stats
+ *                          ts_sort_tiles / ts_sort_tiles_above; with longest_list != NULL they also store the length of
+ *                          the frame's longest list there (what ts_tile_offsets_stats stores in the matrix form; n and
+ *                          bin_ws are those of ts_bin_scatter_groups, which left one maximum per group in bin_ws).
+ *                          longest_list == NULL: n and bin_ws are ignored
+ * All of them return TS_E_BADARG for an n the group form does not apply to.  The three stages of a frame must be taken
+ * from the same form. */
+int32_t ts_bin_group_form(int32_t n);
+int ts_bin_count_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
+                        const ts_camera* cam_host, int32_t* bin_ws, void* stream);
+int ts_group_offsets(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins,
+                     const int32_t* cum_tiles_hit, int64_t capacity, int32_t* longest_list, void* stream);
+int ts_bin_scatter_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
+                          const ts_camera* cam_host, int32_t* bin_ws, int32_t* tile_bins, int32_t* bucket_ids,
+                          int32_t* scratch, void* stream);
+int ts_sort_tiles_stats(int32_t num_tiles, const int32_t* tile_bins, const float* depths,
+                        const int32_t* bucket_ids, int32_t* gaussian_ids_sorted, int32_t* sort_ws,
+                        int32_t* zeroed_counter, int32_t n, const int32_t* bin_ws, int32_t* longest_list,
+                        void* stream);
+int ts_sort_tiles_above_stats(int32_t num_tiles, const int32_t* tile_bins, const float* depths,
+                              const int32_t* bucket_ids, int32_t* gaussian_ids_sorted, int32_t n,
+                              const int32_t* bin_ws, int32_t* longest_list, void* stream);
+
 #define TS_RASTER_LOGIT_OPACITY 1 /* `opacity` holds logits: sigmoid (rasterize.py:86) is applied while */
                                   /* packing, and ts_reduce_partials returns the gradient w.r.t. logits */
 
@@ -352,6 +386,11 @@ int ts_reduce_partials(int32_t n, int32_t channels, int32_t flags, const int32_t
 #define TS_FRAME_SEPARATE_SORT 128     /* ts_sort_tiles + ts_raster_fwd_planes even where ts_raster_fwd_sort applies: A/B */
 #define TS_FRAME_STRIPE 16             /* one stripe of a multi-GPU frame: colour stage only for the Gaussians the
                                           stripe lists, clamp mask applied in reduce_partials (before the all-reduce) */
+#define TS_FRAME_GROUP_COUNTS 1024      /* the GROUP FORM of the list-building launches (ts_bin_count_groups ...) where it
+                                          applies: ts_bin_group_form(n) and no TS_FRAME_DIRECT_SCATTER; ignored otherwise.
+                                          Same lists, same image, bit for bit.  For frames whose lists ts_frame_fwd_prepare
+                                          counts: ts_shard_stripe_fwd_import counts in the matrix form, so the stripe
+                                          frame of a sharded step must not set it */
 #define TS_FRAME_SURVIVORS 512         /* SURVIVOR LISTS (csrc/raster.hip): the forward compositing pass hands the entries
                                           it staged to the backward pass, which replays those instead of re-culling the
                                           lists (same rows, same gradients).  Only with the in-kernel sort on 16x16 lists

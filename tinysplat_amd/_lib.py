@@ -114,6 +114,12 @@ SIGNATURES = {
     "ts_bin_scatter": (c_int32, [c_int32, _P, _P, _P, _CAM, _P, _P, _P, _P]),
     "ts_sort_tiles": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "ts_sort_tiles_above": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_bin_group_form": (c_int32, [c_int32]),
+    "ts_bin_count_groups": (c_int32, [c_int32, _P, _P, _P, _CAM, _P, _P]),
+    "ts_group_offsets": (c_int32, [c_int32, c_int32, _P, _P, _P, c_int64, _P, _P]),
+    "ts_bin_scatter_groups": (c_int32, [c_int32, _P, _P, _P, _CAM, _P, _P, _P, _P, _P]),
+    "ts_sort_tiles_stats": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, c_int32, _P, _P, _P]),
+    "ts_sort_tiles_above_stats": (c_int32, [c_int32, _P, _P, _P, _P, c_int32, _P, _P, _P]),
     "ts_num_tiles": (c_int32, [_CAM]),
     "ts_final_floats": (c_int64, [_CAM, c_int32]),
     "ts_cut_tiles": (c_int32, [_CAM, _P, _P]),

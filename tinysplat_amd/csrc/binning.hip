@@ -17,8 +17,10 @@
 //                   sorted sample, LDS histogram + cursors, then every wave sorts sub-buckets of
 //                   <= 256 keys on its own) - O(n log n), no size limit
 //   pack_splats     gathers the compositing operands of a Gaussian into one 48-byte record
-// Traffic: 4 I written + 4 I read (+ gathers) + 4 I written (+ 8 B T for the count matrix) against the 36 I a 3-pass 64-bit
-// LSD radix sort of key+payload would move at minimum.
+// Frames that scatter in two hops (2^18 Gaussians and more) have a GROUP FORM of bin_count / tile_offsets / bin_scatter:
+// counts per (chunk, group of 32 tiles), all offsets in one launch, the lists counted by the scatter's fine hop.
+// Traffic: 4 I written + 4 I read (+ gathers) + 4 I written (+ 8 B T for the count matrix; 8 B G + 4 I read once more in the
+// group form) against the 36 I a 3-pass 64-bit LSD radix sort of key+payload would move at minimum.
 #include <hip/hip_runtime.h>
 
 #include "../../include/tinysplat_hip.h"
@@ -359,7 +361,7 @@ __global__ __launch_bounds__(kBinThreads) void bin_count_kernel(
     for (int j = threadIdx.x; j < tw; j += kBinThreads) dst[j] = hist[j];
 }
 
-constexpr int kScanGroups = 16;      // chunk groups of the column scan (waves of its workgroup)
+constexpr int kScanGroups = 16;     // chunk groups of the column scan (waves of its workgroup)
 
 // Column scan of the B x T count matrix in ONE launch: a workgroup owns 64 tile columns, its 16 waves own the
 // 16 chunk groups; thread (tile, group) loads its <= kColPer counts (coalesced across the tiles of a wave, all
@@ -508,8 +510,133 @@ constexpr int kCoarseIdBits = 32 - kCoarseShift;            // ids below 2^27
 #define TS_TWO_HOP_FROM (1 << 18)
 #endif
 constexpr int kTwoHopFrom = TS_TWO_HOP_FROM;
+// THE predicate of the two-hop scatter, and therefore of the group form of count and offsets (below): a frame
+// either runs all three launches in the group form or none
+inline bool two_hop(int n) { return n >= kTwoHopFrom && n < (1 << kCoarseIdBits); }
+// (a two-hop frame has at least four chunks: the group form keeps G + T + 1 words in front of the B x T words of
+// the workspace that the matrix form fills)
+static_assert(kTwoHopFrom >= 4096, "the group form's workspace layout needs bin_num_chunks(n) >= 4");
 
-template <bool BAL>
+// GROUP COUNTS (ts_bin_count_groups -> ts_group_offsets -> ts_bin_scatter_groups).  The coarse hop of a two-hop frame
+// consumes a base per (chunk, tile GROUP), and the fine hop streams the whole region of its group anyway - it can
+// count its 32 lists itself.  So nobody needs the B x T matrix: the histogram has one counter per group of
+// kCoarseTiles lists and the matrix is B x G (250 KB instead of 8 MB on a 1080p frame of 1 M Gaussians), written
+// once, scanned by one workgroup, read once.  Workspace in this form:
+//   bin_ws[0 .. B*G)            counts -> bases (dead once the coarse hop has run)
+//   bin_ws[B*G .. B*G + G)      column totals where the columns are scanned by a launch of their own
+//   bin_ws[T+1 .. T+1+G)        longest list of every group (fine hop; behind the T + 1 words ts_sort_tiles may use)
+//   bin_ws[B*T ..]              tile_start[T + 1] | guard | spare: where the matrix form has them, same meaning
+// counts[b * groups + g]; same walk, same TightTest, same list index as bin_count_kernel.
+__global__ __launch_bounds__(kBinThreads) void group_bin_count_kernel(
+    int n, int chunk, const float* __restrict__ xys, const int* __restrict__ radii,
+    const float4* __restrict__ splats, const ts_camera cam, int groups, int* __restrict__ counts) {
+    extern __shared__ int hist[];
+    for (int j = threadIdx.x; j < groups; j += kBinThreads) hist[j] = 0;
+    __syncthreads();
+    const int g0 = blockIdx.x * chunk, g1 = min(n, g0 + chunk);
+    walk_chunk(g0, g1, xys, radii, splats, cam, [&](int t, int) { atomicAdd(&hist[t >> kCoarseShift], 1); });
+    __syncthreads();
+    int* dst = counts + (size_t)blockIdx.x * groups;
+    for (int j = threadIdx.x; j < groups; j += kBinThreads) dst[j] = hist[j];
+}
+
+// Group offsets in ONE launch of one workgroup: exclusive prefix over the chunks of every group column (in place),
+// exclusive prefix of the column totals -> tile_start[g * kCoarseTiles] (a group's region starts where its first
+// list does), tile_start[T] = grand total, and tile_offsets_kernel's other duties: the sort counter word, the
+// capacity guard, all lists emptied on overflow.  tile_bins and the tile_start entries inside a group are the fine
+// hop's; a frame that lists nothing at all gets them here, because its caller may skip the scatter.
+// Columns: thread (column, row group) of a 256 x 4 layout loads its <= kGoPer counts (coalesced across columns, all
+// loads issued before the first use), scans them in registers; row-group sums meet in LDS.  Frames with more than
+// 256 columns or 256 chunks take several such steps.  counts == nullptr: column_scan_kernel has run over the B x G
+// matrix (B x G > kGoSingleMax ints: too many bytes for one CU's load path) and col_total holds its totals.
+constexpr int kGoThreads = 1024;
+constexpr int kGoCols = 256;
+constexpr int kGoRows = kGoThreads / kGoCols;
+constexpr int kGoPer = 64;
+constexpr int kGoLdsGroups = 2048;
+constexpr int kGoSingleMax = 1 << 17;
+__global__ __launch_bounds__(kGoThreads) void group_tile_offsets_kernel(
+    int num_tiles, int groups, int chunks, int* __restrict__ counts, const int* col_total,
+    int* __restrict__ tile_start, int* __restrict__ tile_bins, int* __restrict__ spare,
+    const int* __restrict__ total_ptr, long long capacity, int* __restrict__ longest_out) {
+    __shared__ int rsum[kGoRows][kGoCols];
+    __shared__ int gtot[kGoLdsGroups];
+    __shared__ int carry, over;
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        carry = 0;
+        *spare = 0;                                       // the workspace's last word: ts_sort_tiles' tile counter
+        over = (total_ptr && capacity >= 0 && ((long long)*total_ptr > capacity || *total_ptr < 0)) ? 1 : 0;
+        spare[-1] = over;
+    }
+    __syncthreads();
+    if (!over) {
+        const int* tot = col_total;
+        if (counts) {
+            const int gl = tid & (kGoCols - 1), r = tid / kGoCols;
+#pragma unroll 1
+            for (int c0 = 0; c0 < groups; c0 += kGoCols) {
+                const int g = c0 + gl;
+                int colbase = 0;                           // (the same in the kGoRows threads of a column)
+#pragma unroll 1
+                for (int r0 = 0; r0 < chunks; r0 += kGoRows * kGoPer) {
+                    const int b0 = r0 + r * kGoPer;
+                    int c[kGoPer];
+                    int sum = 0;
+                    const unsigned int col = (unsigned int)(b0 * groups + g);     // (B x G <= kGoSingleMax: 32 bits)
+                    if (g < groups) {
+#pragma unroll
+                        for (int j = 0; j < kGoPer; ++j) c[j] = (b0 + j < chunks) ? counts[col + (unsigned int)(j * groups)] : 0;
+#pragma unroll
+                        for (int j = 0; j < kGoPer; ++j) {
+                            const int v = c[j];
+                            c[j] = sum;
+                            sum += v;
+                        }
+                    }
+                    rsum[r][gl] = sum;
+                    __syncthreads();
+                    int base = colbase, all = 0;
+#pragma unroll
+                    for (int q = 0; q < kGoRows; ++q) {
+                        const int v = rsum[q][gl];
+                        if (q < r) base += v;
+                        all += v;
+                    }
+                    if (g < groups) {
+#pragma unroll
+                        for (int j = 0; j < kGoPer; ++j)
+                            if (b0 + j < chunks) counts[col + (unsigned int)(j * groups)] = base + c[j];
+                    }
+                    colbase += all;
+                    __syncthreads();                       // rsum is rewritten by the next step
+                }
+                if (r == 0 && g < groups) gtot[g] = colbase;
+            }
+            __syncthreads();
+            tot = gtot;
+        }
+        for (int base = 0; base < groups; base += kGoThreads) {
+            const int g = base + tid;
+            const int v = g < groups ? tot[g] : 0;
+            int total;
+            const int inc = block_inclusive_scan<kGoThreads / 64>(v, &total);
+            if (g < groups) tile_start[g << kCoarseShift] = carry + inc - v;
+            __syncthreads();
+            if (tid == 0) carry += total;
+            __syncthreads();
+        }
+        if (tid == 0) tile_start[num_tiles] = carry;         // tile_start[T]: end of the last bucket
+        if (carry != 0) return;
+        if (tid == 0 && longest_out) *longest_out = 0;       // nothing listed: no later launch may come to say so
+    }
+    for (int t = tid; t <= num_tiles; t += kGoThreads) {     // overflow, or nothing listed: every list empty
+        tile_start[t] = 0;
+        if (t < num_tiles) reinterpret_cast<int2*>(tile_bins)[t] = make_int2(0, 0);
+    }
+}
+
+template <bool BAL, bool GROUPS = false>
 __global__ __launch_bounds__(kBinThreads) void bin_scatter_coarse_kernel(
     int n, int chunk, const float* __restrict__ xys, const int* __restrict__ radii,
     const float4* __restrict__ splats, const ts_camera cam, int num_tiles, const int* __restrict__ bases,
@@ -517,14 +644,20 @@ __global__ __launch_bounds__(kBinThreads) void bin_scatter_coarse_kernel(
     extern __shared__ int cursor[];
     if (tile_start[num_tiles + 1] != 0) return;              // capacity guard (tile_offsets_kernel)
     const int groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
-    // cursor[g] = start of the group's region + the entries earlier chunks put into the group's tiles; the chunk's
-    // row of the base matrix is read coalesced by the whole workgroup and summed per group with LDS atomics
-    const int* src = bases + (size_t)blockIdx.x * num_tiles;
-    for (int g = threadIdx.x; g < groups; g += kBinThreads) cursor[g] = tile_start[g << kCoarseShift];
-    __syncthreads();
-    for (int t = threadIdx.x; t < num_tiles; t += kBinThreads) {
-        const int v = src[t];
-        if (v) atomicAdd(&cursor[t >> kCoarseShift], v);
+    if (GROUPS) {
+        // the chunk's row of the B x G base matrix: one value per cursor
+        const int* src = bases + (size_t)blockIdx.x * groups;
+        for (int g = threadIdx.x; g < groups; g += kBinThreads) cursor[g] = tile_start[g << kCoarseShift] + src[g];
+    } else {
+        // cursor[g] = start of the group's region + the entries earlier chunks put into the group's tiles; the chunk's
+        // row of the base matrix is read coalesced by the whole workgroup and summed per group with LDS atomics
+        const int* src = bases + (size_t)blockIdx.x * num_tiles;
+        for (int g = threadIdx.x; g < groups; g += kBinThreads) cursor[g] = tile_start[g << kCoarseShift];
+        __syncthreads();
+        for (int t = threadIdx.x; t < num_tiles; t += kBinThreads) {
+            const int v = src[t];
+            if (v) atomicAdd(&cursor[t >> kCoarseShift], v);
+        }
     }
     __syncthreads();
     const int g0 = blockIdx.x * chunk, g1 = min(n, g0 + chunk);
@@ -616,6 +749,152 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_kernel(int num_
         }
         __syncthreads();                                              // ids / tiles / loff are rewritten by the next pass
     }
+}
+
+// Fine hop of the GROUP form: the workgroup knows only where its group's region begins and ends (tile_start at the
+// group boundaries, group_tile_offsets_kernel); the tile-in-group sits in the top kCoarseShift bits of every scratch
+// word, so it counts its lists itself, scans the 32 counts and publishes what tile_offsets_kernel publishes in the
+// matrix form - tile_bins[t] ((0, 0) for an empty list), tile_start[t] - plus the group's longest list, then places
+// the ids exactly as bin_scatter_fine_kernel does.  A region of up to kFinePass entries is counted by the placing
+// pass itself (one read); a longer one is streamed twice (the second time out of the L2 the coarse hop filled).
+__global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_groups_kernel(int num_tiles,
+                                                                               int* __restrict__ tile_start,
+                                                                               int* __restrict__ tile_bins,
+                                                                               int* __restrict__ group_max,
+                                                                               const int* __restrict__ scratch,
+                                                                               int* __restrict__ bucket_ids) {
+    if (tile_start[num_tiles + 1] != 0) return;          // capacity guard: every list was emptied already
+    __shared__ int cursor[kCoarseTiles];                 // next free word of every bucket of the group
+    const int t0 = blockIdx.x << kCoarseShift, t1 = min(num_tiles, t0 + kCoarseTiles);
+    const int begin = tile_start[t0], end = tile_start[t1];
+    __shared__ int hist[kCoarseTiles], loff[kCoarseTiles + 1], gbase[kCoarseTiles];
+    __shared__ int ids[kFinePass];
+    __shared__ unsigned char tiles[kFinePass];
+    if ((int)threadIdx.x < kCoarseTiles) {
+        hist[threadIdx.x] = 0;
+        cursor[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    // wave 0, lane t: list t of the group has c entries, ex in the lists before it
+    auto publish = [&](int t, int c, int ex) {
+        const int s = begin + ex;
+        if (t < t1 - t0) {
+            cursor[t] = s;
+            if (t > 0) tile_start[t0 + t] = s;           // ([t0] is the group's start: there since the offsets launch)
+            reinterpret_cast<int2*>(tile_bins)[t0 + t] = c > 0 ? make_int2(s, s + c) : make_int2(0, 0);
+        }
+        int longest = c;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) longest = max(longest, __shfl_xor(longest, d, 64));
+        if (t == 0) group_max[blockIdx.x] = longest;
+    };
+    const bool counted = end - begin > kFinePass || end == begin;
+    if (counted) {
+        for (int c0 = begin; c0 < end; c0 += kFinePass) {
+            const int m = min(kFinePass, end - c0);
+            unsigned int w[kFineAhead];
+#pragma unroll
+            for (int u = 0; u < kFineAhead; ++u) {
+                const int k = u * kFineThreads + (int)threadIdx.x;
+                if (k < m) w[u] = (unsigned int)scratch[c0 + k];
+            }
+#pragma unroll
+            for (int u = 0; u < kFineAhead; ++u) {
+                const int k = u * kFineThreads + (int)threadIdx.x;
+                if (k < m) atomicAdd(&hist[w[u] >> kCoarseIdBits], 1);
+            }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < 64) {
+            const int t = threadIdx.x;
+            const int c = t < kCoarseTiles ? hist[t] : 0;
+            int inc = c;
+#pragma unroll
+            for (int d = 1; d < kCoarseTiles; d <<= 1) {
+                const int o = __shfl_up(inc, d, 64);
+                if (t >= d) inc += o;
+            }
+            publish(t, c, inc - c);
+            if (t < kCoarseTiles) hist[t] = 0;
+        }
+        __syncthreads();
+    }
+    for (int c0 = begin; c0 < end; c0 += kFinePass) {
+        const int m = min(kFinePass, end - c0);                       // entries of this pass
+        unsigned int w[kFineAhead];
+        int rank[kFineAhead];
+#pragma unroll
+        for (int u = 0; u < kFineAhead; ++u) {
+            const int k = u * kFineThreads + (int)threadIdx.x;
+            if (k < m) w[u] = (unsigned int)scratch[c0 + k];
+        }
+#pragma unroll
+        for (int u = 0; u < kFineAhead; ++u) {
+            const int k = u * kFineThreads + (int)threadIdx.x;
+            if (k < m) rank[u] = atomicAdd(&hist[w[u] >> kCoarseIdBits], 1);
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < 64) {                                  // one wave: offsets of the pass, bases, reset
+            const int t = threadIdx.x;
+            const int c = t < kCoarseTiles ? hist[t] : 0;
+            int inc = c;                                              // inclusive scan over the first 32 lanes
+#pragma unroll
+            for (int d = 1; d < kCoarseTiles; d <<= 1) {
+                const int o = __shfl_up(inc, d, 64);
+                if (t >= d) inc += o;
+            }
+            if (!counted) publish(t, c, inc - c);                     // the only pass of the region: its counts are the lists'
+            if (t < kCoarseTiles) {
+                loff[t] = inc - c;
+                gbase[t] = cursor[t];
+                cursor[t] += c;
+                hist[t] = 0;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kFineAhead; ++u) {
+            const int k = u * kFineThreads + (int)threadIdx.x;
+            if (k < m) {
+                const int t = (int)(w[u] >> kCoarseIdBits);
+                const int lp = loff[t] + rank[u];
+                ids[lp] = (int)(w[u] & ((1u << kCoarseIdBits) - 1u));
+                tiles[lp] = (unsigned char)t;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kFineAhead; ++u) {
+            const int k = u * kFineThreads + (int)threadIdx.x;
+            if (k < m) {
+                const int t = tiles[k];
+                bucket_ids[gbase[t] + (k - loff[t])] = ids[k];
+            }
+        }
+        __syncthreads();                                              // ids / tiles / loff are rewritten by the next pass
+    }
+}
+
+// The frame's longest list in the group form: the fine hop left one maximum per group, and the first workgroup of
+// the sort launch that follows it anyway reduces them into the caller's word (no launch of its own, no device-scope
+// atomics).  Nothing is stored for a frame that tripped the capacity guard, as in the matrix form.
+struct ListStats {
+    const int* group_max;       // null: no statistic asked for
+    const int* guard;
+    int* longest_out;
+    int groups;
+};
+__device__ __forceinline__ void store_longest(const ListStats& st) {
+    __shared__ int longest;
+    if (threadIdx.x == 0) longest = 0;
+    __syncthreads();
+    int m = 0;
+    for (int g = threadIdx.x; g < st.groups; g += kThreads) m = max(m, st.group_max[g]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, __shfl_xor(m, d, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(&longest, m);             // (LDS)
+    __syncthreads();
+    if (threadIdx.x == 0 && *st.guard == 0) *st.longest_out = longest;
 }
 
 // ---- per-tile bitonic sort ---------------------------------------------------------------------
@@ -812,7 +1091,8 @@ __device__ __forceinline__ void sort_tile_sample(const int* __restrict__ g,
 __global__ __launch_bounds__(kThreads) void sort_tiles_small_kernel(
     int num_tiles, const int* __restrict__ tile_bins, const float* __restrict__ depths,
     const int* __restrict__ bucket_ids, int* __restrict__ ids_sorted, int* __restrict__ large_count,
-    int* __restrict__ large_list) {
+    int* __restrict__ large_list, const ListStats stats) {
+    if (stats.group_max && blockIdx.x == 0) store_longest(stats);
     const int lane = threadIdx.x & 63;
     const int tile = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
     if (tile >= num_tiles) return;
@@ -874,8 +1154,9 @@ __global__ __launch_bounds__(kThreads) void sort_tiles_large_kernel(
 // footprint costs nothing here, and the queue of oversized tiles with its second launch is gone.
 __global__ __launch_bounds__(kThreads) void sort_tiles_above_kernel(
     const int* __restrict__ tile_bins, const float* __restrict__ depths,
-    const int* __restrict__ bucket_ids, int* __restrict__ ids_sorted) {
+    const int* __restrict__ bucket_ids, int* __restrict__ ids_sorted, const ListStats stats) {
     __shared__ unsigned long long lds_u64[kLargeLdsU64 > kSortCap / 2 ? kLargeLdsU64 : kSortCap / 2];
+    if (stats.group_max && blockIdx.x == 0) store_longest(stats);
     const int2 range = reinterpret_cast<const int2*>(tile_bins)[blockIdx.x];
     const int n = range.y - range.x;
     if (n <= kWaveSortMax) return;
@@ -978,6 +1259,78 @@ int ts_tile_offsets_stats(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t
     return launch_status();
 }
 
+int32_t ts_bin_group_form(int32_t n) { return two_hop(n) ? 1 : 0; }
+
+int ts_bin_count_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
+                        const ts_camera* cam, int32_t* bin_ws, void* stream) {
+    if (!cam || !bin_ws || !xys || !radii || !two_hop(n)) return TS_E_BADARG;
+    const int nt = ts_num_tiles(cam);
+    if (nt <= 0) return 0;
+    const int chunks = bin_num_chunks(n);
+    const int chunk = (n + chunks - 1) / chunks;
+    const int groups = (nt + kCoarseTiles - 1) >> kCoarseShift;
+    hipLaunchKernelGGL(group_bin_count_kernel, dim3(chunks), dim3(kBinThreads), (size_t)groups * sizeof(int),
+                       (hipStream_t)stream, n, chunk, xys, radii, reinterpret_cast<const float4*>(splats), *cam,
+                       groups, bin_ws);
+    return launch_status();
+}
+
+int ts_group_offsets(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins,
+                     const int32_t* cum_tiles_hit, int64_t capacity, int32_t* longest_list, void* stream) {
+    if (num_tiles < 0 || !two_hop(n)) return TS_E_BADARG;
+    if (num_tiles == 0) return 0;
+    if (!bin_ws || !tile_bins) return TS_E_BADARG;
+    const int chunks = bin_num_chunks(n);
+    const int groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
+    int* tile_start = bin_ws + (size_t)chunks * num_tiles;
+    int* spare = bin_ws + (ts_bin_ws_ints(n, num_tiles) - 1);
+    const int* total_ptr = cum_tiles_hit ? cum_tiles_hit + (n - 1) : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    // one workgroup scans the columns too while the B x G matrix is small (config 3: 245 x 255 ints = 250 KB);
+    // beyond kGoSingleMax ints (config 5: 512 x 507) the columns get column_scan_kernel's many workgroups first
+    if ((long long)chunks * groups <= kGoSingleMax && groups <= kGoLdsGroups) {
+        hipLaunchKernelGGL(group_tile_offsets_kernel, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups, chunks,
+                           bin_ws, (const int*)nullptr, tile_start, tile_bins, spare, total_ptr, (long long)capacity,
+                           longest_list);
+    } else {
+        int* col_total = bin_ws + (size_t)chunks * groups;
+        const int per_group = (chunks + kScanGroups - 1) / kScanGroups;
+        hipLaunchKernelGGL(column_scan_kernel, dim3((groups + kColTiles - 1) / kColTiles),
+                           dim3(kColTiles * kScanGroups), 0, s, groups, chunks, per_group, bin_ws, col_total);
+        hipLaunchKernelGGL(group_tile_offsets_kernel, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups, chunks,
+                           (int*)nullptr, (const int*)col_total, tile_start, tile_bins, spare, total_ptr,
+                           (long long)capacity, longest_list);
+    }
+    return launch_status();
+}
+
+int ts_bin_scatter_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
+                          const ts_camera* cam, int32_t* bin_ws, int32_t* tile_bins, int32_t* bucket_ids,
+                          int32_t* scratch, void* stream) {
+    if (!cam || !xys || !radii || !bin_ws || !tile_bins || !bucket_ids || !scratch || !two_hop(n))
+        return TS_E_BADARG;
+    const int nt = ts_num_tiles(cam);
+    if (nt <= 0) return 0;
+    const int chunks = bin_num_chunks(n);
+    const int chunk = (n + chunks - 1) / chunks;
+    const int groups = (nt + kCoarseTiles - 1) >> kCoarseShift;
+    int* tile_start = bin_ws + (size_t)chunks * nt;
+    hipStream_t s = (hipStream_t)stream;
+    if (cam->hints & TS_HINT_BALANCED_WALK)
+        hipLaunchKernelGGL((bin_scatter_coarse_kernel<true, true>), dim3(chunks), dim3(kBinThreads),
+                           (size_t)groups * sizeof(int), s, n, chunk, xys, radii,
+                           reinterpret_cast<const float4*>(splats), *cam, nt, (const int*)bin_ws,
+                           (const int*)tile_start, scratch);
+    else
+        hipLaunchKernelGGL((bin_scatter_coarse_kernel<false, true>), dim3(chunks), dim3(kBinThreads),
+                           (size_t)groups * sizeof(int), s, n, chunk, xys, radii,
+                           reinterpret_cast<const float4*>(splats), *cam, nt, (const int*)bin_ws,
+                           (const int*)tile_start, scratch);
+    hipLaunchKernelGGL(bin_scatter_fine_groups_kernel, dim3(groups), dim3(kFineThreads), 0, s, nt, tile_start,
+                       tile_bins, bin_ws + nt + 1, (const int*)scratch, bucket_ids);
+    return launch_status();
+}
+
 int ts_bin_scatter(int32_t n, const float* xys, const int32_t* radii, const float* splats,
                    const ts_camera* cam, const int32_t* bin_ws, int32_t* bucket_ids, int32_t* scratch,
                    void* stream) {
@@ -992,7 +1345,7 @@ int ts_bin_scatter(int32_t n, const float* xys, const int32_t* radii, const floa
     // two coalesced hops (see bin_scatter_coarse_kernel) where the write amplification of the direct scatter is what
     // binds; a small launch (a 100 k scene, the ~125 k records of one rank of a sharded frame) is latency-bound and
     // the second launch costs more than it saves (34 vs 12 us on a 1/8 stripe of config 3)
-    if (scratch && n >= kTwoHopFrom && n < (1 << kCoarseIdBits)) {
+    if (scratch && two_hop(n)) {
         const int groups = (nt + kCoarseTiles - 1) >> kCoarseShift;
         // load-balanced walk where the caller says a Gaussian covers many tiles (ts_camera.hints & TS_HINT_BALANCED_WALK):
         // config 5 (16 bounding-box tiles per Gaussian) coarse hop 369 -> 274 us; config 3 (6 tiles) 51 -> 56 us
@@ -1021,12 +1374,40 @@ int ts_bin_scatter(int32_t n, const float* xys, const int32_t* radii, const floa
     return launch_status();
 }
 
+}  // extern "C"
+
+namespace {
+// where the group form keeps what the sort launch needs for the longest-list word (layout: GROUP COUNTS above)
+inline bool list_stats(int n, int num_tiles, const int32_t* bin_ws, int32_t* longest_list, ListStats* st) {
+    *st = ListStats{nullptr, nullptr, nullptr, 0};
+    if (!longest_list) return true;
+    if (!bin_ws || !two_hop(n) || num_tiles <= 0) return false;
+    st->group_max = bin_ws + num_tiles + 1;
+    st->guard = bin_ws + (size_t)bin_num_chunks(n) * num_tiles + num_tiles + 1;
+    st->longest_out = longest_list;
+    st->groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
 int ts_sort_tiles(int32_t num_tiles, const int32_t* tile_bins, const float* depths,
                   const int32_t* bucket_ids, int32_t* gaussian_ids_sorted, int32_t* sort_ws,
                   int32_t* zeroed_counter, void* stream) {
+    return ts_sort_tiles_stats(num_tiles, tile_bins, depths, bucket_ids, gaussian_ids_sorted, sort_ws, zeroed_counter,
+                               0, nullptr, nullptr, stream);
+}
+
+int ts_sort_tiles_stats(int32_t num_tiles, const int32_t* tile_bins, const float* depths,
+                        const int32_t* bucket_ids, int32_t* gaussian_ids_sorted, int32_t* sort_ws,
+                        int32_t* zeroed_counter, int32_t n, const int32_t* bin_ws, int32_t* longest_list,
+                        void* stream) {
     if (num_tiles < 0) return TS_E_BADARG;
     if (num_tiles == 0) return 0;
     if (!tile_bins || !depths || !bucket_ids || !gaussian_ids_sorted || !sort_ws) return TS_E_BADARG;
+    ListStats stats;
+    if (!list_stats(n, num_tiles, bin_ws, longest_list, &stats)) return TS_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     // counter + list of the tiles beyond the sorting network.  zeroed_counter: a word the caller knows to
     // be zero (ts_tile_offsets leaves the last word of its workspace so) - saves a 4-byte memset launch
@@ -1038,7 +1419,7 @@ int ts_sort_tiles(int32_t num_tiles, const int32_t* tile_bins, const float* dept
     }
     hipLaunchKernelGGL(sort_tiles_small_kernel, dim3((num_tiles + kThreads / 64 - 1) / (kThreads / 64)),
                        dim3(kThreads), 0, s, (int)num_tiles, tile_bins, depths, bucket_ids,
-                       gaussian_ids_sorted, counter, list);
+                       gaussian_ids_sorted, counter, list, stats);
     hipLaunchKernelGGL(sort_tiles_mid_kernel, dim3(num_tiles), dim3(kThreads), 0, s, tile_bins, depths,
                        bucket_ids, gaussian_ids_sorted, (int*)nullptr, (int*)nullptr);
     const int grid = num_tiles < 768 ? num_tiles : 768;
@@ -1050,12 +1431,21 @@ int ts_sort_tiles(int32_t num_tiles, const int32_t* tile_bins, const float* dept
 int ts_sort_tiles_above(int32_t num_tiles, const int32_t* tile_bins, const float* depths,
                         const int32_t* bucket_ids, int32_t* gaussian_ids_sorted, int32_t* sort_ws,
                         int32_t* zeroed_counter, void* stream) {
+    (void)sort_ws; (void)zeroed_counter;        // (no queue of oversized tiles any more: every tile has its workgroup)
+    return ts_sort_tiles_above_stats(num_tiles, tile_bins, depths, bucket_ids, gaussian_ids_sorted, 0, nullptr, nullptr,
+                                     stream);
+}
+
+int ts_sort_tiles_above_stats(int32_t num_tiles, const int32_t* tile_bins, const float* depths,
+                              const int32_t* bucket_ids, int32_t* gaussian_ids_sorted, int32_t n,
+                              const int32_t* bin_ws, int32_t* longest_list, void* stream) {
     if (num_tiles < 0) return TS_E_BADARG;
     if (num_tiles == 0) return 0;
     if (!tile_bins || !depths || !bucket_ids || !gaussian_ids_sorted) return TS_E_BADARG;
-    (void)sort_ws; (void)zeroed_counter;        // (no queue of oversized tiles any more: every tile has its workgroup)
+    ListStats stats;
+    if (!list_stats(n, num_tiles, bin_ws, longest_list, &stats)) return TS_E_BADARG;
     hipLaunchKernelGGL(sort_tiles_above_kernel, dim3(num_tiles), dim3(kThreads), 0, (hipStream_t)stream, tile_bins,
-                       depths, bucket_ids, gaussian_ids_sorted);
+                       depths, bucket_ids, gaussian_ids_sorted, stats);
     return launch_status();
 }
 

@@ -117,6 +117,19 @@ inline bool survivors(const ts_frame* f) {
            f->cam.wide_tiles == 0 &&
            !(f->flags & (TS_FRAME_SPLIT | TS_FRAME_NARROW_WAVES | TS_FRAME_SEPARATE_SORT));
 }
+// GROUP COUNTS (TS_FRAME_GROUP_COUNTS): count, offsets and scatter of a frame in the group form (binning.hip).  _prepare
+// and _composite ask the same question of the same struct, so the three launches are always of one form
+inline bool group_counts(const ts_frame* f) {
+    return (f->flags & TS_FRAME_GROUP_COUNTS) && !(f->flags & TS_FRAME_DIRECT_SCATTER) && ts_bin_group_form(f->n);
+}
+// TS_FRAME_LIST_STATS: the word behind the count word, or null
+inline int32_t* longest_word(const ts_frame* f) {
+    if ((f->flags & TS_FRAME_LIST_STATS) && f->total_host) {
+        int32_t* dev = mapped_pointer(f->total_host);
+        if (dev) return dev + 1;
+    }
+    return nullptr;
+}
 inline int raster_flags(const ts_frame* f) {
     return TS_RASTER_CLAMP_RGB | ((f->flags & TS_FRAME_SPLIT) ? TS_RASTER_SPLIT_BLOCKS : 0) |
            ((f->flags & TS_FRAME_NARROW_WAVES) ? TS_RASTER_NARROW_WAVES : 0);
@@ -168,14 +181,19 @@ int ts_frame_fwd_prepare(const ts_frame* f, void* stream) {
                                        f->cum_tiles_hit, &f->cam, f->channels == 4 ? f->depths : nullptr, f->splats,
                                        stream)));
     const float* tight = (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr;
-    TS_TRY(TS_ENTRY("ts_bin_count", ts_bin_count(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, stream)));
     // (TS_FRAME_LIST_STATS: the longest list goes to the word behind the count word - read a frame later by the caller's
     // launch policy, never waited for)
-    int32_t* longest = nullptr;
-    if ((f->flags & TS_FRAME_LIST_STATS) && f->total_host) {
-        int32_t* dev = mapped_pointer(f->total_host);
-        if (dev) longest = dev + 1;
+    int32_t* longest = longest_word(f);
+    if (group_counts(f)) {
+        // the lists themselves (tile_bins) are the scatter's work in this form; the longest list's length reaches its
+        // word from the sort launch of _composite (from here only for a frame that lists nothing)
+        TS_TRY(TS_ENTRY("ts_bin_count",
+                        ts_bin_count_groups(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, stream)));
+        return TS_ENTRY("ts_tile_offsets",
+                        ts_group_offsets(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->cum_tiles_hit, f->capacity,
+                                         longest, stream));
     }
+    TS_TRY(TS_ENTRY("ts_bin_count", ts_bin_count(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, stream)));
     TS_TRY(TS_ENTRY("ts_tile_offsets",
                     ts_tile_offsets_stats(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->cum_tiles_hit, f->capacity,
                                           longest, stream)));
@@ -194,19 +212,29 @@ int ts_frame_fwd_composite(const ts_frame* f, void* stream) {
     if (f->num_intersects > 0) {
         const float* tight = (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr;
         // the sorted-id buffer is dead until the sort: it carries the ids between the two scatter hops
-        TS_TRY(TS_ENTRY("ts_bin_scatter",
-                        ts_bin_scatter(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, f->bucket_ids,
-                                       (f->flags & TS_FRAME_DIRECT_SCATTER) ? nullptr : f->gaussian_ids_sorted,
-                                       stream)));
+        const bool groups = group_counts(f);
+        if (groups)
+            TS_TRY(TS_ENTRY("ts_bin_scatter",
+                            ts_bin_scatter_groups(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, f->tile_bins,
+                                                  f->bucket_ids, f->gaussian_ids_sorted, stream)));
+        else
+            TS_TRY(TS_ENTRY("ts_bin_scatter",
+                            ts_bin_scatter(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, f->bucket_ids,
+                                           (f->flags & TS_FRAME_DIRECT_SCATTER) ? nullptr : f->gaussian_ids_sorted,
+                                           stream)));
         int32_t* counter = f->bin_ws + (ts_bin_ws_ints(f->n, num_tiles(f)) - 1);
+        // (group form: the first workgroup of the sort launch also reduces the fine hop's per-group maxima into the
+        // longest-list word)
+        int32_t* longest = groups ? longest_word(f) : nullptr;
         if (fused_sort)
             TS_TRY(TS_ENTRY("ts_sort_tiles",
-                            ts_sort_tiles_above(num_tiles(f), f->tile_bins, f->depths, f->bucket_ids,
-                                                f->gaussian_ids_sorted, f->bin_ws, counter, stream)));
+                            ts_sort_tiles_above_stats(num_tiles(f), f->tile_bins, f->depths, f->bucket_ids,
+                                                      f->gaussian_ids_sorted, f->n, f->bin_ws, longest, stream)));
         else
             TS_TRY(TS_ENTRY("ts_sort_tiles",
-                            ts_sort_tiles(num_tiles(f), f->tile_bins, f->depths, f->bucket_ids, f->gaussian_ids_sorted,
-                                          f->bin_ws, counter, stream)));
+                            ts_sort_tiles_stats(num_tiles(f), f->tile_bins, f->depths, f->bucket_ids,
+                                                f->gaussian_ids_sorted, f->bin_ws, counter, f->n, f->bin_ws, longest,
+                                                stream)));
     }
     if (fused_sort)
         return TS_ENTRY("ts_raster_fwd",

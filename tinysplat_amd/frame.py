@@ -294,6 +294,12 @@ DIRECT_GRADS = os.environ.get("TS_DIRECT_GRADS", "1") != "0"      # A/B switch (
 # of gathering and culling every listed entry again.  Same rows, same gradients.  TS_SURVIVORS=0: the re-culling replay.
 SURVIVORS = os.environ.get("TS_SURVIVORS", "1") != "0"
 
+# GROUP COUNTS (TS_FRAME_GROUP_COUNTS, csrc/binning.hip): a frame whose scatter runs in two hops (2^18 Gaussians and more)
+# counts its pairs per (chunk, group of 32 lists) instead of per (chunk, list) - a B x G matrix, one launch for all
+# offsets - and the scatter's fine hop counts the lists themselves.  Same lists, same frame, bit for bit.
+# TS_GROUP_COUNTS=0: the B x T count matrix for every frame.
+GROUP_COUNTS = os.environ.get("TS_GROUP_COUNTS", "1") != "0"
+
 # CAPACITY ALLOCATION (option, off by default): the per-intersection buffers (bucket_ids | gaussian_ids_sorted;
 # partials in backward) are sized by the bounding-box pair count I, which only the GPU knows (gsplat synchronises
 # for it at the same place, rasterize.py:44).  With TS_CAPACITY_ALLOC=1, from the second frame of a (scene size,
@@ -458,6 +464,8 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
         surv = SURVIVORS and keep and full and mode == 0 and not F.split and INLINE_SORT
         if surv:
             fr.flags |= 512                                               # TS_FRAME_SURVIVORS
+        if GROUP_COUNTS:
+            fr.flags |= 1024                                              # TS_FRAME_GROUP_COUNTS (the executor decides where it applies)
         if full:
             _stats_mode[dev.index] = mode
         fr.cam = cam
