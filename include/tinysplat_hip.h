@@ -1006,6 +1006,19 @@ int ts_splat_pack(int32_t n, int32_t m, const float* means, const float* scales,
 int ts_splat_unpack(int32_t n, const void* records, float* means, float* scales, float* colors_dc, float* opacities,
                     float* quats, void* stream);
 
+/* Image undistortion and resampling (csrc/undistort_math.h).  An additive entry: the ABI version
+ * is unchanged.  It neither allocates nor synchronises; one thread per 4 output pixels, no atomics, the same bits on
+ * every run.
+ * ts_undistort_image: src uint8 [src_h, src_w, 3] on the device; src_k and dst_k (fx fy cx cy, in pixel indices: the
+ * first pixel's centre is 0) and dist (k1 k2 p1 p2 k3 k4 k5 k6) are float32 arrays in HOST memory, read before the call
+ * returns.  Output pixel (u, v) is the mean of n x n bilinear samples of the source at the distorted positions of
+ * (u, v) + ((a + 0.5) / n - 0.5, (b + 0.5) / n - 0.5), n = min(8, ceil(max(src_w / out_w, src_h / out_h))), source
+ * positions clamped to the frame.  out (16-byte aligned, on the device): uint8 [out_h, out_w, 3], the mean rounded half
+ * to even, or with out_float != 0 float32 [out_h, out_w, 3], the unrounded mean / 255.  TS_E_BADARG, before any launch:
+ * a NULL pointer, a size below 1, src_h src_w or out_h out_w of 2^31 or more, out not 16-byte aligned. */
+int ts_undistort_image(const uint8_t* src, int32_t src_h, int32_t src_w, const float* src_k, const float* dst_k,
+                       const float* dist, int32_t out_h, int32_t out_w, int32_t out_float, void* out, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

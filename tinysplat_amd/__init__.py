@@ -9,6 +9,7 @@ from .extract import ExtractConfig, SurfacePoints, extract_surface_points, level
 from .mesh import MeshConfig, TriangleMesh, extract_mesh, vertex_colors
 from .simplify import SimplifyConfig, simplify_mesh
 from .clean import CleanConfig, clean_mesh, mesh_components
+from .dataset import Dataset
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
 from .rasterizer import GaussianRasterizer
 from .scene import Scene
@@ -21,4 +22,4 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "read_point_cloud_ply", "SurfaceConfig", "SurfaceRegularizer", "opacity_entropy", "DensitySamples",
            "sample_points", "density_loss", "density_parts", "ExtractConfig", "SurfacePoints", "extract_surface_points",
            "level_set_points", "MeshConfig", "TriangleMesh", "extract_mesh", "vertex_colors", "SimplifyConfig",
-           "simplify_mesh", "CleanConfig", "clean_mesh", "mesh_components"]
+           "simplify_mesh", "CleanConfig", "clean_mesh", "mesh_components", "Dataset"]

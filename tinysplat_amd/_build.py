@@ -46,6 +46,9 @@ SOURCES = [
     # splatfile.hip: a record's bytes are truncations of float32 (and, for the rotation, double) expressions that the host
     # build of splat_record.h and the float64 oracle round operation by operation; an fma would move values across integers
     ("splatfile.hip", ["-ffp-contract=off"]),
+    # undistort.hip: source coordinates and bilinear sums are compared with a float64 restatement whose float32 run, like
+    # the host build of undistort_math.h, rounds every product and sum on its own
+    ("undistort.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

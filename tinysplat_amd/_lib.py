@@ -225,6 +225,8 @@ SIGNATURES = {
     "ts_splat_keys": (c_int32, [c_int32, _P, _P, _P, _P]),
     "ts_splat_pack": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ts_splat_unpack": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_undistort_image": (c_int32, [_P, c_int32, c_int32, POINTER(c_float), POINTER(c_float), POINTER(c_float),
+                                     c_int32, c_int32, c_int32, _P, _P]),
 }
 
 _lib = None

@@ -1,0 +1,68 @@
+#!/usr/bin/env python
+"""Trains a scene from a COLMAP reconstruction and saves it.
+
+    python tools/train.py --dataset-dir datasets/train --max-iter 10000 --output scene.ply
+
+The flow of the reference's scripts/train.py without its viewer, depth prior and metrics table: ``Dataset`` reads
+``<dataset-dir>/<colmap-path>`` (cameras.bin, images.bin, points3D.bin) and undistorts the images of
+``<dataset-dir>/<images-path>`` on the GPU, ``from_pcd`` starts the model from the sparse points, ``fit`` trains it
+with densification every ``len(cameras)`` steps (train.py:277), and the result is written as a 3DGS PLY (``.ply``), a
+checkpoint (``.pth`` / ``.pt``) or a ``.splat`` file, told apart by the extension of ``--output``.  Flags the reference's
+parser has keep its names and defaults.  Needs a GPU: there is no CPU path.
+"""
+import argparse
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+WRITERS = {".ply": "export_ply", ".pth": "save_checkpoint", ".pt": "save_checkpoint", ".splat": "export_splat"}
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--device", type=str, default="cuda:0")
+    ap.add_argument("--sh-degree", type=int, default=3)
+    ap.add_argument("--max-iter", type=int, default=10_000)
+    ap.add_argument("--dataset-dir", type=str, default="datasets/train")
+    ap.add_argument("--colmap-path", type=str, default="colmap/sparse/0", help="below --dataset-dir")
+    ap.add_argument("--images-path", type=str, default="images", help="below --dataset-dir")
+    ap.add_argument("--max-image-dimension", type=int, default=None,
+                    help="downscale the targets so that their longer side is at most this many pixels")
+    ap.add_argument("--principal-point", choices=("reference", "center"), default="reference",
+                    help="reference: the reference's camera matrices; center: recentre the images on the principal point")
+    ap.add_argument("--output", type=str, default="scene.ply", help="scene.ply, scene.pth or scene.splat")
+    args = ap.parse_args(argv)
+    if Path(args.output).suffix.lower() not in WRITERS:
+        ap.error(f"--output must end in one of {', '.join(WRITERS)}")
+    if args.max_iter < 0 or (args.max_image_dimension is not None and args.max_image_dimension < 1):
+        ap.error("--max-iter must not be negative and --max-image-dimension must be at least 1")
+    return args
+
+
+def main(argv=None):
+    args = parse(argv)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: tinysplat_amd has no CPU path")
+    from tinysplat_amd import Dataset, formats, from_pcd
+    from tinysplat_amd.densify import DensifyConfig, Densifier
+    from tinysplat_amd.training import fit
+    base = Path(args.dataset_dir)
+    dataset = Dataset(base / args.colmap_path, base / args.images_path, max_image_dimension=args.max_image_dimension,
+                      device=args.device, principal_point=args.principal_point)
+    print(f"{len(dataset.cameras)} cameras ({sum(dataset.resampled)} resampled), {dataset.pcd.xyz.shape[0]} points, "
+          f"extent {dataset.spatial_extent:.3f}")
+    model = from_pcd(dataset.pcd, sh_degree=args.sh_degree, device=args.device)
+    densifier = Densifier(model, DensifyConfig(interval_densify=len(dataset.cameras)))      # train.py:277
+    out = fit(model, dataset.cameras, dataset.targets, args.device, args.max_iter, max_sh_degree=args.sh_degree,
+              densifier=densifier)
+    if out is not None:
+        print(f"step {args.max_iter}: loss {float(out['loss']):.6f}")
+    getattr(formats, WRITERS[Path(args.output).suffix.lower()])(model, args.output)
+    print(f"wrote {args.output}: {Path(args.output).stat().st_size} bytes from {model.num_points} Gaussians")
+
+
+if __name__ == "__main__":
+    main()
