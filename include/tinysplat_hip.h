@@ -1019,6 +1019,28 @@ int ts_splat_unpack(int32_t n, const void* records, float* means, float* scales,
 int ts_undistort_image(const uint8_t* src, int32_t src_h, int32_t src_w, const float* src_k, const float* dst_k,
                        const float* dist, int32_t out_h, int32_t out_w, int32_t out_float, void* out, void* stream);
 
+/* Baseline JPEG of a device image (csrc/jpeg_math.h).  Additive entries: the ABI version is
+ * unchanged.  subsampling: 0 = 4:4:4, 1 = 4:2:0; restart_interval in MCUs, 1..65535, or 0 for one MCU row.  All four return
+ * TS_E_BADARG, before any launch, for a width or height outside 1..65535, an unknown subsampling, an interval outside
+ * 0..65535, or an image of so many blocks that the scan's bits leave 31 bits.
+ * ts_jpeg_ws_bytes: the bytes of `workspace`.  ts_jpeg_max_bytes: the largest file of this shape (every block at its
+ * longest, every byte stuffed).  ts_jpeg_header: host only, no device is touched: the file's bytes up to the entropy-coded
+ * data (629 of them) to `out` in host memory -> their number; TS_E_BADARG also for a quality outside 1..100 or a capacity
+ * below 629.
+ * ts_jpeg_encode: image on the device, dtype 0 = uint8 [height, width, 3] (pixel_stride 3) or 1 = float32 with a pixel
+ * stride of 3 or 4 floats, whose samples become rint(clamp(255 x, 0, 255)); workspace: >= ts_jpeg_ws_bytes bytes, 256-byte
+ * aligned; out: device bytes, out_capacity >= ts_jpeg_max_bytes (TS_E_BADARG otherwise: the kernels do not check);
+ * size_word: a device int32 <- the file's size; coefficients: NULL, or device int16 [blocks, 64] <- the quantised
+ * coefficients in zigzag order, blocks in scan order.  It neither allocates nor synchronises; the same bytes on every run.
+ * TS_E_BADARG also for a quality outside 1..100, another dtype or stride, a NULL pointer. */
+int64_t ts_jpeg_ws_bytes(int32_t width, int32_t height, int32_t subsampling, int32_t restart_interval);
+int64_t ts_jpeg_max_bytes(int32_t width, int32_t height, int32_t subsampling, int32_t restart_interval);
+int64_t ts_jpeg_header(int32_t width, int32_t height, int32_t quality, int32_t subsampling, int32_t restart_interval,
+                       uint8_t* out, int64_t out_capacity);
+int ts_jpeg_encode(const void* image, int32_t dtype, int32_t pixel_stride, int32_t width, int32_t height, int32_t quality,
+                   int32_t subsampling, int32_t restart_interval, void* workspace, uint8_t* out, int64_t out_capacity,
+                   int32_t* size_word, int16_t* coefficients, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

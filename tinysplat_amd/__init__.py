@@ -10,16 +10,18 @@ from .mesh import MeshConfig, TriangleMesh, extract_mesh, vertex_colors
 from .simplify import SimplifyConfig, simplify_mesh
 from .clean import CleanConfig, clean_mesh, mesh_components
 from .dataset import Dataset
+from .jpeg import JpegEncoder, encode_jpeg
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
 from .rasterizer import GaussianRasterizer
 from .scene import Scene
 from .surface import (DensitySamples, SurfaceConfig, SurfaceRegularizer, density_loss, density_parts, opacity_entropy,
                       sample_points)
 from .synthetic import RGB2SH, SH2RGB
+from .viewer import Viewer
 
 __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "num_sh_bases",
            "deg_from_sh", "GaussianRasterizer", "Scene", "RGB2SH", "SH2RGB", "PointCloud", "from_pcd", "knn_points",
            "read_point_cloud_ply", "SurfaceConfig", "SurfaceRegularizer", "opacity_entropy", "DensitySamples",
            "sample_points", "density_loss", "density_parts", "ExtractConfig", "SurfacePoints", "extract_surface_points",
            "level_set_points", "MeshConfig", "TriangleMesh", "extract_mesh", "vertex_colors", "SimplifyConfig",
-           "simplify_mesh", "CleanConfig", "clean_mesh", "mesh_components", "Dataset"]
+           "simplify_mesh", "CleanConfig", "clean_mesh", "mesh_components", "Dataset", "Viewer", "encode_jpeg", "JpegEncoder"]

@@ -49,6 +49,10 @@ SOURCES = [
     # undistort.hip: source coordinates and bilinear sums are compared with a float64 restatement whose float32 run, like
     # the host build of undistort_math.h, rounds every product and sum on its own
     ("undistort.hip", ["-ffp-contract=off"]),
+    # jpeg.hip: a quantised coefficient is rint of a float32 quotient of sums of eight products; the host build of
+    # jpeg_math.h must round every product and sum as the kernel does, or a coefficient near a half differs and with it
+    # the file
+    ("jpeg.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

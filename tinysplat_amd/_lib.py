@@ -227,6 +227,11 @@ SIGNATURES = {
     "ts_splat_unpack": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "ts_undistort_image": (c_int32, [_P, c_int32, c_int32, POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                      c_int32, c_int32, c_int32, _P, _P]),
+    "ts_jpeg_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "ts_jpeg_max_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "ts_jpeg_header": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int64]),
+    "ts_jpeg_encode": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int64, _P,
+                                 _P, _P]),
 }
 
 _lib = None

@@ -3,12 +3,14 @@
 
     python tools/train.py --dataset-dir datasets/train --max-iter 10000 --output scene.ply
 
-The flow of the reference's scripts/train.py without its viewer, depth prior and metrics table: ``Dataset`` reads
+The flow of the reference's scripts/train.py without its depth prior and metrics table: ``Dataset`` reads
 ``<dataset-dir>/<colmap-path>`` (cameras.bin, images.bin, points3D.bin) and undistorts the images of
 ``<dataset-dir>/<images-path>`` on the GPU, ``from_pcd`` starts the model from the sparse points, ``fit`` trains it
 with densification every ``len(cameras)`` steps (train.py:277), and the result is written as a 3DGS PLY (``.ply``), a
-checkpoint (``.pth`` / ``.pt``) or a ``.splat`` file, told apart by the extension of ``--output``.  Flags the reference's
-parser has keep its names and defaults.  Needs a GPU: there is no CPU path.
+checkpoint (``.pth`` / ``.pt``) or a ``.splat`` file, told apart by the extension of ``--output``.  ``--viewer`` serves the
+scene while it trains (``tinysplat_amd.Viewer``, the reference's websocket protocol; it is off unless asked for): a pending
+request is rendered between two steps.  Flags the reference's parser has keep its names and defaults.  Needs a GPU: there
+is no CPU path.
 """
 import argparse
 import sys
@@ -33,6 +35,9 @@ def parse(argv=None):
     ap.add_argument("--principal-point", choices=("reference", "center"), default="reference",
                     help="reference: the reference's camera matrices; center: recentre the images on the principal point")
     ap.add_argument("--output", type=str, default="scene.ply", help="scene.ply, scene.pth or scene.splat")
+    ap.add_argument("--viewer", action="store_true", help="serve the scene to a websocket viewer while it trains")
+    ap.add_argument("--viewer-ip", type=str, default="127.0.0.1")
+    ap.add_argument("--viewer-port", type=int, default=8765)
     args = ap.parse_args(argv)
     if Path(args.output).suffix.lower() not in WRITERS:
         ap.error(f"--output must end in one of {', '.join(WRITERS)}")
@@ -56,8 +61,18 @@ def main(argv=None):
           f"extent {dataset.spatial_extent:.3f}")
     model = from_pcd(dataset.pcd, sh_degree=args.sh_degree, device=args.device)
     densifier = Densifier(model, DensifyConfig(interval_densify=len(dataset.cameras)))      # train.py:277
-    out = fit(model, dataset.cameras, dataset.targets, args.device, args.max_iter, max_sh_degree=args.sh_degree,
-              densifier=densifier)
+    viewer = None
+    if args.viewer:
+        from tinysplat_amd import Viewer
+        from tinysplat_amd.viewer import ViewRenderer
+        viewer = Viewer(ViewRenderer(model, dataset.cameras[0], args.device), args.viewer_ip, args.viewer_port)
+        print(f"viewer on ws://{args.viewer_ip}:{viewer.port}")
+    try:
+        out = fit(model, dataset.cameras, dataset.targets, args.device, args.max_iter, max_sh_degree=args.sh_degree,
+                  densifier=densifier, on_step=viewer.service if viewer else None)
+    finally:
+        if viewer:
+            viewer.stop()
     if out is not None:
         print(f"step {args.max_iter}: loss {float(out['loss']):.6f}")
     getattr(formats, WRITERS[Path(args.output).suffix.lower()])(model, args.output)
