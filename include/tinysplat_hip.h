@@ -260,6 +260,26 @@ int ts_group_offsets(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* til
 int ts_bin_scatter_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
                           const ts_camera* cam_host, int32_t* bin_ws, int32_t* tile_bins, int32_t* bucket_ids,
                           int32_t* scratch, void* stream);
+/* ONE WALK form of the same three stages (additive entries, ABI 8): the Gaussians are walked once.  Every chunk writes
+ * its entries, ordered by group, into its own part of scratch - it starts at cum_tiles_hit[first Gaussian - 1], and a
+ * chunk lists at most its bounding-box slots - and leaves its counts and run starts per group in bin_ws; the fine hop
+ * gathers a group's runs.  Applies where ts_bin_one_walk_form(n, num_tiles) != 0 (a group-form n whose groups fit the
+ * emit launch: num_tiles <= 65536 and not a handful) and the camera carries no TS_HINT_BALANCED_WALK; TS_E_BADARG,
+ * before any launch, otherwise.  Same lists, tile starts, guard, spare and longest-list words as the group form.
+ *   ts_bin_emit_groups     the walk.  Reads cum_tiles_hit[n-1] against capacity itself (it runs BEFORE the offsets) and
+ *                          writes nothing when the guard would trip.  scratch: as for ts_bin_scatter_groups
+ *   ts_emit_offsets        ts_group_offsets' duties except the bases; cum_tiles_hit not NULL
+ *   ts_bin_gather_groups   the fine hop: tile_bins, the remaining tile starts, bucket_ids, one maximum per group
+ * ts_bin_stage_capacity(): pairs a chunk can stage in LDS; a chunk that lists more walks twice inside its workgroup. */
+int32_t ts_bin_one_walk_form(int32_t n, int32_t num_tiles);
+int32_t ts_bin_stage_capacity(void);
+int ts_bin_emit_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
+                       const ts_camera* cam_host, const int32_t* cum_tiles_hit, int64_t capacity, int32_t* bin_ws,
+                       int32_t* scratch, void* stream);
+int ts_emit_offsets(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins,
+                    const int32_t* cum_tiles_hit, int64_t capacity, int32_t* longest_list, void* stream);
+int ts_bin_gather_groups(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins, int32_t* bucket_ids,
+                         const int32_t* scratch, void* stream);
 int ts_sort_tiles_stats(int32_t num_tiles, const int32_t* tile_bins, const float* depths,
                         const int32_t* bucket_ids, int32_t* gaussian_ids_sorted, int32_t* sort_ws,
                         int32_t* zeroed_counter, int32_t n, const int32_t* bin_ws, int32_t* longest_list,
@@ -391,6 +411,11 @@ int ts_reduce_partials(int32_t n, int32_t channels, int32_t flags, const int32_t
                                           Same lists, same image, bit for bit.  For frames whose lists ts_frame_fwd_prepare
                                           counts: ts_shard_stripe_fwd_import counts in the matrix form, so the stripe
                                           frame of a sharded step must not set it */
+#define TS_FRAME_ONE_WALK 2048          /* the ONE WALK form (ts_bin_emit_groups ...) where TS_FRAME_GROUP_COUNTS is honoured,
+                                          ts_bin_one_walk_form(n, tiles) holds and cam.hints carries no
+                                          TS_HINT_BALANCED_WALK; ignored otherwise.  ts_frame_fwd_prepare then enqueues
+                                          the colour stage only; ts_frame_fwd_composite emit, offsets, fine hop, sort,
+                                          raster.  Same lists, same frame */
 #define TS_FRAME_SURVIVORS 512         /* SURVIVOR LISTS (csrc/raster.hip): the forward compositing pass hands the entries
                                           it staged to the backward pass, which replays those instead of re-culling the
                                           lists (same rows, same gradients).  Only with the in-kernel sort on 16x16 lists

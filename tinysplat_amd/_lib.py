@@ -118,6 +118,11 @@ SIGNATURES = {
     "ts_bin_count_groups": (c_int32, [c_int32, _P, _P, _P, _CAM, _P, _P]),
     "ts_group_offsets": (c_int32, [c_int32, c_int32, _P, _P, _P, c_int64, _P, _P]),
     "ts_bin_scatter_groups": (c_int32, [c_int32, _P, _P, _P, _CAM, _P, _P, _P, _P, _P]),
+    "ts_bin_one_walk_form": (c_int32, [c_int32, c_int32]),
+    "ts_bin_stage_capacity": (c_int32, []),
+    "ts_bin_emit_groups": (c_int32, [c_int32, _P, _P, _P, _CAM, _P, c_int64, _P, _P, _P]),
+    "ts_emit_offsets": (c_int32, [c_int32, c_int32, _P, _P, _P, c_int64, _P, _P]),
+    "ts_bin_gather_groups": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P]),
     "ts_sort_tiles_stats": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, c_int32, _P, _P, _P]),
     "ts_sort_tiles_above_stats": (c_int32, [c_int32, _P, _P, _P, _P, c_int32, _P, _P, _P]),
     "ts_num_tiles": (c_int32, [_CAM]),

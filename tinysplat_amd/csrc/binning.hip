@@ -19,6 +19,9 @@
 //   pack_splats     gathers the compositing operands of a Gaussian into one 48-byte record
 // Frames that scatter in two hops (2^18 Gaussians and more) have a GROUP FORM of bin_count / tile_offsets / bin_scatter:
 // counts per (chunk, group of 32 tiles), all offsets in one launch, the lists counted by the scatter's fine hop.
+// ONE WALK form of the same frames (bin_scatter_emit / group_tile_offsets<false> / bin_scatter_fine_runs): the Gaussians are
+// walked once - a chunk stages its pairs in LDS, orders them by group and writes them into its own bounding-box slots of
+// the scratch buffer; the fine hop gathers its group's run from every chunk.
 // Traffic: 4 I written + 4 I read (+ gathers) + 4 I written (+ 8 B T for the count matrix; 8 B G + 4 I read once more in the
 // group form) against the 36 I a 3-pass 64-bit LSD radix sort of key+payload would move at minimum.
 #include <hip/hip_runtime.h>
@@ -373,7 +376,8 @@ constexpr int kColPer = (kBinMaxChunks + kScanGroups - 1) / kScanGroups;      //
 __global__ __launch_bounds__(kColTiles * kScanGroups) void column_scan_kernel(int num_tiles, int chunks,
                                                                               int per_group,
                                                                               int* __restrict__ counts,
-                                                                              int* __restrict__ tile_total) {
+                                                                              int* __restrict__ tile_total,
+                                                                              bool write_bases) {
     __shared__ int gsum[kScanGroups][kColTiles];
     const int tl = threadIdx.x & (kColTiles - 1), g = threadIdx.x / kColTiles;
     const int t = blockIdx.x * kColTiles + tl;
@@ -400,9 +404,11 @@ __global__ __launch_bounds__(kColTiles * kScanGroups) void column_scan_kernel(in
         if (q < g) base += v;
         tot += v;
     }
+    if (write_bases) {                                     // (the ONE WALK form wants the totals only: its counts stay counts)
 #pragma unroll
-    for (int j = 0; j < kColPer; ++j)
-        if (b0 + j < b1) counts[(size_t)(b0 + j) * num_tiles + t] = base + c[j];
+        for (int j = 0; j < kColPer; ++j)
+            if (b0 + j < b1) counts[(size_t)(b0 + j) * num_tiles + t] = base + c[j];
+    }
     if (g == 0) tile_total[t] = tot;
 }
 
@@ -500,6 +506,11 @@ __global__ __launch_bounds__(kBinThreads) void bin_scatter_kernel(
 //           entries for it form one run of ~64 words;
 //   fine    one workgroup per group streams its region and places the ids in the tiles' buckets with LDS
 //           cursors: all of a bucket's lines are written by one workgroup, merge in one L2 and leave as full lines.
+// Three forms of these launches exist, chosen per frame (frame.hip asks one predicate per form):
+//   matrix    bin_count -> column_scan + tile_offsets -> scatter (direct, or coarse + fine): B x T counts
+//   group     group_bin_count -> group_tile_offsets -> coarse<.., true> + fine_groups: B x G counts, two walks
+//   one walk  emit -> group_tile_offsets<false> -> fine_runs: B x G counts and run starts, ONE walk; the coarse hop's
+//             scattered 4-byte stores into ~G open runs become a linear copy of the chunk's region out of LDS
 #ifndef TS_COARSE_SHIFT
 #define TS_COARSE_SHIFT 5
 #endif
@@ -555,6 +566,9 @@ constexpr int kGoRows = kGoThreads / kGoCols;
 constexpr int kGoPer = 64;
 constexpr int kGoLdsGroups = 2048;
 constexpr int kGoSingleMax = 1 << 17;
+// BASES = false (ONE WALK, below): the counts are left as they are - every chunk already knows where it writes - and a
+// negative total is refused whatever the capacity, because the emit launch in front has placed nothing for it.
+template <bool BASES = true>
 __global__ __launch_bounds__(kGoThreads) void group_tile_offsets_kernel(
     int num_tiles, int groups, int chunks, int* __restrict__ counts, const int* col_total,
     int* __restrict__ tile_start, int* __restrict__ tile_bins, int* __restrict__ spare,
@@ -567,12 +581,35 @@ __global__ __launch_bounds__(kGoThreads) void group_tile_offsets_kernel(
         carry = 0;
         *spare = 0;                                       // the workspace's last word: ts_sort_tiles' tile counter
         over = (total_ptr && capacity >= 0 && ((long long)*total_ptr > capacity || *total_ptr < 0)) ? 1 : 0;
+        if (!BASES && total_ptr && *total_ptr < 0) over = 1;
         spare[-1] = over;
     }
     __syncthreads();
     if (!over) {
         const int* tot = col_total;
-        if (counts) {
+        if (counts && !BASES) {
+            // column totals only: thread (column, row residue) adds every kGoRows-th count of its column
+            const int gl = tid & (kGoCols - 1), r = tid / kGoCols;
+#pragma unroll 1
+            for (int c0 = 0; c0 < groups; c0 += kGoCols) {
+                const int g = c0 + gl;
+                int sum = 0;
+                if (g < groups) {
+#pragma unroll 8
+                    for (int b = r; b < chunks; b += kGoRows) sum += counts[(unsigned int)(b * groups + g)];
+                }
+                rsum[r][gl] = sum;
+                __syncthreads();
+                if (r == 0 && g < groups) {
+                    int all = 0;
+#pragma unroll
+                    for (int q = 0; q < kGoRows; ++q) all += rsum[q][gl];
+                    gtot[g] = all;
+                }
+                __syncthreads();                           // rsum is rewritten by the next step
+            }
+            tot = gtot;
+        } else if (counts) {
             const int gl = tid & (kGoCols - 1), r = tid / kGoCols;
 #pragma unroll 1
             for (int c0 = 0; c0 < groups; c0 += kGoCols) {
@@ -872,6 +909,308 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_groups_kernel(i
             }
         }
         __syncthreads();                                              // ids / tiles / loff are rewritten by the next pass
+    }
+}
+
+// ONE WALK (ts_bin_emit_groups -> ts_emit_offsets -> ts_bin_gather_groups).  The group form still walks every chunk
+// twice with identical decisions: once to count, once to store at the bases the count gave.  A chunk's destination can
+// be fixed before anything is counted: cum_tiles_hit gives every Gaussian a private range of bounding-box slots, the
+// walk lists at most that many pairs per Gaussian (same ts::tile_bbox, row_range clamped to the box - what
+// reduce_partials relies on for its row slots), and the scratch buffer is sized by the bounding-box total.  So chunk b
+// writes its entries, ordered by group, contiguously from cum_tiles_hit[g0 - 1] on, and leaves two rows of B x G words:
+// how many entries it has per group and where each of those runs starts.  The fine hop gathers its group's runs.
+// Workspace in this form (the group form's words stay where they are):
+//   bin_ws[0 .. T+1)                what ts_sort_tiles may use
+//   bin_ws[T+1 .. T+1+G)            longest list of every group (fine hop)
+//   bin_ws[T+1+G ..)                counts[B][G] | starts[B][G] | column totals[G] (only with the column-scan launch)
+//   bin_ws[B*T ..]                  tile_start[T + 1] | guard | spare
+// During the walk an emitted pair bumps the chunk's per-group histogram and is appended to a staging buffer in LDS
+// (one LDS atomic per wave and emit step: the active lanes take consecutive slots).  A chunk that fits the buffer
+// scans the histogram and places the staged words; one that does not - the append notices, the histogram counts
+// everything regardless - walks a second time and places from the then complete histogram: what two launches did.
+#ifndef TS_STAGE_CAP
+#define TS_STAGE_CAP 20480
+#endif
+constexpr int kStageCap = TS_STAGE_CAP;                  // staged pairs per chunk: 6 bytes each (word + group index)
+constexpr int kEmitMaxGroups = 2048;                     // histogram + cursors: 8 bytes per group; 136 KiB in all
+static_assert((size_t)kStageCap * 6 + (size_t)kEmitMaxGroups * 8 <= 144 * 1024, "LDS budget of a binning workgroup");
+static_assert(kEmitMaxGroups <= 2 * kBinThreads && kEmitMaxGroups <= 65536, "two groups per thread, 16-bit group index");
+static_assert(kEmitMaxGroups <= kGoLdsGroups, "the offsets launch keeps the column totals in LDS");
+
+struct OneWalkLayout {
+    long long counts, starts, col_total, end;            // word offsets into bin_ws
+};
+__host__ __device__ inline OneWalkLayout one_walk_layout(int chunks, int groups, int num_tiles) {
+    OneWalkLayout l;
+    l.counts = (long long)num_tiles + 1 + groups;
+    l.starts = l.counts + (long long)chunks * groups;
+    l.col_total = l.starts + (long long)chunks * groups;
+    l.end = l.col_total + groups;
+    return l;
+}
+// THE predicate of the one-walk form: a two-hop frame whose groups fit the emit launch's LDS and whose rows fit in
+// front of tile_start
+inline bool one_walk_form(int n, int num_tiles) {
+    if (!two_hop(n) || num_tiles <= 0) return false;
+    const int groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
+    const int chunks = bin_num_chunks(n);
+    return groups <= kEmitMaxGroups && one_walk_layout(chunks, groups, num_tiles).end <= (long long)chunks * num_tiles;
+}
+
+__global__ __launch_bounds__(kBinThreads) void bin_scatter_emit_kernel(
+    int n, int chunk, const float* __restrict__ xys, const int* __restrict__ radii,
+    const float4* __restrict__ splats, const ts_camera cam, int groups, const int* __restrict__ cum,
+    long long capacity, int* __restrict__ counts, int* __restrict__ starts, int* __restrict__ scratch) {
+    extern __shared__ int lds[];
+    __shared__ int staged;
+    // capacity guard, read here because the offsets launch runs behind this one; a wrapped total places nothing either.
+    // (The three words of cum_tiles_hit are in flight together, while the histogram is cleared)
+    const int g0 = min(n, (int)blockIdx.x * chunk), g1 = min(n, g0 + chunk);
+    const int total = cum[n - 1];
+    const int chunk_base = g0 > 0 ? cum[g0 - 1] : 0;
+    const int chunk_end = g1 > g0 ? cum[g1 - 1] : chunk_base;
+    int* hist = lds;
+    int* cursor = lds + groups;
+    unsigned int* words = reinterpret_cast<unsigned int*>(lds + 2 * groups);
+    unsigned short* grp = reinterpret_cast<unsigned short*>(words + kStageCap);
+    const int tid = threadIdx.x;
+    for (int j = tid; j < groups; j += kBinThreads) hist[j] = 0;
+    if (tid == 0) staged = 0;
+    __syncthreads();
+    if (total < 0 || (capacity >= 0 && (long long)total > capacity)) return;
+    const int room = chunk_end - chunk_base;                         // the chunk's bounding-box slots
+    walk_chunk(g0, g1, xys, radii, splats, cam, [&](int t, int i) {
+        const int g = t >> kCoarseShift;
+        atomicAdd(&hist[g], 1);
+        const unsigned long long m = __ballot(1);                     // the lanes that emit in this step
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32),
+                                                        __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
+        int base = 0;
+        if (rank == 0) base = atomicAdd(&staged, (int)__popcll(m));
+        base = __builtin_amdgcn_readfirstlane(base);                  // (the first active lane is the one of rank 0)
+        const int slot = base + rank;
+        if (slot < kStageCap) {
+            words[slot] = (unsigned int)i | ((unsigned int)(t & (kCoarseTiles - 1)) << kCoarseIdBits);
+            grp[slot] = (unsigned short)g;
+        }
+    });
+    __syncthreads();
+    const int pairs = staged;                                         // everything the chunk lists
+    // a chunk cannot list more than its bounding-box slots; were it ever to, it lists nothing rather than write
+    // beyond its region
+    const bool sound = pairs <= room;
+    {   // exclusive scan of the histogram: two groups per thread; the chunk's two rows
+        const int a = 2 * tid;
+        const int h0 = a < groups ? hist[a] : 0, h1 = a + 1 < groups ? hist[a + 1] : 0;
+        int all;
+        const int ex = block_inclusive_scan<kBinThreads / 64>(h0 + h1, &all) - h0 - h1;
+        int* crow = counts + (size_t)blockIdx.x * groups;
+        int* srow = starts + (size_t)blockIdx.x * groups;
+        if (a < groups) {
+            cursor[a] = ex;
+            crow[a] = sound ? h0 : 0;
+            srow[a] = chunk_base + ex;
+        }
+        if (a + 1 < groups) {
+            cursor[a + 1] = ex + h0;
+            crow[a + 1] = sound ? h1 : 0;
+            srow[a + 1] = chunk_base + ex + h0;
+        }
+    }
+    __syncthreads();
+    if (!sound) return;
+    int* dst = scratch + chunk_base;
+    if (pairs <= kStageCap) {
+        // ordered by group inside LDS first (every thread keeps its entries and their places in registers while the
+        // buffer changes hands), then copied out: consecutive lanes store consecutive words of the chunk's region.
+        // Straight from the staging order a wave's store touched up to 64 lines, 16 k such words in one burst
+        constexpr int kPer = kStageCap / kBinThreads;
+        static_assert(kStageCap % kBinThreads == 0, "whole staging rounds");
+        unsigned int w[kPer];
+        int at[kPer];
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            const int j = u * kBinThreads + tid;
+            if (j < pairs) {
+                w[u] = words[j];
+                at[u] = atomicAdd(&cursor[grp[j]], 1);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kPer; ++u)
+            if (u * kBinThreads + tid < pairs) words[at[u]] = w[u];
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            const int j = u * kBinThreads + tid;
+            if (j < pairs) dst[j] = (int)words[j];
+        }
+    } else {
+        walk_chunk(g0, g1, xys, radii, splats, cam, [&](int t, int i) {
+            dst[atomicAdd(&cursor[t >> kCoarseShift], 1)] = i | ((t & (kCoarseTiles - 1)) << kCoarseIdBits);
+        });
+    }
+}
+
+// Fine hop of the ONE WALK form: the group's entries are one run per chunk (starts[b][g], counts[b][g]) instead of one
+// region.  The run table goes to LDS (one chunk per thread, a workgroup scan of the lengths); a pass of kRunPass
+// entries is gathered into LDS by whole waves, a run at a time and kRunAhead runs in flight per wave, and from there
+// it is what bin_scatter_fine_groups_kernel does: count the 32 lists, publish tile_bins / tile_start / the group's
+// maximum, reorder by tile in LDS, store.  A group of more than one pass counts its lists from the runs first.
+#ifndef TS_RUN_AHEAD
+#define TS_RUN_AHEAD 20
+#endif
+constexpr int kRunItems = TS_RUN_AHEAD;                  // entries per thread and pass
+static_assert(kFineThreads * TS_RUN_AHEAD <= 65536, "16-bit ranks inside a pass");
+constexpr int kRunPass = kFineThreads * kRunItems;       // 20480 entries, 80 KiB: config 3's ~16 k per group in one pass
+                                                         // (24 items per thread spill registers at 1024 threads)
+#ifndef TS_RUNS_IN_FLIGHT
+#define TS_RUNS_IN_FLIGHT 8
+#endif
+constexpr int kRunAhead = TS_RUNS_IN_FLIGHT;             // runs a wave has in flight
+__global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_runs_kernel(
+    int num_tiles, int groups, int chunks, const int* __restrict__ counts, const int* __restrict__ starts,
+    int* __restrict__ tile_start, int* __restrict__ tile_bins, int* __restrict__ group_max,
+    const int* __restrict__ scratch, int* __restrict__ bucket_ids) {
+    extern __shared__ unsigned int buf[];                // kRunPass words: the pass, then the pass ordered by tile
+    // (the group's column of the two matrices is asked for before the guard word is looked at: stale words where the
+    // guard tripped, never used)
+    const int my_count = (int)threadIdx.x < chunks ? counts[(size_t)threadIdx.x * groups + blockIdx.x] : 0;
+    const int my_start = (int)threadIdx.x < chunks ? starts[(size_t)threadIdx.x * groups + blockIdx.x] : 0;
+    const int begin = tile_start[min(num_tiles, (int)(blockIdx.x << kCoarseShift))];
+    if (tile_start[num_tiles + 1] != 0) return;          // capacity guard: every list was emptied already
+    __shared__ int cursor[kCoarseTiles], hist[kCoarseTiles], loff[kCoarseTiles + 1], gbase[kCoarseTiles];
+    __shared__ int roff[kBinMaxChunks + 1], rsrc[kBinMaxChunks];
+    constexpr int kWaves = kFineThreads / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t0 = blockIdx.x << kCoarseShift, t1 = min(num_tiles, t0 + kCoarseTiles);
+    if (tid < kCoarseTiles) {
+        hist[tid] = 0;
+        cursor[tid] = 0;
+    }
+    int total;
+    {
+        const int c = my_count;
+        const int inc = block_inclusive_scan<kWaves>(c, &total);
+        if (tid < chunks) {
+            roff[tid] = inc - c;
+            rsrc[tid] = my_start;
+        }
+        if (tid == 0) roff[chunks] = total;
+    }
+    __syncthreads();
+    // wave 0, lane t: list t of the group has c entries, ex in the lists before it
+    auto publish = [&](int t, int c, int ex) {
+        const int s = begin + ex;
+        if (t < t1 - t0) {
+            cursor[t] = s;
+            if (t > 0) tile_start[t0 + t] = s;           // ([t0] is the group's start: there since the offsets launch)
+            reinterpret_cast<int2*>(tile_bins)[t0 + t] = c > 0 ? make_int2(s, s + c) : make_int2(0, 0);
+        }
+        int longest = c;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) longest = max(longest, __shfl_xor(longest, d, 64));
+        if (t == 0) group_max[blockIdx.x] = longest;
+    };
+    // the window [c0, c0 + m) of the group's entries, run by run: op(position in the window, scratch word)
+    auto for_runs = [&](int c0, int m, auto op) {
+#pragma unroll 1
+        for (int b0 = wave; b0 < chunks; b0 += kWaves * kRunAhead) {
+            int len[kRunAhead], src[kRunAhead], dst[kRunAhead];         // this lane's first entry of the run and what is left
+            unsigned int v[kRunAhead];
+#pragma unroll
+            for (int u = 0; u < kRunAhead; ++u) {
+                const int b = b0 + u * kWaves;
+                len[u] = src[u] = dst[u] = 0;
+                if (b < chunks) {
+                    const int o = roff[b], c = roff[b + 1] - o;
+                    const int lo = max(0, c0 - o) + lane;
+                    len[u] = min(c, c0 + m - o) - lo;
+                    src[u] = rsrc[b] + lo;
+                    dst[u] = o - c0 + lo;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kRunAhead; ++u)
+                if (len[u] > 0) v[u] = (unsigned int)scratch[src[u]];
+#pragma unroll
+            for (int u = 0; u < kRunAhead; ++u)
+                if (len[u] > 0) op(dst[u], v[u]);
+#pragma unroll
+            for (int u = 0; u < kRunAhead; ++u)
+                for (int j = 64; j < len[u]; j += 64) op(dst[u] + j, (unsigned int)scratch[src[u] + j]);
+        }
+    };
+    const bool counted = total > kRunPass || total == 0;
+    if (counted) {
+        for_runs(0, total, [&](int, unsigned int w) { atomicAdd(&hist[w >> kCoarseIdBits], 1); });
+        __syncthreads();
+        if (tid < 64) {
+            const int c = tid < kCoarseTiles ? hist[tid] : 0;
+            int inc = c;
+#pragma unroll
+            for (int d = 1; d < kCoarseTiles; d <<= 1) {
+                const int o = __shfl_up(inc, d, 64);
+                if (tid >= d) inc += o;
+            }
+            publish(tid, c, inc - c);
+            if (tid < kCoarseTiles) hist[tid] = 0;
+        }
+        __syncthreads();
+    }
+    for (int c0 = 0; c0 < total; c0 += kRunPass) {
+        const int m = min(kRunPass, total - c0);                      // entries of this pass
+        for_runs(c0, m, [&](int k, unsigned int w) { buf[k] = w; });
+        __syncthreads();
+        unsigned int w[kRunItems];
+        unsigned int rank2[(kRunItems + 1) / 2];                      // two 16-bit ranks per register (a rank is < kRunPass)
+#pragma unroll
+        for (int u = 0; u < (kRunItems + 1) / 2; ++u) rank2[u] = 0u;
+#pragma unroll
+        for (int u = 0; u < kRunItems; ++u) {
+            const int k = u * kFineThreads + tid;
+            if (k < m) w[u] = buf[k];
+        }
+#pragma unroll
+        for (int u = 0; u < kRunItems; ++u) {
+            const int k = u * kFineThreads + tid;
+            if (k < m) rank2[u / 2] |= (unsigned int)atomicAdd(&hist[w[u] >> kCoarseIdBits], 1) << (16 * (u & 1));
+        }
+        __syncthreads();
+        if (tid < 64) {                                               // one wave: offsets of the pass, bases, reset
+            const int c = tid < kCoarseTiles ? hist[tid] : 0;
+            int inc = c;                                              // inclusive scan over the first 32 lanes
+#pragma unroll
+            for (int d = 1; d < kCoarseTiles; d <<= 1) {
+                const int o = __shfl_up(inc, d, 64);
+                if (tid >= d) inc += o;
+            }
+            if (!counted) publish(tid, c, inc - c);                   // the only pass of the group: its counts are the lists'
+            if (tid < kCoarseTiles) {
+                loff[tid] = inc - c;
+                gbase[tid] = cursor[tid];
+                cursor[tid] += c;
+                hist[tid] = 0;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kRunItems; ++u) {
+            const int k = u * kFineThreads + tid;
+            if (k < m) buf[loff[w[u] >> kCoarseIdBits] + (int)((rank2[u / 2] >> (16 * (u & 1))) & 0xffffu)] = w[u];   // (the tile travels with the id)
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kRunItems; ++u) {
+            const int k = u * kFineThreads + tid;
+            if (k < m) {
+                const unsigned int e = buf[k];
+                const int t = (int)(e >> kCoarseIdBits);
+                bucket_ids[gbase[t] + (k - loff[t])] = (int)(e & ((1u << kCoarseIdBits) - 1u));
+            }
+        }
+        __syncthreads();                                              // buf / loff are rewritten by the next pass
     }
 }
 
@@ -1252,7 +1591,7 @@ int ts_tile_offsets_stats(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t
     const int per_group = (chunks + kScanGroups - 1) / kScanGroups;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(column_scan_kernel, dim3((num_tiles + kColTiles - 1) / kColTiles),
-                       dim3(kColTiles * kScanGroups), 0, s, num_tiles, chunks, per_group, bin_ws, tile_total);
+                       dim3(kColTiles * kScanGroups), 0, s, num_tiles, chunks, per_group, bin_ws, tile_total, true);
     hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(kOffsetsThreads), 0, s, num_tiles, tile_total,
                        tile_bins, bin_ws + (ts_bin_ws_ints(n, num_tiles) - 1),
                        (cum_tiles_hit && n > 0) ? cum_tiles_hit + (n - 1) : nullptr, (long long)capacity, longest_list);
@@ -1289,15 +1628,15 @@ int ts_group_offsets(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* til
     // one workgroup scans the columns too while the B x G matrix is small (config 3: 245 x 255 ints = 250 KB);
     // beyond kGoSingleMax ints (config 5: 512 x 507) the columns get column_scan_kernel's many workgroups first
     if ((long long)chunks * groups <= kGoSingleMax && groups <= kGoLdsGroups) {
-        hipLaunchKernelGGL(group_tile_offsets_kernel, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups, chunks,
+        hipLaunchKernelGGL(group_tile_offsets_kernel<true>, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups, chunks,
                            bin_ws, (const int*)nullptr, tile_start, tile_bins, spare, total_ptr, (long long)capacity,
                            longest_list);
     } else {
         int* col_total = bin_ws + (size_t)chunks * groups;
         const int per_group = (chunks + kScanGroups - 1) / kScanGroups;
         hipLaunchKernelGGL(column_scan_kernel, dim3((groups + kColTiles - 1) / kColTiles),
-                           dim3(kColTiles * kScanGroups), 0, s, groups, chunks, per_group, bin_ws, col_total);
-        hipLaunchKernelGGL(group_tile_offsets_kernel, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups, chunks,
+                           dim3(kColTiles * kScanGroups), 0, s, groups, chunks, per_group, bin_ws, col_total, true);
+        hipLaunchKernelGGL(group_tile_offsets_kernel<true>, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups, chunks,
                            (int*)nullptr, (const int*)col_total, tile_start, tile_bins, spare, total_ptr,
                            (long long)capacity, longest_list);
     }
@@ -1328,6 +1667,73 @@ int ts_bin_scatter_groups(int32_t n, const float* xys, const int32_t* radii, con
                            (const int*)tile_start, scratch);
     hipLaunchKernelGGL(bin_scatter_fine_groups_kernel, dim3(groups), dim3(kFineThreads), 0, s, nt, tile_start,
                        tile_bins, bin_ws + nt + 1, (const int*)scratch, bucket_ids);
+    return launch_status();
+}
+
+int32_t ts_bin_one_walk_form(int32_t n, int32_t num_tiles) { return one_walk_form(n, num_tiles) ? 1 : 0; }
+
+int32_t ts_bin_stage_capacity(void) { return kStageCap; }
+
+int ts_bin_emit_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
+                       const ts_camera* cam, const int32_t* cum_tiles_hit, int64_t capacity, int32_t* bin_ws,
+                       int32_t* scratch, void* stream) {
+    if (!cam || !xys || !radii || !cum_tiles_hit || !bin_ws || !scratch) return TS_E_BADARG;
+    const int nt = ts_num_tiles(cam);
+    if (!one_walk_form(n, nt) || (cam->hints & TS_HINT_BALANCED_WALK)) return TS_E_BADARG;
+    const int chunks = bin_num_chunks(n);
+    const int chunk = (n + chunks - 1) / chunks;
+    const int groups = (nt + kCoarseTiles - 1) >> kCoarseShift;
+    const OneWalkLayout l = one_walk_layout(chunks, groups, nt);
+    const size_t lds = (size_t)groups * 8 + (size_t)kStageCap * 6;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_emit_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(bin_scatter_emit_kernel, dim3(chunks), dim3(kBinThreads), lds, (hipStream_t)stream, n, chunk,
+                       xys, radii, reinterpret_cast<const float4*>(splats), *cam, groups, cum_tiles_hit,
+                       (long long)capacity, bin_ws + l.counts, bin_ws + l.starts, scratch);
+    return launch_status();
+}
+
+int ts_emit_offsets(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins,
+                    const int32_t* cum_tiles_hit, int64_t capacity, int32_t* longest_list, void* stream) {
+    if (!one_walk_form(n, num_tiles) || !bin_ws || !tile_bins || !cum_tiles_hit) return TS_E_BADARG;
+    const int chunks = bin_num_chunks(n);
+    const int groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
+    const OneWalkLayout l = one_walk_layout(chunks, groups, num_tiles);
+    int* tile_start = bin_ws + (size_t)chunks * num_tiles;
+    int* spare = bin_ws + (ts_bin_ws_ints(n, num_tiles) - 1);
+    const int* total_ptr = cum_tiles_hit + (n - 1);
+    hipStream_t s = (hipStream_t)stream;
+    if ((long long)chunks * groups <= kGoSingleMax) {
+        hipLaunchKernelGGL(group_tile_offsets_kernel<false>, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups,
+                           chunks, bin_ws + l.counts, (const int*)nullptr, tile_start, tile_bins, spare, total_ptr,
+                           (long long)capacity, longest_list);
+    } else {
+        // (the column totals of a frame that tripped the guard are sums of stale words: the offsets launch never reads them)
+        int* col_total = bin_ws + l.col_total;
+        const int per_group = (chunks + kScanGroups - 1) / kScanGroups;
+        hipLaunchKernelGGL(column_scan_kernel, dim3((groups + kColTiles - 1) / kColTiles),
+                           dim3(kColTiles * kScanGroups), 0, s, groups, chunks, per_group, bin_ws + l.counts, col_total,
+                           false);
+        hipLaunchKernelGGL(group_tile_offsets_kernel<false>, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups,
+                           chunks, (int*)nullptr, (const int*)col_total, tile_start, tile_bins, spare, total_ptr,
+                           (long long)capacity, longest_list);
+    }
+    return launch_status();
+}
+
+int ts_bin_gather_groups(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins, int32_t* bucket_ids,
+                         const int32_t* scratch, void* stream) {
+    if (!one_walk_form(n, num_tiles) || !bin_ws || !tile_bins || !bucket_ids || !scratch) return TS_E_BADARG;
+    const int chunks = bin_num_chunks(n);
+    const int groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
+    const OneWalkLayout l = one_walk_layout(chunks, groups, num_tiles);
+    int* tile_start = bin_ws + (size_t)chunks * num_tiles;
+    const size_t lds = (size_t)kRunPass * sizeof(int);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_fine_runs_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(bin_scatter_fine_runs_kernel, dim3(groups), dim3(kFineThreads), lds, (hipStream_t)stream,
+                       num_tiles, groups, chunks, (const int*)(bin_ws + l.counts), (const int*)(bin_ws + l.starts),
+                       tile_start, tile_bins, bin_ws + num_tiles + 1, scratch, bucket_ids);
     return launch_status();
 }
 

@@ -122,6 +122,12 @@ inline bool survivors(const ts_frame* f) {
 inline bool group_counts(const ts_frame* f) {
     return (f->flags & TS_FRAME_GROUP_COUNTS) && !(f->flags & TS_FRAME_DIRECT_SCATTER) && ts_bin_group_form(f->n);
 }
+// ONE WALK (TS_FRAME_ONE_WALK): a group-form frame whose lists are built from one walk of the Gaussians - all of it in
+// _composite (emit, offsets, fine hop); _prepare enqueues the colour stage alone.  One predicate for both calls
+inline bool one_walk(const ts_frame* f) {
+    return (f->flags & TS_FRAME_ONE_WALK) && group_counts(f) && !(f->cam.hints & TS_HINT_BALANCED_WALK) &&
+           ts_bin_one_walk_form(f->n, num_tiles(f));
+}
 // TS_FRAME_LIST_STATS: the word behind the count word, or null
 inline int32_t* longest_word(const ts_frame* f) {
     if ((f->flags & TS_FRAME_LIST_STATS) && f->total_host) {
@@ -180,6 +186,7 @@ int ts_frame_fwd_prepare(const ts_frame* f, void* stream) {
                                        TS_RASTER_LOGIT_OPACITY, f->xys, f->radii, f->conics, f->opacities,
                                        f->cum_tiles_hit, &f->cam, f->channels == 4 ? f->depths : nullptr, f->splats,
                                        stream)));
+    if (one_walk(f)) return 0;          // the lists are _composite's work, offsets included
     const float* tight = (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr;
     // (TS_FRAME_LIST_STATS: the longest list goes to the word behind the count word - read a frame later by the caller's
     // launch policy, never waited for)
@@ -209,11 +216,26 @@ int ts_frame_fwd_composite(const ts_frame* f, void* stream) {
     // entries itself
     const bool fused_sort = f->num_intersects > 0 && f->cam.wide_tiles == 0 &&
                             !(f->flags & (TS_FRAME_NARROW_WAVES | TS_FRAME_SEPARATE_SORT));
+    const bool walk_once = one_walk(f);
+    if (walk_once) {
+        // (also for a frame without intersections: the offsets launch is what empties its lists)
+        const float* tight = (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr;
+        TS_TRY(TS_ENTRY("ts_bin_scatter",
+                        ts_bin_emit_groups(f->n, f->xys, f->radii, tight, &f->cam, f->cum_tiles_hit, f->capacity,
+                                           f->bin_ws, f->gaussian_ids_sorted, stream)));
+        TS_TRY(TS_ENTRY("ts_tile_offsets",
+                        ts_emit_offsets(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->cum_tiles_hit, f->capacity,
+                                        longest_word(f), stream)));
+    }
     if (f->num_intersects > 0) {
         const float* tight = (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr;
         // the sorted-id buffer is dead until the sort: it carries the ids between the two scatter hops
         const bool groups = group_counts(f);
-        if (groups)
+        if (walk_once)
+            TS_TRY(TS_ENTRY("ts_bin_scatter",
+                            ts_bin_gather_groups(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->bucket_ids,
+                                                 f->gaussian_ids_sorted, stream)));
+        else if (groups)
             TS_TRY(TS_ENTRY("ts_bin_scatter",
                             ts_bin_scatter_groups(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, f->tile_bins,
                                                   f->bucket_ids, f->gaussian_ids_sorted, stream)));

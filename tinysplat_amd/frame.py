@@ -300,6 +300,12 @@ SURVIVORS = os.environ.get("TS_SURVIVORS", "1") != "0"
 # TS_GROUP_COUNTS=0: the B x T count matrix for every frame.
 GROUP_COUNTS = os.environ.get("TS_GROUP_COUNTS", "1") != "0"
 
+# ONE WALK (TS_FRAME_ONE_WALK, csrc/binning.hip): a group-form frame builds its lists from one walk of the Gaussians - the
+# emit launch stages every chunk's pairs in LDS and writes them to the chunk's own bounding-box slots, the fine hop
+# gathers a group's runs.  All of it is enqueued by ts_frame_fwd_composite.  Same lists, same frame, bit for bit.
+# TS_ONE_WALK=0: the group form.
+ONE_WALK = os.environ.get("TS_ONE_WALK", "1") != "0"
+
 # CAPACITY ALLOCATION (option, off by default): the per-intersection buffers (bucket_ids | gaussian_ids_sorted;
 # partials in backward) are sized by the bounding-box pair count I, which only the GPU knows (gsplat synchronises
 # for it at the same place, rasterize.py:44).  With TS_CAPACITY_ALLOC=1, from the second frame of a (scene size,
@@ -466,6 +472,8 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
             fr.flags |= 512                                               # TS_FRAME_SURVIVORS
         if GROUP_COUNTS:
             fr.flags |= 1024                                              # TS_FRAME_GROUP_COUNTS (the executor decides where it applies)
+        if ONE_WALK:
+            fr.flags |= 2048                                              # TS_FRAME_ONE_WALK (the executor decides where it applies)
         if full:
             _stats_mode[dev.index] = mode
         fr.cam = cam
