@@ -251,7 +251,8 @@ int ts_sort_tiles_above(int32_t num_tiles, const int32_t* tile_bins, const float
  *                          bin_ws are those of ts_bin_scatter_groups, which left one maximum per group in bin_ws).
  *                          longest_list == NULL: n and bin_ws are ignored
  * All of them return TS_E_BADARG for an n the group form does not apply to.  The three stages of a frame must be taken
- * from the same form. */
+ * from the same form (the frame executor decides it in one place: list_form, csrc/frame.hip).  The fine hop is the same
+ * code in every form; the layout of bin_ws in all of them is described once, at BinGeometry in csrc/binning.hip. */
 int32_t ts_bin_group_form(int32_t n);
 int ts_bin_count_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
                         const ts_camera* cam_host, int32_t* bin_ws, void* stream);
@@ -269,7 +270,8 @@ int ts_bin_scatter_groups(int32_t n, const float* xys, const int32_t* radii, con
  *   ts_bin_emit_groups     the walk.  Reads cum_tiles_hit[n-1] against capacity itself (it runs BEFORE the offsets) and
  *                          writes nothing when the guard would trip.  scratch: as for ts_bin_scatter_groups
  *   ts_emit_offsets        ts_group_offsets' duties except the bases; cum_tiles_hit not NULL
- *   ts_bin_gather_groups   the fine hop: tile_bins, the remaining tile starts, bucket_ids, one maximum per group
+ *   ts_bin_gather_groups   the fine hop (ts_bin_scatter_groups', fed run by run): tile_bins, the remaining tile starts,
+ *                          bucket_ids, one maximum per group
  * ts_bin_stage_capacity(): pairs a chunk can stage in LDS; a chunk that lists more walks twice inside its workgroup. */
 int32_t ts_bin_one_walk_form(int32_t n, int32_t num_tiles);
 int32_t ts_bin_stage_capacity(void);

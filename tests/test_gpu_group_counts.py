@@ -12,102 +12,18 @@ import pytest
 import torch
 
 from tinysplat_amd import _lib, frame, ops
-from tinysplat_amd.rasterizer import project_args, tile_bounds
+from tinysplat_amd.rasterizer import tile_bounds
 from tinysplat_amd.synthetic import make_scene
 
+from binning_cases import GROUP, H, MATRIX, N, SENTINEL, UNSET, W, projected as _projected, same as _same
+import binning_cases
 from test_gpu_survivors import _render
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-N = (1 << 18) + 77
-W, H = 400, 304
-SENTINEL = -1
-UNSET = -7
-_scenes = {}
 
 
-def _projected(clustered=0.0, n=N, tile_rows=None):
-    """2-D inputs of the binning stages (projection, scan, packed records for the tight lists), once per scene"""
-    key = (clustered, n, tile_rows)
-    if key not in _scenes:
-        lib = _lib.load()
-        dev = torch.device(DEV)
-        model, cam = make_scene(n, 0, W, H, seed=41, clustered=clustered)
-        md = model.to(dev)
-        with torch.no_grad():
-            xys, depths, radii, conics, nth, _ = ops.project_gaussians(*project_args(md, cam, (W, H), DEV),
-                                                                       tile_rows=tile_rows)
-            opac = torch.sigmoid(md.opacities).reshape(-1).contiguous()
-        colors = torch.rand(n, 3, generator=torch.Generator().manual_seed(2)).to(dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        s, p = ops._stream(dev), ops._ptr
-        cum = torch.empty((n,), **i32)
-        ws = torch.empty((int(lib.ts_scan_ws_ints(n)),), **i32)
-        ops._call("ts_scan_tiles", lib.ts_scan_tiles, n, p(nth), p(cum), p(ws), None, s)
-        splats = torch.zeros((n, 12), dtype=torch.float32, device=dev)
-        cam16 = ops._camera(0.0, 0.0, 0.0, 0.0, H, W, tile_bounds((W, H)), tile_rows=tile_rows)
-        ops._call("ts_pack_splats", lib.ts_pack_splats, n, 3, 0, p(xys), p(radii), p(conics), p(colors), p(opac), p(cum),
-                  cam16, None, p(splats), s)
-        torch.cuda.synchronize()
-        _scenes[key] = dict(n=n, xys=xys, depths=depths, radii=radii, cum=cum, splats=splats, total=int(cum[-1]),
-                            tile_rows=tile_rows)
-    return _scenes[key]
-
-
-def _chain(inp, group, wide=False, hints=0, capacity=-1):
-    """the four list-building stages in one form -> everything a later stage or the host reads"""
-    lib = _lib.load()
-    dev = torch.device(DEV)
-    n, total = inp["n"], inp["total"]
-    cam = ops._camera(0.0, 0.0, 0.0, 0.0, H, W, tile_bounds((W, H)), tile_rows=inp["tile_rows"], wide_tiles=wide)
-    cam.hints = hints
-    nt = int(lib.ts_num_tiles(ctypes.byref(cam)))
-    i32 = dict(dtype=torch.int32, device=dev)
-    s, p = ops._stream(dev), ops._ptr
-    xys, rad, tl, depths, cum = inp["xys"], inp["radii"], p(inp["splats"]), inp["depths"], inp["cum"]
-    bin_ws = torch.full((int(lib.ts_bin_ws_ints(n, nt)),), UNSET, **i32)
-    tile_bins = torch.full((nt, 2), UNSET, **i32)
-    bucket_ids = torch.full((total,), SENTINEL, **i32)
-    ids = torch.full((total,), SENTINEL, **i32)
-    longest = torch.full((1,), UNSET, **i32)
-    spare = bin_ws.data_ptr() + 4 * (bin_ws.numel() - 1)
-    if group:
-        ops._call("ts_bin_count_groups", lib.ts_bin_count_groups, n, p(xys), p(rad), tl, cam, p(bin_ws), s)
-        ops._call("ts_group_offsets", lib.ts_group_offsets, n, nt, p(bin_ws), p(tile_bins), p(cum), capacity, p(longest), s)
-        ops._call("ts_bin_scatter_groups", lib.ts_bin_scatter_groups, n, p(xys), p(rad), tl, cam, p(bin_ws), p(tile_bins),
-                  p(bucket_ids), p(ids), s)
-        scattered = bucket_ids.clone()
-        ops._call("ts_sort_tiles_stats", lib.ts_sort_tiles_stats, nt, p(tile_bins), p(depths), p(bucket_ids), p(ids),
-                  p(bin_ws), spare, n, p(bin_ws), p(longest), s)
-    else:
-        ops._call("ts_bin_count", lib.ts_bin_count, n, p(xys), p(rad), tl, cam, p(bin_ws), s)
-        ops._call("ts_tile_offsets_stats", lib.ts_tile_offsets_stats, n, nt, p(bin_ws), p(tile_bins), p(cum), capacity,
-                  p(longest), s)
-        ops._call("ts_bin_scatter", lib.ts_bin_scatter, n, p(xys), p(rad), tl, cam, p(bin_ws), p(bucket_ids), p(ids), s)
-        scattered = bucket_ids.clone()
-        ops._call("ts_sort_tiles", lib.ts_sort_tiles, nt, p(tile_bins), p(depths), p(bucket_ids), p(ids), p(bin_ws),
-                  spare, s)
-    torch.cuda.synchronize()
-    bins = tile_bins.cpu()
-    listed = int(bins[:, 1].max())
-    assert 0 <= listed <= total
-    # tile_start[0..T] | guard | spare.  (ts_sort_tiles counts the lists beyond 4096 entries in the spare word: it is
-    # compared as it stands after the sort in both forms)
-    tail = bin_ws[-(nt + 3):].cpu()
-    return dict(bins=bins, ids=ids[:listed].cpu(), tail=tail, longest=int(longest), listed=listed, nt=nt,
-                scattered=scattered.cpu(), lens=(bins[:, 1] - bins[:, 0]))
-
-
-def _same(ref, got):
-    assert torch.equal(ref["bins"], got["bins"])
-    assert ref["listed"] == got["listed"] and torch.equal(ref["ids"], got["ids"])
-    assert torch.equal(ref["tail"], got["tail"])            # tile_start[0..T], guard word, spare word
-    assert int(ref["tail"][-2]) == 0
-    want = int(ref["lens"].max())
-    assert ref["longest"] == want and got["longest"] == want
-    # the scatter filled exactly the listed part of bucket_ids (the order inside a bucket is arbitrary until the sort)
-    for r in (ref, got):
-        assert int(r["scattered"][:r["listed"]].min()) >= 0 and bool((r["scattered"][r["listed"]:] == SENTINEL).all())
+def _chain(inp, group, **kw):
+    return binning_cases.chain(inp, GROUP if group else MATRIX, **kw)
 
 
 def test_predicate_and_refusals():

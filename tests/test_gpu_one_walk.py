@@ -12,114 +12,18 @@ import pytest
 import torch
 
 from tinysplat_amd import _lib, frame, ops
-from tinysplat_amd.rasterizer import project_args, tile_bounds
+from tinysplat_amd.rasterizer import tile_bounds
 from tinysplat_amd.synthetic import make_scene
 
+from binning_cases import GROUP, H, N, SENTINEL, UNSET, W, WALK, chunks as _chunks, projected as _projected, same as _same
+import binning_cases
 from test_gpu_survivors import _render
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-N = (1 << 18) + 77
-W, H = 400, 304
-SENTINEL = -1
-UNSET = -7
-_scenes = {}
 
 
-def _chunks(n):
-    """bin_num_chunks of csrc/binning.hip -> (chunks, Gaussians per chunk)"""
-    per = min(max(n // 192, 1024), 4096)
-    b = min(max((n + per - 1) // per, 1), 512)
-    return b, (n + b - 1) // b
-
-
-def _projected(clustered=0.0, tile_rows=None, enlarge=None, dims=(W, H)):
-    """2-D inputs of the binning stages (projection, scan, packed records for the tight lists), once per scene.
-    enlarge = (share, factor): the first `share` of the Gaussians get `factor` times the extent"""
-    key = (clustered, tile_rows, enlarge, dims)
-    if key not in _scenes:
-        lib = _lib.load()
-        dev = torch.device(DEV)
-        w, h = dims
-        model, cam = make_scene(N, 0, w, h, seed=41, clustered=clustered)
-        if enlarge:
-            with torch.no_grad():
-                model.scales[:int(N * enlarge[0])] += torch.log(torch.tensor(float(enlarge[1])))
-        md = model.to(dev)
-        with torch.no_grad():
-            xys, depths, radii, conics, nth, _ = ops.project_gaussians(*project_args(md, cam, (w, h), DEV),
-                                                                       tile_rows=tile_rows)
-            opac = torch.sigmoid(md.opacities).reshape(-1).contiguous()
-        colors = torch.rand(N, 3, generator=torch.Generator().manual_seed(2)).to(dev)
-        s, p = ops._stream(dev), ops._ptr
-        cum = torch.empty((N,), dtype=torch.int32, device=dev)
-        ws = torch.empty((int(lib.ts_scan_ws_ints(N)),), dtype=torch.int32, device=dev)
-        ops._call("ts_scan_tiles", lib.ts_scan_tiles, N, p(nth), p(cum), p(ws), None, s)
-        splats = torch.zeros((N, 12), dtype=torch.float32, device=dev)
-        cam16 = ops._camera(0.0, 0.0, 0.0, 0.0, h, w, tile_bounds((w, h)), tile_rows=tile_rows)
-        ops._call("ts_pack_splats", lib.ts_pack_splats, N, 3, 0, p(xys), p(radii), p(conics), p(colors), p(opac), p(cum),
-                  cam16, None, p(splats), s)
-        torch.cuda.synchronize()
-        _scenes[key] = dict(xys=xys, depths=depths, radii=radii, cum=cum, splats=splats, total=int(cum[-1]),
-                            tile_rows=tile_rows, dims=dims)
-    return _scenes[key]
-
-
-def _chain(inp, walk, wide=False, capacity=-1):
-    """the list-building stages in the group form or the one-walk form -> everything a later stage or the host reads"""
-    lib = _lib.load()
-    dev = torch.device(DEV)
-    total = inp["total"]
-    w, h = inp["dims"]
-    cam = ops._camera(0.0, 0.0, 0.0, 0.0, h, w, tile_bounds((w, h)), tile_rows=inp["tile_rows"], wide_tiles=wide)
-    nt = int(lib.ts_num_tiles(ctypes.byref(cam)))
-    i32 = dict(dtype=torch.int32, device=dev)
-    s, p = ops._stream(dev), ops._ptr
-    xys, rad, tl, depths, cum = inp["xys"], inp["radii"], p(inp["splats"]), inp["depths"], inp["cum"]
-    bin_ws = torch.full((int(lib.ts_bin_ws_ints(N, nt)),), UNSET, **i32)
-    tile_bins = torch.full((nt, 2), UNSET, **i32)
-    bucket_ids = torch.full((total,), SENTINEL, **i32)
-    ids = torch.full((total,), SENTINEL, **i32)
-    longest = torch.full((1,), UNSET, **i32)
-    spare = bin_ws.data_ptr() + 4 * (bin_ws.numel() - 1)
-    matrix = None
-    if walk:
-        assert lib.ts_bin_one_walk_form(N, nt) == 1
-        ops._call("ts_bin_emit_groups", lib.ts_bin_emit_groups, N, p(xys), p(rad), tl, cam, p(cum), capacity, p(bin_ws),
-                  p(ids), s)
-        ops._call("ts_emit_offsets", lib.ts_emit_offsets, N, nt, p(bin_ws), p(tile_bins), p(cum), capacity, p(longest), s)
-        staged = ids.clone()
-        ops._call("ts_bin_gather_groups", lib.ts_bin_gather_groups, N, nt, p(bin_ws), p(tile_bins), p(bucket_ids), p(ids), s)
-    else:
-        ops._call("ts_bin_count_groups", lib.ts_bin_count_groups, N, p(xys), p(rad), tl, cam, p(bin_ws), s)
-        b, g = _chunks(N)[0], (nt + 31) // 32
-        matrix = bin_ws[:b * g].view(b, g).cpu()                  # pairs per (chunk, group), before they become bases
-        ops._call("ts_group_offsets", lib.ts_group_offsets, N, nt, p(bin_ws), p(tile_bins), p(cum), capacity, p(longest), s)
-        ops._call("ts_bin_scatter_groups", lib.ts_bin_scatter_groups, N, p(xys), p(rad), tl, cam, p(bin_ws), p(tile_bins),
-                  p(bucket_ids), p(ids), s)
-        staged = ids.clone()
-    scattered = bucket_ids.clone()
-    ops._call("ts_sort_tiles_stats", lib.ts_sort_tiles_stats, nt, p(tile_bins), p(depths), p(bucket_ids), p(ids),
-              p(bin_ws), spare, N, p(bin_ws), p(longest), s)
-    torch.cuda.synchronize()
-    bins = tile_bins.cpu()
-    listed = int(bins[:, 1].max())
-    assert 0 <= listed <= total
-    tail = bin_ws[-(nt + 3):].cpu()                               # tile_start[0..T] | guard | spare
-    return dict(bins=bins, ids=ids[:listed].cpu(), tail=tail, longest=int(longest), listed=listed, nt=nt,
-                scattered=scattered.cpu(), staged=staged.cpu(), lens=(bins[:, 1] - bins[:, 0]), matrix=matrix)
-
-
-def _same(ref, got):
-    assert torch.equal(ref["bins"], got["bins"])
-    assert ref["listed"] == got["listed"] and torch.equal(ref["ids"], got["ids"])
-    assert torch.equal(ref["tail"], got["tail"])            # tile_start[0..T], guard word, spare word
-    assert int(ref["tail"][-2]) == 0
-    want = int(ref["lens"].max())
-    assert ref["longest"] == want and got["longest"] == want
-    # the scatter filled exactly the listed part of bucket_ids (the order inside a bucket is arbitrary until the sort)
-    for r in (ref, got):
-        assert int(r["scattered"][:r["listed"]].min()) >= 0 and bool((r["scattered"][r["listed"]:] == SENTINEL).all())
+def _chain(inp, walk, **kw):
+    return binning_cases.chain(inp, WALK if walk else GROUP, **kw)
 
 
 def _rows_fit_their_slots(inp, ref):

@@ -342,7 +342,6 @@ __device__ __forceinline__ void walk_chunk_balanced(int g0, int g1, const float*
 }
 
 // grid = (chunks, windows); counts[b * T + t]
-template <bool BAL>
 __global__ __launch_bounds__(kBinThreads) void bin_count_kernel(
     int n, int chunk, const float* __restrict__ xys, const int* __restrict__ radii,
     const float4* __restrict__ splats, const ts_camera cam, int num_tiles, int window,
@@ -357,8 +356,8 @@ __global__ __launch_bounds__(kBinThreads) void bin_count_kernel(
         t -= t0;
         if ((unsigned)t < (unsigned)tw) atomicAdd(&hist[t], 1);
     };
-    if (BAL) walk_chunk_balanced(g0, g1, xys, radii, splats, cam, emit);
-    else walk_chunk(g0, g1, xys, radii, splats, cam, emit);
+    // (the load-balanced walk does not pay for the count: 26 -> 28 us on config 3, 111 -> 149 us on config 5)
+    walk_chunk(g0, g1, xys, radii, splats, cam, emit);
     __syncthreads();
     int* dst = counts + (size_t)blockIdx.x * num_tiles + t0;
     for (int j = threadIdx.x; j < tw; j += kBinThreads) dst[j] = hist[j];
@@ -506,7 +505,7 @@ __global__ __launch_bounds__(kBinThreads) void bin_scatter_kernel(
 //           entries for it form one run of ~64 words;
 //   fine    one workgroup per group streams its region and places the ids in the tiles' buckets with LDS
 //           cursors: all of a bucket's lines are written by one workgroup, merge in one L2 and leave as full lines.
-// Three forms of these launches exist, chosen per frame (frame.hip asks one predicate per form):
+// Three forms of these launches exist, chosen per frame (frame.hip: list_form); the fine hop is one piece of code:
 //   matrix    bin_count -> column_scan + tile_offsets -> scatter (direct, or coarse + fine): B x T counts
 //   group     group_bin_count -> group_tile_offsets -> coarse<.., true> + fine_groups: B x G counts, two walks
 //   one walk  emit -> group_tile_offsets<false> -> fine_runs: B x G counts and run starts, ONE walk; the coarse hop's
@@ -532,11 +531,7 @@ static_assert(kTwoHopFrom >= 4096, "the group form's workspace layout needs bin_
 // consumes a base per (chunk, tile GROUP), and the fine hop streams the whole region of its group anyway - it can
 // count its 32 lists itself.  So nobody needs the B x T matrix: the histogram has one counter per group of
 // kCoarseTiles lists and the matrix is B x G (250 KB instead of 8 MB on a 1080p frame of 1 M Gaussians), written
-// once, scanned by one workgroup, read once.  Workspace in this form:
-//   bin_ws[0 .. B*G)            counts -> bases (dead once the coarse hop has run)
-//   bin_ws[B*G .. B*G + G)      column totals where the columns are scanned by a launch of their own
-//   bin_ws[T+1 .. T+1+G)        longest list of every group (fine hop; behind the T + 1 words ts_sort_tiles may use)
-//   bin_ws[B*T ..]              tile_start[T + 1] | guard | spare: where the matrix form has them, same meaning
+// once, scanned by one workgroup, read once (the workspace: BinGeometry below).
 // counts[b * groups + g]; same walk, same TightTest, same list index as bin_count_kernel.
 __global__ __launch_bounds__(kBinThreads) void group_bin_count_kernel(
     int n, int chunk, const float* __restrict__ xys, const int* __restrict__ radii,
@@ -714,86 +709,158 @@ __global__ __launch_bounds__(kBinThreads) void bin_scatter_coarse_kernel(
 constexpr int kFineThreads = TS_FINE_THREADS;
 constexpr int kFineAhead = TS_FINE_AHEAD;
 constexpr int kFinePass = kFineThreads * kFineAhead;     // entries handled together
-// Fine hop: one workgroup per tile group streams the group's region in passes of kFinePass entries.  A pass is
-// reordered by tile in LDS before it is written (rank inside the tile from a returning LDS atomic, tile offsets
-// from a 32-entry scan), so that consecutive lanes store consecutive words of one bucket: with one 4-byte store
-// per entry straight from the stream a wave's store touched ~32 different lines, and the kernel was bound by
-// those write transactions (137 us for 250 MB on config 5), not by bytes.  The order inside a bucket is
-// arbitrary, as before; ts_sort_tiles follows.
+// THE FINE HOP: one workgroup per tile group takes the group's entries in passes.  A pass is reordered by tile in LDS
+// before it is written (rank inside the tile from a returning LDS atomic, tile offsets from a 32-entry scan), so that
+// consecutive lanes store consecutive words of one bucket: with one 4-byte store per entry straight from the stream a
+// wave's store touched ~32 different lines, and the kernel was bound by those write transactions (137 us for 250 MB on
+// config 5), not by bytes.  The order inside a bucket is arbitrary, as before; ts_sort_tiles follows.
+// The three kernels of the hop (one per form) share everything below and differ in two things only:
+//   where the entries come from   one contiguous region of the scratch buffer (matrix and group forms), or one run per
+//                                 chunk (one walk)
+//   where the cursors come from   tile_start, which tile_offsets_kernel filled (matrix form), or the kernel's own count:
+//                                 the tile-in-group sits in the top kCoarseShift bits of every scratch word, so the
+//                                 workgroup counts its 32 lists, scans the counts and PUBLISHES what tile_offsets_kernel
+//                                 publishes in the matrix form - tile_bins[t] ((0, 0) for an empty list), tile_start[t] -
+//                                 plus the group's longest list.  A group of one pass is counted by the placing pass
+//                                 itself (one read); a longer one is streamed twice (the second time out of the L2)
+constexpr unsigned int kCoarseIdMask = (1u << kCoarseIdBits) - 1u;
+struct FineGroup {                                       // LDS of a fine-hop workgroup beside the pass itself
+    int cursor[kCoarseTiles];                            // next free word of every bucket of the group
+    int hist[kCoarseTiles];                              // entries per list: of the group while it is counted, of a pass while it is placed
+    int loff[kCoarseTiles + 1];                          // where a list's entries start in the reordered pass ...
+    int gbase[kCoarseTiles];                             // ... and in bucket_ids
+};
+struct GroupLists {                                      // what a workgroup that counts its lists itself publishes
+    int t0, t1, begin;                                   // the group's lists, and where its entries begin in bucket_ids
+    int* tile_start;
+    int* tile_bins;
+    int* group_max;
+};
+
+// wave 0, lane t: c = entries of list t (0 beyond the 32 lists) -> entries of the lists before it
+__device__ __forceinline__ int scan_lists(const int* hist, int t, int& c) {
+    c = t < kCoarseTiles ? hist[t] : 0;
+    int inc = c;                                         // inclusive scan over the first 32 lanes
+#pragma unroll
+    for (int d = 1; d < kCoarseTiles; d <<= 1) {
+        const int o = __shfl_up(inc, d, 64);
+        if (t >= d) inc += o;
+    }
+    return inc - c;
+}
+
+// wave 0, lane t: list t of the group has c entries, ex in the lists before it
+__device__ __forceinline__ void publish_lists(FineGroup& sh, const GroupLists& g, int t, int c, int ex) {
+    const int s = g.begin + ex;
+    if (t < g.t1 - g.t0) {
+        sh.cursor[t] = s;
+        if (t > 0) g.tile_start[g.t0 + t] = s;           // ([t0] is the group's start: there since the offsets launch)
+        reinterpret_cast<int2*>(g.tile_bins)[g.t0 + t] = c > 0 ? make_int2(s, s + c) : make_int2(0, 0);
+    }
+    int longest = c;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) longest = max(longest, __shfl_xor(longest, d, 64));
+    if (t == 0) g.group_max[blockIdx.x] = longest;
+}
+
+// a group counted ahead of its placing passes: sh.hist holds the lists' counts
+__device__ __forceinline__ void publish_counted(FineGroup& sh, const GroupLists& g) {
+    __syncthreads();
+    if ((int)threadIdx.x < 64) {
+        int c;
+        const int ex = scan_lists(sh.hist, threadIdx.x, c);
+        publish_lists(sh, g, threadIdx.x, c, ex);
+        if ((int)threadIdx.x < kCoarseTiles) sh.hist[threadIdx.x] = 0;
+    }
+    __syncthreads();
+}
+
+// The ranks of a thread's ITEMS entries inside their lists while a pass is placed: two 16-bit ranks per register (a
+// rank is < 65536: place_pass asserts the pass size)
+template <int ITEMS>
+struct PassRanks {
+    unsigned int r[(ITEMS + 1) / 2];
+    __device__ __forceinline__ PassRanks() {
+#pragma unroll
+        for (int u = 0; u < (ITEMS + 1) / 2; ++u) r[u] = 0u;
+    }
+    __device__ __forceinline__ void set(int u, int v) { r[u / 2] |= (unsigned int)v << (16 * (u & 1)); }
+    __device__ __forceinline__ int get(int u) const { return (int)((r[u / 2] >> (16 * (u & 1))) & 0xffffu); }
+};
+
+// Places one pass of m <= ITEMS * kFineThreads entries, load(k) being entry k: rank inside the list by LDS atomic, the
+// pass's offsets per list, the lists' cursors moved on, the pass reordered by tile in buf (LDS, one word per entry: the
+// tile travels with the id) and stored with consecutive lanes on consecutive words.  publish: the pass is the whole
+// group and its counts are the lists', published to g.  load may read buf (everything is loaded before anything is put).
+// One representation of a pass for all three kernels: measured against ids[] + tiles[] with a rank per register,
+// profiles/r20_one_fine_hop.txt.
+template <int ITEMS, typename Load>
+__device__ __forceinline__ void place_pass(FineGroup& sh, unsigned int* buf, int m, Load load, bool publish,
+                                           const GroupLists& g, int* __restrict__ bucket_ids) {
+    static_assert(ITEMS * kFineThreads <= 65536, "16-bit ranks inside a pass");
+    const int tid = threadIdx.x;
+    unsigned int w[ITEMS];
+    PassRanks<ITEMS> rank;
+#pragma unroll
+    for (int u = 0; u < ITEMS; ++u) {
+        const int k = u * kFineThreads + tid;
+        if (k < m) w[u] = load(k);
+    }
+#pragma unroll
+    for (int u = 0; u < ITEMS; ++u) {
+        const int k = u * kFineThreads + tid;
+        if (k < m) rank.set(u, atomicAdd(&sh.hist[w[u] >> kCoarseIdBits], 1));
+    }
+    __syncthreads();
+    if (tid < 64) {                                                   // one wave: offsets of the pass, bases, reset
+        int c;
+        const int ex = scan_lists(sh.hist, tid, c);
+        if (publish) publish_lists(sh, g, tid, c, ex);
+        if (tid < kCoarseTiles) {
+            sh.loff[tid] = ex;
+            sh.gbase[tid] = sh.cursor[tid];
+            sh.cursor[tid] += c;
+            sh.hist[tid] = 0;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < ITEMS; ++u) {
+        const int k = u * kFineThreads + tid;
+        if (k < m) buf[sh.loff[w[u] >> kCoarseIdBits] + rank.get(u)] = w[u];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < ITEMS; ++u) {
+        const int k = u * kFineThreads + tid;
+        if (k < m) {
+            const unsigned int e = buf[k];
+            const int t = (int)(e >> kCoarseIdBits);
+            bucket_ids[sh.gbase[t] + (k - sh.loff[t])] = (int)(e & kCoarseIdMask);
+        }
+    }
+    __syncthreads();                                                  // buf and loff are rewritten by the next pass
+}
+
+// Fine hop of the MATRIX form: a linear region, cursors from tile_start.
 __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_kernel(int num_tiles,
                                                                         const int* __restrict__ tile_start,
                                                                         const int* __restrict__ scratch,
                                                                         int* __restrict__ bucket_ids) {
-    __shared__ int cursor[kCoarseTiles];                 // next free word of every bucket of the group
+    __shared__ FineGroup sh;
+    __shared__ unsigned int buf[kFinePass];
     const int t0 = blockIdx.x << kCoarseShift, t1 = min(num_tiles, t0 + kCoarseTiles);
-    if ((int)threadIdx.x < t1 - t0) cursor[threadIdx.x] = tile_start[t0 + threadIdx.x];
+    if ((int)threadIdx.x < t1 - t0) sh.cursor[threadIdx.x] = tile_start[t0 + threadIdx.x];
     const int begin = tile_start[t0], end = tile_start[t1];
-    __shared__ int hist[kCoarseTiles], loff[kCoarseTiles + 1], gbase[kCoarseTiles];
-    __shared__ int ids[kFinePass];
-    __shared__ unsigned char tiles[kFinePass];
-    if ((int)threadIdx.x < kCoarseTiles) hist[threadIdx.x] = 0;
+    if ((int)threadIdx.x < kCoarseTiles) sh.hist[threadIdx.x] = 0;
     __syncthreads();
-    for (int c0 = begin; c0 < end; c0 += kFinePass) {
-        const int m = min(kFinePass, end - c0);                       // entries of this pass
-        unsigned int w[kFineAhead];
-        int rank[kFineAhead];
-#pragma unroll
-        for (int u = 0; u < kFineAhead; ++u) {
-            const int k = u * kFineThreads + (int)threadIdx.x;
-            if (k < m) w[u] = (unsigned int)scratch[c0 + k];
-        }
-#pragma unroll
-        for (int u = 0; u < kFineAhead; ++u) {
-            const int k = u * kFineThreads + (int)threadIdx.x;
-            if (k < m) rank[u] = atomicAdd(&hist[w[u] >> kCoarseIdBits], 1);
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < 64) {                                  // one wave: offsets of the pass, bases, reset
-            const int t = threadIdx.x;
-            const int c = t < kCoarseTiles ? hist[t] : 0;
-            int inc = c;                                              // inclusive scan over the first 32 lanes
-#pragma unroll
-            for (int d = 1; d < kCoarseTiles; d <<= 1) {
-                const int o = __shfl_up(inc, d, 64);
-                if (t >= d) inc += o;
-            }
-            if (t < kCoarseTiles) {
-                loff[t] = inc - c;
-                gbase[t] = cursor[t];
-                cursor[t] += c;
-                hist[t] = 0;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kFineAhead; ++u) {
-            const int k = u * kFineThreads + (int)threadIdx.x;
-            if (k < m) {
-                const int t = (int)(w[u] >> kCoarseIdBits);
-                const int lp = loff[t] + rank[u];
-                ids[lp] = (int)(w[u] & ((1u << kCoarseIdBits) - 1u));
-                tiles[lp] = (unsigned char)t;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kFineAhead; ++u) {
-            const int k = u * kFineThreads + (int)threadIdx.x;
-            if (k < m) {
-                const int t = tiles[k];
-                bucket_ids[gbase[t] + (k - loff[t])] = ids[k];
-            }
-        }
-        __syncthreads();                                              // ids / tiles / loff are rewritten by the next pass
-    }
+    for (int c0 = begin; c0 < end; c0 += kFinePass)
+        place_pass<kFineAhead>(sh, buf, min(kFinePass, end - c0),
+                               [&](int k) { return (unsigned int)scratch[c0 + k]; }, false, GroupLists{}, bucket_ids);
 }
 
-// Fine hop of the GROUP form: the workgroup knows only where its group's region begins and ends (tile_start at the
-// group boundaries, group_tile_offsets_kernel); the tile-in-group sits in the top kCoarseShift bits of every scratch
-// word, so it counts its lists itself, scans the 32 counts and publishes what tile_offsets_kernel publishes in the
-// matrix form - tile_bins[t] ((0, 0) for an empty list), tile_start[t] - plus the group's longest list, then places
-// the ids exactly as bin_scatter_fine_kernel does.  A region of up to kFinePass entries is counted by the placing
-// pass itself (one read); a longer one is streamed twice (the second time out of the L2 the coarse hop filled).
+// Fine hop of the GROUP form: a linear region of which the workgroup knows only where it begins and ends (tile_start at
+// the group boundaries, group_tile_offsets_kernel); it counts its lists itself.
 __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_groups_kernel(int num_tiles,
                                                                                int* __restrict__ tile_start,
                                                                                int* __restrict__ tile_bins,
@@ -801,30 +868,16 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_groups_kernel(i
                                                                                const int* __restrict__ scratch,
                                                                                int* __restrict__ bucket_ids) {
     if (tile_start[num_tiles + 1] != 0) return;          // capacity guard: every list was emptied already
-    __shared__ int cursor[kCoarseTiles];                 // next free word of every bucket of the group
+    __shared__ FineGroup sh;
+    __shared__ unsigned int buf[kFinePass];
     const int t0 = blockIdx.x << kCoarseShift, t1 = min(num_tiles, t0 + kCoarseTiles);
     const int begin = tile_start[t0], end = tile_start[t1];
-    __shared__ int hist[kCoarseTiles], loff[kCoarseTiles + 1], gbase[kCoarseTiles];
-    __shared__ int ids[kFinePass];
-    __shared__ unsigned char tiles[kFinePass];
     if ((int)threadIdx.x < kCoarseTiles) {
-        hist[threadIdx.x] = 0;
-        cursor[threadIdx.x] = 0;
+        sh.hist[threadIdx.x] = 0;
+        sh.cursor[threadIdx.x] = 0;
     }
     __syncthreads();
-    // wave 0, lane t: list t of the group has c entries, ex in the lists before it
-    auto publish = [&](int t, int c, int ex) {
-        const int s = begin + ex;
-        if (t < t1 - t0) {
-            cursor[t] = s;
-            if (t > 0) tile_start[t0 + t] = s;           // ([t0] is the group's start: there since the offsets launch)
-            reinterpret_cast<int2*>(tile_bins)[t0 + t] = c > 0 ? make_int2(s, s + c) : make_int2(0, 0);
-        }
-        int longest = c;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) longest = max(longest, __shfl_xor(longest, d, 64));
-        if (t == 0) group_max[blockIdx.x] = longest;
-    };
+    const GroupLists lists{t0, t1, begin, tile_start, tile_bins, group_max};
     const bool counted = end - begin > kFinePass || end == begin;
     if (counted) {
         for (int c0 = begin; c0 < end; c0 += kFinePass) {
@@ -838,78 +891,14 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_groups_kernel(i
 #pragma unroll
             for (int u = 0; u < kFineAhead; ++u) {
                 const int k = u * kFineThreads + (int)threadIdx.x;
-                if (k < m) atomicAdd(&hist[w[u] >> kCoarseIdBits], 1);
+                if (k < m) atomicAdd(&sh.hist[w[u] >> kCoarseIdBits], 1);
             }
         }
-        __syncthreads();
-        if ((int)threadIdx.x < 64) {
-            const int t = threadIdx.x;
-            const int c = t < kCoarseTiles ? hist[t] : 0;
-            int inc = c;
-#pragma unroll
-            for (int d = 1; d < kCoarseTiles; d <<= 1) {
-                const int o = __shfl_up(inc, d, 64);
-                if (t >= d) inc += o;
-            }
-            publish(t, c, inc - c);
-            if (t < kCoarseTiles) hist[t] = 0;
-        }
-        __syncthreads();
+        publish_counted(sh, lists);
     }
-    for (int c0 = begin; c0 < end; c0 += kFinePass) {
-        const int m = min(kFinePass, end - c0);                       // entries of this pass
-        unsigned int w[kFineAhead];
-        int rank[kFineAhead];
-#pragma unroll
-        for (int u = 0; u < kFineAhead; ++u) {
-            const int k = u * kFineThreads + (int)threadIdx.x;
-            if (k < m) w[u] = (unsigned int)scratch[c0 + k];
-        }
-#pragma unroll
-        for (int u = 0; u < kFineAhead; ++u) {
-            const int k = u * kFineThreads + (int)threadIdx.x;
-            if (k < m) rank[u] = atomicAdd(&hist[w[u] >> kCoarseIdBits], 1);
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < 64) {                                  // one wave: offsets of the pass, bases, reset
-            const int t = threadIdx.x;
-            const int c = t < kCoarseTiles ? hist[t] : 0;
-            int inc = c;                                              // inclusive scan over the first 32 lanes
-#pragma unroll
-            for (int d = 1; d < kCoarseTiles; d <<= 1) {
-                const int o = __shfl_up(inc, d, 64);
-                if (t >= d) inc += o;
-            }
-            if (!counted) publish(t, c, inc - c);                     // the only pass of the region: its counts are the lists'
-            if (t < kCoarseTiles) {
-                loff[t] = inc - c;
-                gbase[t] = cursor[t];
-                cursor[t] += c;
-                hist[t] = 0;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kFineAhead; ++u) {
-            const int k = u * kFineThreads + (int)threadIdx.x;
-            if (k < m) {
-                const int t = (int)(w[u] >> kCoarseIdBits);
-                const int lp = loff[t] + rank[u];
-                ids[lp] = (int)(w[u] & ((1u << kCoarseIdBits) - 1u));
-                tiles[lp] = (unsigned char)t;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kFineAhead; ++u) {
-            const int k = u * kFineThreads + (int)threadIdx.x;
-            if (k < m) {
-                const int t = tiles[k];
-                bucket_ids[gbase[t] + (k - loff[t])] = ids[k];
-            }
-        }
-        __syncthreads();                                              // ids / tiles / loff are rewritten by the next pass
-    }
+    for (int c0 = begin; c0 < end; c0 += kFinePass)
+        place_pass<kFineAhead>(sh, buf, min(kFinePass, end - c0),
+                               [&](int k) { return (unsigned int)scratch[c0 + k]; }, !counted, lists, bucket_ids);
 }
 
 // ONE WALK (ts_bin_emit_groups -> ts_emit_offsets -> ts_bin_gather_groups).  The group form still walks every chunk
@@ -919,11 +908,6 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_groups_kernel(i
 // reduce_partials relies on for its row slots), and the scratch buffer is sized by the bounding-box total.  So chunk b
 // writes its entries, ordered by group, contiguously from cum_tiles_hit[g0 - 1] on, and leaves two rows of B x G words:
 // how many entries it has per group and where each of those runs starts.  The fine hop gathers its group's runs.
-// Workspace in this form (the group form's words stay where they are):
-//   bin_ws[0 .. T+1)                what ts_sort_tiles may use
-//   bin_ws[T+1 .. T+1+G)            longest list of every group (fine hop)
-//   bin_ws[T+1+G ..)                counts[B][G] | starts[B][G] | column totals[G] (only with the column-scan launch)
-//   bin_ws[B*T ..]                  tile_start[T + 1] | guard | spare
 // During the walk an emitted pair bumps the chunk's per-group histogram and is appended to a staging buffer in LDS
 // (one LDS atomic per wave and emit step: the active lanes take consecutive slots).  A chunk that fits the buffer
 // scans the histogram and places the staged words; one that does not - the append notices, the histogram counts
@@ -937,24 +921,52 @@ static_assert((size_t)kStageCap * 6 + (size_t)kEmitMaxGroups * 8 <= 144 * 1024, 
 static_assert(kEmitMaxGroups <= 2 * kBinThreads && kEmitMaxGroups <= 65536, "two groups per thread, 16-bit group index");
 static_assert(kEmitMaxGroups <= kGoLdsGroups, "the offsets launch keeps the column totals in LDS");
 
-struct OneWalkLayout {
-    long long counts, starts, col_total, end;            // word offsets into bin_ws
+// THE WORKSPACE AND THE GEOMETRY of a frame's list building, derived once per entry from (n, num_tiles).  B chunks of
+// `chunk` Gaussians, T lists, G groups of kCoarseTiles lists; every member below that names a place is a word offset into
+// bin_ws, whose ts_bin_ws_ints(n, T) = (B + 1) T + 3 words are laid out as
+//   all forms   [B*T .. B*T + T]         tile_start[T + 1]: where every list starts, [T] = all entries
+//               [B*T + T + 1]            guard: set where the frame exceeds the caller's capacity (every list is left empty)
+//               [B*T + T + 2]            spare: zero behind the offsets launch; ts_sort_tiles' counter of oversized tiles
+//   matrix      [0 .. B*T)               counts[b][t] -> bases
+//   group       [0 .. B*G)               counts[b][g] -> bases (dead once the coarse hop has run)
+//               [B*G .. B*G + G)         group_totals: column totals where the columns are scanned by a launch of their own
+//   one walk    [T+1+G .. +B*G)          counts[b][g]: entries of chunk b in group g
+//               [.. +B*G)                starts[b][g]: where that run begins in the scratch buffer
+//               [.. +G) = rows_end       col_total (only with the column-scan launch)
+//   group and   [0 .. T+1)               what ts_sort_tiles may use (the bases are dead by then)
+//   one walk    [T+1 .. T+1+G)           group_max: longest list of every group (fine hop -> the sort launch, ListStats)
+// A two-hop frame has at least four chunks, so T + 1 + G words fit in front of tile_start; the one-walk rows fit where
+// one_walk_form says so.
+struct BinGeometry {
+    int chunks, chunk, groups;
+    long long tile_start, guard, spare;
+    long long group_totals, group_max;
+    long long counts, starts, col_total, rows_end;
 };
-__host__ __device__ inline OneWalkLayout one_walk_layout(int chunks, int groups, int num_tiles) {
-    OneWalkLayout l;
-    l.counts = (long long)num_tiles + 1 + groups;
-    l.starts = l.counts + (long long)chunks * groups;
-    l.col_total = l.starts + (long long)chunks * groups;
-    l.end = l.col_total + groups;
-    return l;
+inline BinGeometry bin_geometry(int n, int num_tiles) {
+    const long long nt = num_tiles < 0 ? 0 : num_tiles;
+    BinGeometry g;
+    g.chunks = bin_num_chunks(n);
+    g.chunk = n > 0 ? (n + g.chunks - 1) / g.chunks : 1;
+    g.groups = (int)((nt + kCoarseTiles - 1) >> kCoarseShift);
+    const long long rows = (long long)g.chunks * g.groups;
+    g.tile_start = g.chunks * nt;
+    g.guard = g.tile_start + nt + 1;
+    g.spare = g.guard + 1;
+    g.group_totals = rows;
+    g.group_max = nt + 1;
+    g.counts = g.group_max + g.groups;
+    g.starts = g.counts + rows;
+    g.col_total = g.starts + rows;
+    g.rows_end = g.col_total + g.groups;
+    return g;
 }
 // THE predicate of the one-walk form: a two-hop frame whose groups fit the emit launch's LDS and whose rows fit in
 // front of tile_start
 inline bool one_walk_form(int n, int num_tiles) {
     if (!two_hop(n) || num_tiles <= 0) return false;
-    const int groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
-    const int chunks = bin_num_chunks(n);
-    return groups <= kEmitMaxGroups && one_walk_layout(chunks, groups, num_tiles).end <= (long long)chunks * num_tiles;
+    const BinGeometry g = bin_geometry(n, num_tiles);
+    return g.groups <= kEmitMaxGroups && g.rows_end <= g.tile_start;
 }
 
 __global__ __launch_bounds__(kBinThreads) void bin_scatter_emit_kernel(
@@ -1054,15 +1066,13 @@ __global__ __launch_bounds__(kBinThreads) void bin_scatter_emit_kernel(
 }
 
 // Fine hop of the ONE WALK form: the group's entries are one run per chunk (starts[b][g], counts[b][g]) instead of one
-// region.  The run table goes to LDS (one chunk per thread, a workgroup scan of the lengths); a pass of kRunPass
-// entries is gathered into LDS by whole waves, a run at a time and kRunAhead runs in flight per wave, and from there
-// it is what bin_scatter_fine_groups_kernel does: count the 32 lists, publish tile_bins / tile_start / the group's
-// maximum, reorder by tile in LDS, store.  A group of more than one pass counts its lists from the runs first.
+// region, and the workgroup counts its lists itself.  The run table goes to LDS (one chunk per thread, a workgroup scan of
+// the lengths); a pass of kRunPass entries is gathered into LDS by whole waves, a run at a time and kRunAhead runs in
+// flight per wave, and placed from there.  A group of more than one pass counts its lists from the runs first.
 #ifndef TS_RUN_AHEAD
 #define TS_RUN_AHEAD 20
 #endif
 constexpr int kRunItems = TS_RUN_AHEAD;                  // entries per thread and pass
-static_assert(kFineThreads * TS_RUN_AHEAD <= 65536, "16-bit ranks inside a pass");
 constexpr int kRunPass = kFineThreads * kRunItems;       // 20480 entries, 80 KiB: config 3's ~16 k per group in one pass
                                                          // (24 items per thread spill registers at 1024 threads)
 #ifndef TS_RUNS_IN_FLIGHT
@@ -1080,14 +1090,14 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_runs_kernel(
     const int my_start = (int)threadIdx.x < chunks ? starts[(size_t)threadIdx.x * groups + blockIdx.x] : 0;
     const int begin = tile_start[min(num_tiles, (int)(blockIdx.x << kCoarseShift))];
     if (tile_start[num_tiles + 1] != 0) return;          // capacity guard: every list was emptied already
-    __shared__ int cursor[kCoarseTiles], hist[kCoarseTiles], loff[kCoarseTiles + 1], gbase[kCoarseTiles];
+    __shared__ FineGroup sh;
     __shared__ int roff[kBinMaxChunks + 1], rsrc[kBinMaxChunks];
     constexpr int kWaves = kFineThreads / 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int t0 = blockIdx.x << kCoarseShift, t1 = min(num_tiles, t0 + kCoarseTiles);
     if (tid < kCoarseTiles) {
-        hist[tid] = 0;
-        cursor[tid] = 0;
+        sh.hist[tid] = 0;
+        sh.cursor[tid] = 0;
     }
     int total;
     {
@@ -1100,19 +1110,6 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_runs_kernel(
         if (tid == 0) roff[chunks] = total;
     }
     __syncthreads();
-    // wave 0, lane t: list t of the group has c entries, ex in the lists before it
-    auto publish = [&](int t, int c, int ex) {
-        const int s = begin + ex;
-        if (t < t1 - t0) {
-            cursor[t] = s;
-            if (t > 0) tile_start[t0 + t] = s;           // ([t0] is the group's start: there since the offsets launch)
-            reinterpret_cast<int2*>(tile_bins)[t0 + t] = c > 0 ? make_int2(s, s + c) : make_int2(0, 0);
-        }
-        int longest = c;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) longest = max(longest, __shfl_xor(longest, d, 64));
-        if (t == 0) group_max[blockIdx.x] = longest;
-    };
     // the window [c0, c0 + m) of the group's entries, run by run: op(position in the window, scratch word)
     auto for_runs = [&](int c0, int m, auto op) {
 #pragma unroll 1
@@ -1142,75 +1139,17 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_runs_kernel(
                 for (int j = 64; j < len[u]; j += 64) op(dst[u] + j, (unsigned int)scratch[src[u] + j]);
         }
     };
+    const GroupLists lists{t0, t1, begin, tile_start, tile_bins, group_max};
     const bool counted = total > kRunPass || total == 0;
     if (counted) {
-        for_runs(0, total, [&](int, unsigned int w) { atomicAdd(&hist[w >> kCoarseIdBits], 1); });
-        __syncthreads();
-        if (tid < 64) {
-            const int c = tid < kCoarseTiles ? hist[tid] : 0;
-            int inc = c;
-#pragma unroll
-            for (int d = 1; d < kCoarseTiles; d <<= 1) {
-                const int o = __shfl_up(inc, d, 64);
-                if (tid >= d) inc += o;
-            }
-            publish(tid, c, inc - c);
-            if (tid < kCoarseTiles) hist[tid] = 0;
-        }
-        __syncthreads();
+        for_runs(0, total, [&](int, unsigned int w) { atomicAdd(&sh.hist[w >> kCoarseIdBits], 1); });
+        publish_counted(sh, lists);
     }
     for (int c0 = 0; c0 < total; c0 += kRunPass) {
         const int m = min(kRunPass, total - c0);                      // entries of this pass
         for_runs(c0, m, [&](int k, unsigned int w) { buf[k] = w; });
         __syncthreads();
-        unsigned int w[kRunItems];
-        unsigned int rank2[(kRunItems + 1) / 2];                      // two 16-bit ranks per register (a rank is < kRunPass)
-#pragma unroll
-        for (int u = 0; u < (kRunItems + 1) / 2; ++u) rank2[u] = 0u;
-#pragma unroll
-        for (int u = 0; u < kRunItems; ++u) {
-            const int k = u * kFineThreads + tid;
-            if (k < m) w[u] = buf[k];
-        }
-#pragma unroll
-        for (int u = 0; u < kRunItems; ++u) {
-            const int k = u * kFineThreads + tid;
-            if (k < m) rank2[u / 2] |= (unsigned int)atomicAdd(&hist[w[u] >> kCoarseIdBits], 1) << (16 * (u & 1));
-        }
-        __syncthreads();
-        if (tid < 64) {                                               // one wave: offsets of the pass, bases, reset
-            const int c = tid < kCoarseTiles ? hist[tid] : 0;
-            int inc = c;                                              // inclusive scan over the first 32 lanes
-#pragma unroll
-            for (int d = 1; d < kCoarseTiles; d <<= 1) {
-                const int o = __shfl_up(inc, d, 64);
-                if (tid >= d) inc += o;
-            }
-            if (!counted) publish(tid, c, inc - c);                   // the only pass of the group: its counts are the lists'
-            if (tid < kCoarseTiles) {
-                loff[tid] = inc - c;
-                gbase[tid] = cursor[tid];
-                cursor[tid] += c;
-                hist[tid] = 0;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kRunItems; ++u) {
-            const int k = u * kFineThreads + tid;
-            if (k < m) buf[loff[w[u] >> kCoarseIdBits] + (int)((rank2[u / 2] >> (16 * (u & 1))) & 0xffffu)] = w[u];   // (the tile travels with the id)
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kRunItems; ++u) {
-            const int k = u * kFineThreads + tid;
-            if (k < m) {
-                const unsigned int e = buf[k];
-                const int t = (int)(e >> kCoarseIdBits);
-                bucket_ids[gbase[t] + (k - loff[t])] = (int)(e & ((1u << kCoarseIdBits) - 1u));
-            }
-        }
-        __syncthreads();                                              // buf / loff are rewritten by the next pass
+        place_pass<kRunItems>(sh, buf, m, [&](int k) { return buf[k]; }, !counted, lists, bucket_ids);
     }
 }
 
@@ -1548,12 +1487,7 @@ int ts_scan_tiles(int32_t n, const int32_t* num_tiles_hit, int32_t* cum_tiles_hi
     return launch_status();
 }
 
-int64_t ts_bin_ws_ints(int32_t n, int32_t num_tiles) {
-    if (num_tiles < 0) num_tiles = 0;
-    return (int64_t)(bin_num_chunks(n) + 1) * num_tiles + 3;     // counts | tile_start[T + 1] | guard | the spare word
-}
-
-
+int64_t ts_bin_ws_ints(int32_t n, int32_t num_tiles) { return bin_geometry(n, num_tiles).spare + 1; }
 
 int ts_bin_count(int32_t n, const float* xys, const int32_t* radii, const float* splats,
                  const ts_camera* cam, int32_t* bin_ws, void* stream) {
@@ -1561,17 +1495,15 @@ int ts_bin_count(int32_t n, const float* xys, const int32_t* radii, const float*
     const int nt = ts_num_tiles(cam);
     if (nt <= 0) return 0;
     if (n > 0 && (!xys || !radii)) return TS_E_BADARG;
-    const int chunks = bin_num_chunks(n);
-    const int chunk = n > 0 ? (n + chunks - 1) / chunks : 1;
+    const BinGeometry g = bin_geometry(n, nt);
     const int window = bin_window_tiles(n, nt);
     const int windows = (nt + window - 1) / window;
     const size_t lds = (size_t)window * sizeof(int);
-    // (the load-balanced walk does not pay for the count: 26 -> 28 us on config 3, 111 -> 149 us on config 5)
     if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_count_kernel<false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_count_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(bin_count_kernel<false>, dim3(chunks, windows), dim3(kBinThreads), lds,
-                       (hipStream_t)stream, n, chunk, xys, radii,
+    hipLaunchKernelGGL(bin_count_kernel, dim3(g.chunks, windows), dim3(kBinThreads), lds,
+                       (hipStream_t)stream, n, g.chunk, xys, radii,
                        reinterpret_cast<const float4*>(splats), *cam, nt, window, bin_ws);
     return launch_status();
 }
@@ -1586,14 +1518,14 @@ int ts_tile_offsets_stats(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t
     if (n < 0 || num_tiles < 0) return TS_E_BADARG;
     if (num_tiles == 0) return 0;
     if (!bin_ws || !tile_bins) return TS_E_BADARG;
-    const int chunks = bin_num_chunks(n);
-    int* tile_total = bin_ws + (size_t)chunks * num_tiles;     // [T + 1]: becomes tile_start, [T] = grand total
-    const int per_group = (chunks + kScanGroups - 1) / kScanGroups;
+    const BinGeometry g = bin_geometry(n, num_tiles);
+    int* tile_total = bin_ws + g.tile_start;                    // [T + 1]: becomes tile_start, [T] = grand total
+    const int per_group = (g.chunks + kScanGroups - 1) / kScanGroups;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(column_scan_kernel, dim3((num_tiles + kColTiles - 1) / kColTiles),
-                       dim3(kColTiles * kScanGroups), 0, s, num_tiles, chunks, per_group, bin_ws, tile_total, true);
+                       dim3(kColTiles * kScanGroups), 0, s, num_tiles, g.chunks, per_group, bin_ws, tile_total, true);
     hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(kOffsetsThreads), 0, s, num_tiles, tile_total,
-                       tile_bins, bin_ws + (ts_bin_ws_ints(n, num_tiles) - 1),
+                       tile_bins, bin_ws + g.spare,
                        (cum_tiles_hit && n > 0) ? cum_tiles_hit + (n - 1) : nullptr, (long long)capacity, longest_list);
     return launch_status();
 }
@@ -1605,42 +1537,50 @@ int ts_bin_count_groups(int32_t n, const float* xys, const int32_t* radii, const
     if (!cam || !bin_ws || !xys || !radii || !two_hop(n)) return TS_E_BADARG;
     const int nt = ts_num_tiles(cam);
     if (nt <= 0) return 0;
-    const int chunks = bin_num_chunks(n);
-    const int chunk = (n + chunks - 1) / chunks;
-    const int groups = (nt + kCoarseTiles - 1) >> kCoarseShift;
-    hipLaunchKernelGGL(group_bin_count_kernel, dim3(chunks), dim3(kBinThreads), (size_t)groups * sizeof(int),
-                       (hipStream_t)stream, n, chunk, xys, radii, reinterpret_cast<const float4*>(splats), *cam,
-                       groups, bin_ws);
+    const BinGeometry g = bin_geometry(n, nt);
+    hipLaunchKernelGGL(group_bin_count_kernel, dim3(g.chunks), dim3(kBinThreads), (size_t)g.groups * sizeof(int),
+                       (hipStream_t)stream, n, g.chunk, xys, radii, reinterpret_cast<const float4*>(splats), *cam,
+                       g.groups, bin_ws);
     return launch_status();
 }
+
+}  // extern "C"
+
+namespace {
+// The offsets launch of the group form (BASES: the counts at the front of the workspace become bases) and of the
+// one-walk form (its counts row stays as it is).  One workgroup scans the columns too while the B x G matrix is small
+// (config 3: 245 x 255 ints = 250 KB); beyond kGoSingleMax ints (config 5: 512 x 507) the columns get
+// column_scan_kernel's many workgroups first.  (One walk: the column totals of a frame that tripped the guard are sums
+// of stale words, and the offsets launch never reads them; its groups fit the LDS by one_walk_form.)
+template <bool BASES>
+int group_offsets(const BinGeometry& g, int num_tiles, int* bin_ws, int* tile_bins, const int* total_ptr,
+                  long long capacity, int* longest_list, hipStream_t s) {
+    int* counts = bin_ws + (BASES ? 0 : g.counts);
+    int* col_total = nullptr;
+    if ((long long)g.chunks * g.groups > kGoSingleMax || g.groups > kGoLdsGroups) {
+        col_total = bin_ws + (BASES ? g.group_totals : g.col_total);
+        const int per_group = (g.chunks + kScanGroups - 1) / kScanGroups;
+        hipLaunchKernelGGL(column_scan_kernel, dim3((g.groups + kColTiles - 1) / kColTiles),
+                           dim3(kColTiles * kScanGroups), 0, s, g.groups, g.chunks, per_group, counts, col_total, BASES);
+        counts = nullptr;
+    }
+    hipLaunchKernelGGL(group_tile_offsets_kernel<BASES>, dim3(1), dim3(kGoThreads), 0, s, num_tiles, g.groups, g.chunks,
+                       counts, (const int*)col_total, bin_ws + g.tile_start, tile_bins, bin_ws + g.spare, total_ptr,
+                       capacity, longest_list);
+    return launch_status();
+}
+}  // namespace
+
+extern "C" {
 
 int ts_group_offsets(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins,
                      const int32_t* cum_tiles_hit, int64_t capacity, int32_t* longest_list, void* stream) {
     if (num_tiles < 0 || !two_hop(n)) return TS_E_BADARG;
     if (num_tiles == 0) return 0;
     if (!bin_ws || !tile_bins) return TS_E_BADARG;
-    const int chunks = bin_num_chunks(n);
-    const int groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
-    int* tile_start = bin_ws + (size_t)chunks * num_tiles;
-    int* spare = bin_ws + (ts_bin_ws_ints(n, num_tiles) - 1);
-    const int* total_ptr = cum_tiles_hit ? cum_tiles_hit + (n - 1) : nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    // one workgroup scans the columns too while the B x G matrix is small (config 3: 245 x 255 ints = 250 KB);
-    // beyond kGoSingleMax ints (config 5: 512 x 507) the columns get column_scan_kernel's many workgroups first
-    if ((long long)chunks * groups <= kGoSingleMax && groups <= kGoLdsGroups) {
-        hipLaunchKernelGGL(group_tile_offsets_kernel<true>, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups, chunks,
-                           bin_ws, (const int*)nullptr, tile_start, tile_bins, spare, total_ptr, (long long)capacity,
-                           longest_list);
-    } else {
-        int* col_total = bin_ws + (size_t)chunks * groups;
-        const int per_group = (chunks + kScanGroups - 1) / kScanGroups;
-        hipLaunchKernelGGL(column_scan_kernel, dim3((groups + kColTiles - 1) / kColTiles),
-                           dim3(kColTiles * kScanGroups), 0, s, groups, chunks, per_group, bin_ws, col_total, true);
-        hipLaunchKernelGGL(group_tile_offsets_kernel<true>, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups, chunks,
-                           (int*)nullptr, (const int*)col_total, tile_start, tile_bins, spare, total_ptr,
-                           (long long)capacity, longest_list);
-    }
-    return launch_status();
+    return group_offsets<true>(bin_geometry(n, num_tiles), num_tiles, bin_ws, tile_bins,
+                               cum_tiles_hit ? cum_tiles_hit + (n - 1) : nullptr, (long long)capacity, longest_list,
+                               (hipStream_t)stream);
 }
 
 int ts_bin_scatter_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
@@ -1650,23 +1590,16 @@ int ts_bin_scatter_groups(int32_t n, const float* xys, const int32_t* radii, con
         return TS_E_BADARG;
     const int nt = ts_num_tiles(cam);
     if (nt <= 0) return 0;
-    const int chunks = bin_num_chunks(n);
-    const int chunk = (n + chunks - 1) / chunks;
-    const int groups = (nt + kCoarseTiles - 1) >> kCoarseShift;
-    int* tile_start = bin_ws + (size_t)chunks * nt;
+    const BinGeometry g = bin_geometry(n, nt);
+    int* tile_start = bin_ws + g.tile_start;
     hipStream_t s = (hipStream_t)stream;
-    if (cam->hints & TS_HINT_BALANCED_WALK)
-        hipLaunchKernelGGL((bin_scatter_coarse_kernel<true, true>), dim3(chunks), dim3(kBinThreads),
-                           (size_t)groups * sizeof(int), s, n, chunk, xys, radii,
-                           reinterpret_cast<const float4*>(splats), *cam, nt, (const int*)bin_ws,
-                           (const int*)tile_start, scratch);
-    else
-        hipLaunchKernelGGL((bin_scatter_coarse_kernel<false, true>), dim3(chunks), dim3(kBinThreads),
-                           (size_t)groups * sizeof(int), s, n, chunk, xys, radii,
-                           reinterpret_cast<const float4*>(splats), *cam, nt, (const int*)bin_ws,
-                           (const int*)tile_start, scratch);
-    hipLaunchKernelGGL(bin_scatter_fine_groups_kernel, dim3(groups), dim3(kFineThreads), 0, s, nt, tile_start,
-                       tile_bins, bin_ws + nt + 1, (const int*)scratch, bucket_ids);
+    const auto coarse = (cam->hints & TS_HINT_BALANCED_WALK) ? bin_scatter_coarse_kernel<true, true>
+                                                             : bin_scatter_coarse_kernel<false, true>;
+    hipLaunchKernelGGL(coarse, dim3(g.chunks), dim3(kBinThreads), (size_t)g.groups * sizeof(int), s, n, g.chunk, xys,
+                       radii, reinterpret_cast<const float4*>(splats), *cam, nt, (const int*)bin_ws,
+                       (const int*)tile_start, scratch);
+    hipLaunchKernelGGL(bin_scatter_fine_groups_kernel, dim3(g.groups), dim3(kFineThreads), 0, s, nt, tile_start,
+                       tile_bins, bin_ws + g.group_max, (const int*)scratch, bucket_ids);
     return launch_status();
 }
 
@@ -1680,60 +1613,33 @@ int ts_bin_emit_groups(int32_t n, const float* xys, const int32_t* radii, const 
     if (!cam || !xys || !radii || !cum_tiles_hit || !bin_ws || !scratch) return TS_E_BADARG;
     const int nt = ts_num_tiles(cam);
     if (!one_walk_form(n, nt) || (cam->hints & TS_HINT_BALANCED_WALK)) return TS_E_BADARG;
-    const int chunks = bin_num_chunks(n);
-    const int chunk = (n + chunks - 1) / chunks;
-    const int groups = (nt + kCoarseTiles - 1) >> kCoarseShift;
-    const OneWalkLayout l = one_walk_layout(chunks, groups, nt);
-    const size_t lds = (size_t)groups * 8 + (size_t)kStageCap * 6;
+    const BinGeometry g = bin_geometry(n, nt);
+    const size_t lds = (size_t)g.groups * 8 + (size_t)kStageCap * 6;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_emit_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(bin_scatter_emit_kernel, dim3(chunks), dim3(kBinThreads), lds, (hipStream_t)stream, n, chunk,
-                       xys, radii, reinterpret_cast<const float4*>(splats), *cam, groups, cum_tiles_hit,
-                       (long long)capacity, bin_ws + l.counts, bin_ws + l.starts, scratch);
+    hipLaunchKernelGGL(bin_scatter_emit_kernel, dim3(g.chunks), dim3(kBinThreads), lds, (hipStream_t)stream, n, g.chunk,
+                       xys, radii, reinterpret_cast<const float4*>(splats), *cam, g.groups, cum_tiles_hit,
+                       (long long)capacity, bin_ws + g.counts, bin_ws + g.starts, scratch);
     return launch_status();
 }
 
 int ts_emit_offsets(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins,
                     const int32_t* cum_tiles_hit, int64_t capacity, int32_t* longest_list, void* stream) {
     if (!one_walk_form(n, num_tiles) || !bin_ws || !tile_bins || !cum_tiles_hit) return TS_E_BADARG;
-    const int chunks = bin_num_chunks(n);
-    const int groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
-    const OneWalkLayout l = one_walk_layout(chunks, groups, num_tiles);
-    int* tile_start = bin_ws + (size_t)chunks * num_tiles;
-    int* spare = bin_ws + (ts_bin_ws_ints(n, num_tiles) - 1);
-    const int* total_ptr = cum_tiles_hit + (n - 1);
-    hipStream_t s = (hipStream_t)stream;
-    if ((long long)chunks * groups <= kGoSingleMax) {
-        hipLaunchKernelGGL(group_tile_offsets_kernel<false>, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups,
-                           chunks, bin_ws + l.counts, (const int*)nullptr, tile_start, tile_bins, spare, total_ptr,
-                           (long long)capacity, longest_list);
-    } else {
-        // (the column totals of a frame that tripped the guard are sums of stale words: the offsets launch never reads them)
-        int* col_total = bin_ws + l.col_total;
-        const int per_group = (chunks + kScanGroups - 1) / kScanGroups;
-        hipLaunchKernelGGL(column_scan_kernel, dim3((groups + kColTiles - 1) / kColTiles),
-                           dim3(kColTiles * kScanGroups), 0, s, groups, chunks, per_group, bin_ws + l.counts, col_total,
-                           false);
-        hipLaunchKernelGGL(group_tile_offsets_kernel<false>, dim3(1), dim3(kGoThreads), 0, s, num_tiles, groups,
-                           chunks, (int*)nullptr, (const int*)col_total, tile_start, tile_bins, spare, total_ptr,
-                           (long long)capacity, longest_list);
-    }
-    return launch_status();
+    return group_offsets<false>(bin_geometry(n, num_tiles), num_tiles, bin_ws, tile_bins, cum_tiles_hit + (n - 1),
+                                (long long)capacity, longest_list, (hipStream_t)stream);
 }
 
 int ts_bin_gather_groups(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins, int32_t* bucket_ids,
                          const int32_t* scratch, void* stream) {
     if (!one_walk_form(n, num_tiles) || !bin_ws || !tile_bins || !bucket_ids || !scratch) return TS_E_BADARG;
-    const int chunks = bin_num_chunks(n);
-    const int groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
-    const OneWalkLayout l = one_walk_layout(chunks, groups, num_tiles);
-    int* tile_start = bin_ws + (size_t)chunks * num_tiles;
+    const BinGeometry g = bin_geometry(n, num_tiles);
     const size_t lds = (size_t)kRunPass * sizeof(int);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_fine_runs_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(bin_scatter_fine_runs_kernel, dim3(groups), dim3(kFineThreads), lds, (hipStream_t)stream,
-                       num_tiles, groups, chunks, (const int*)(bin_ws + l.counts), (const int*)(bin_ws + l.starts),
-                       tile_start, tile_bins, bin_ws + num_tiles + 1, scratch, bucket_ids);
+    hipLaunchKernelGGL(bin_scatter_fine_runs_kernel, dim3(g.groups), dim3(kFineThreads), lds, (hipStream_t)stream,
+                       num_tiles, g.groups, g.chunks, (const int*)(bin_ws + g.counts), (const int*)(bin_ws + g.starts),
+                       bin_ws + g.tile_start, tile_bins, bin_ws + g.group_max, scratch, bucket_ids);
     return launch_status();
 }
 
@@ -1745,26 +1651,21 @@ int ts_bin_scatter(int32_t n, const float* xys, const int32_t* radii, const floa
     if (!xys || !radii || !bin_ws || !bucket_ids) return TS_E_BADARG;
     const int nt = ts_num_tiles(cam);
     if (nt <= 0) return 0;
-    const int chunks = bin_num_chunks(n);
-    const int chunk = (n + chunks - 1) / chunks;
-    const int* tile_start = bin_ws + (size_t)chunks * nt;
+    const BinGeometry g = bin_geometry(n, nt);
+    const int* tile_start = bin_ws + g.tile_start;
+    hipStream_t s = (hipStream_t)stream;
     // two coalesced hops (see bin_scatter_coarse_kernel) where the write amplification of the direct scatter is what
     // binds; a small launch (a 100 k scene, the ~125 k records of one rank of a sharded frame) is latency-bound and
     // the second launch costs more than it saves (34 vs 12 us on a 1/8 stripe of config 3)
     if (scratch && two_hop(n)) {
-        const int groups = (nt + kCoarseTiles - 1) >> kCoarseShift;
         // load-balanced walk where the caller says a Gaussian covers many tiles (ts_camera.hints & TS_HINT_BALANCED_WALK):
         // config 5 (16 bounding-box tiles per Gaussian) coarse hop 369 -> 274 us; config 3 (6 tiles) 51 -> 56 us
-        if (cam->hints & TS_HINT_BALANCED_WALK)
-            hipLaunchKernelGGL(bin_scatter_coarse_kernel<true>, dim3(chunks), dim3(kBinThreads),
-                               (size_t)groups * sizeof(int), (hipStream_t)stream, n, chunk, xys, radii,
-                               reinterpret_cast<const float4*>(splats), *cam, nt, bin_ws, tile_start, scratch);
-        else
-            hipLaunchKernelGGL(bin_scatter_coarse_kernel<false>, dim3(chunks), dim3(kBinThreads),
-                               (size_t)groups * sizeof(int), (hipStream_t)stream, n, chunk, xys, radii,
-                               reinterpret_cast<const float4*>(splats), *cam, nt, bin_ws, tile_start, scratch);
-        hipLaunchKernelGGL(bin_scatter_fine_kernel, dim3(groups), dim3(kFineThreads), 0, (hipStream_t)stream, nt,
-                           tile_start, scratch, bucket_ids);
+        const auto coarse = (cam->hints & TS_HINT_BALANCED_WALK) ? bin_scatter_coarse_kernel<true, false>
+                                                                 : bin_scatter_coarse_kernel<false, false>;
+        hipLaunchKernelGGL(coarse, dim3(g.chunks), dim3(kBinThreads), (size_t)g.groups * sizeof(int), s, n, g.chunk, xys,
+                           radii, reinterpret_cast<const float4*>(splats), *cam, nt, bin_ws, tile_start, scratch);
+        hipLaunchKernelGGL(bin_scatter_fine_kernel, dim3(g.groups), dim3(kFineThreads), 0, s, nt, tile_start,
+                           (const int*)scratch, bucket_ids);
         return launch_status();
     }
     const int window = bin_window_tiles(n, nt);
@@ -1773,25 +1674,21 @@ int ts_bin_scatter(int32_t n, const float* xys, const int32_t* radii, const floa
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(bin_scatter_kernel, dim3(chunks, windows), dim3(kBinThreads), lds,
-                       (hipStream_t)stream, n, chunk, xys, radii,
-                       reinterpret_cast<const float4*>(splats), *cam, nt, window, bin_ws,
-                       tile_start, bucket_ids);
+    hipLaunchKernelGGL(bin_scatter_kernel, dim3(g.chunks, windows), dim3(kBinThreads), lds, s, n, g.chunk, xys, radii,
+                       reinterpret_cast<const float4*>(splats), *cam, nt, window, bin_ws, tile_start, bucket_ids);
     return launch_status();
 }
 
 }  // extern "C"
 
 namespace {
-// where the group form keeps what the sort launch needs for the longest-list word (layout: GROUP COUNTS above)
+// what the sort launch of a group-form or one-walk frame needs for the longest-list word (BinGeometry: group_max, guard)
 inline bool list_stats(int n, int num_tiles, const int32_t* bin_ws, int32_t* longest_list, ListStats* st) {
     *st = ListStats{nullptr, nullptr, nullptr, 0};
     if (!longest_list) return true;
     if (!bin_ws || !two_hop(n) || num_tiles <= 0) return false;
-    st->group_max = bin_ws + num_tiles + 1;
-    st->guard = bin_ws + (size_t)bin_num_chunks(n) * num_tiles + num_tiles + 1;
-    st->longest_out = longest_list;
-    st->groups = (num_tiles + kCoarseTiles - 1) >> kCoarseShift;
+    const BinGeometry g = bin_geometry(n, num_tiles);
+    *st = ListStats{bin_ws + g.group_max, bin_ws + g.guard, longest_list, g.groups};
     return true;
 }
 }  // namespace

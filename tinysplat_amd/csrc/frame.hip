@@ -117,17 +117,24 @@ inline bool survivors(const ts_frame* f) {
            f->cam.wide_tiles == 0 &&
            !(f->flags & (TS_FRAME_SPLIT | TS_FRAME_NARROW_WAVES | TS_FRAME_SEPARATE_SORT));
 }
-// GROUP COUNTS (TS_FRAME_GROUP_COUNTS): count, offsets and scatter of a frame in the group form (binning.hip).  _prepare
-// and _composite ask the same question of the same struct, so the three launches are always of one form
-inline bool group_counts(const ts_frame* f) {
-    return (f->flags & TS_FRAME_GROUP_COUNTS) && !(f->flags & TS_FRAME_DIRECT_SCATTER) && ts_bin_group_form(f->n);
+// THE FORM of a frame's list building (binning.hip), decided once per call from the struct alone: _prepare and _composite
+// ask the same question of the same struct, so the launches of a frame are always of one form.
+//   direct    count, offsets | scatter                   below 2^18 Gaussians, or TS_FRAME_DIRECT_SCATTER
+//   matrix    count, offsets | coarse hop, fine hop      the two-hop scatter on the B x T count matrix
+//   group     group count, group offsets | coarse hop, fine hop      TS_FRAME_GROUP_COUNTS: B x G counts
+//   one walk  | emit, offsets, fine hop                  TS_FRAME_ONE_WALK: all of it in _composite; not with the
+//                                                        balanced-walk hint, nor where the rows do not fit the workspace
+enum class ListForm { direct, matrix, group, one_walk };
+inline ListForm list_form(const ts_frame* f) {
+    if ((f->flags & TS_FRAME_DIRECT_SCATTER) || !ts_bin_group_form(f->n)) return ListForm::direct;
+    if (!(f->flags & TS_FRAME_GROUP_COUNTS)) return ListForm::matrix;
+    if ((f->flags & TS_FRAME_ONE_WALK) && !(f->cam.hints & TS_HINT_BALANCED_WALK) &&
+        ts_bin_one_walk_form(f->n, num_tiles(f)))
+        return ListForm::one_walk;
+    return ListForm::group;
 }
-// ONE WALK (TS_FRAME_ONE_WALK): a group-form frame whose lists are built from one walk of the Gaussians - all of it in
-// _composite (emit, offsets, fine hop); _prepare enqueues the colour stage alone.  One predicate for both calls
-inline bool one_walk(const ts_frame* f) {
-    return (f->flags & TS_FRAME_ONE_WALK) && group_counts(f) && !(f->cam.hints & TS_HINT_BALANCED_WALK) &&
-           ts_bin_one_walk_form(f->n, num_tiles(f));
-}
+// the records the lists are tightened with (TS_FRAME_TIGHT), or null: bounding-box lists
+inline const float* tight_records(const ts_frame* f) { return (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr; }
 // TS_FRAME_LIST_STATS: the word behind the count word, or null
 inline int32_t* longest_word(const ts_frame* f) {
     if ((f->flags & TS_FRAME_LIST_STATS) && f->total_host) {
@@ -186,25 +193,28 @@ int ts_frame_fwd_prepare(const ts_frame* f, void* stream) {
                                        TS_RASTER_LOGIT_OPACITY, f->xys, f->radii, f->conics, f->opacities,
                                        f->cum_tiles_hit, &f->cam, f->channels == 4 ? f->depths : nullptr, f->splats,
                                        stream)));
-    if (one_walk(f)) return 0;          // the lists are _composite's work, offsets included
-    const float* tight = (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr;
+    const float* tight = tight_records(f);
     // (TS_FRAME_LIST_STATS: the longest list goes to the word behind the count word - read a frame later by the caller's
     // launch policy, never waited for)
-    int32_t* longest = longest_word(f);
-    if (group_counts(f)) {
+    switch (list_form(f)) {
+    case ListForm::one_walk:            // the lists are _composite's work, offsets included
+        return 0;
+    case ListForm::group:
         // the lists themselves (tile_bins) are the scatter's work in this form; the longest list's length reaches its
         // word from the sort launch of _composite (from here only for a frame that lists nothing)
         TS_TRY(TS_ENTRY("ts_bin_count",
                         ts_bin_count_groups(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, stream)));
         return TS_ENTRY("ts_tile_offsets",
                         ts_group_offsets(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->cum_tiles_hit, f->capacity,
-                                         longest, stream));
+                                         longest_word(f), stream));
+    case ListForm::matrix:
+    case ListForm::direct:
+        TS_TRY(TS_ENTRY("ts_bin_count", ts_bin_count(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, stream)));
+        return TS_ENTRY("ts_tile_offsets",
+                        ts_tile_offsets_stats(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->cum_tiles_hit,
+                                              f->capacity, longest_word(f), stream));
     }
-    TS_TRY(TS_ENTRY("ts_bin_count", ts_bin_count(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, stream)));
-    TS_TRY(TS_ENTRY("ts_tile_offsets",
-                    ts_tile_offsets_stats(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->cum_tiles_hit, f->capacity,
-                                          longest, stream)));
-    return 0;
+    return TS_E_BADARG;
 }
 
 int ts_frame_fwd_composite(const ts_frame* f, void* stream) {
@@ -216,38 +226,44 @@ int ts_frame_fwd_composite(const ts_frame* f, void* stream) {
     // entries itself
     const bool fused_sort = f->num_intersects > 0 && f->cam.wide_tiles == 0 &&
                             !(f->flags & (TS_FRAME_NARROW_WAVES | TS_FRAME_SEPARATE_SORT));
-    const bool walk_once = one_walk(f);
-    if (walk_once) {
-        // (also for a frame without intersections: the offsets launch is what empties its lists)
-        const float* tight = (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr;
+    const ListForm form = list_form(f);
+    const float* tight = tight_records(f);
+    const bool listed = f->num_intersects > 0;
+    // the sorted-id buffer is dead until the sort: it carries the ids between the two scatter hops
+    int32_t* scratch = f->gaussian_ids_sorted;
+    switch (form) {
+    case ListForm::one_walk:
+        // (emit and offsets also for a frame without intersections: the offsets launch is what empties its lists)
         TS_TRY(TS_ENTRY("ts_bin_scatter",
                         ts_bin_emit_groups(f->n, f->xys, f->radii, tight, &f->cam, f->cum_tiles_hit, f->capacity,
-                                           f->bin_ws, f->gaussian_ids_sorted, stream)));
+                                           f->bin_ws, scratch, stream)));
         TS_TRY(TS_ENTRY("ts_tile_offsets",
                         ts_emit_offsets(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->cum_tiles_hit, f->capacity,
                                         longest_word(f), stream)));
-    }
-    if (f->num_intersects > 0) {
-        const float* tight = (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr;
-        // the sorted-id buffer is dead until the sort: it carries the ids between the two scatter hops
-        const bool groups = group_counts(f);
-        if (walk_once)
+        if (listed)
             TS_TRY(TS_ENTRY("ts_bin_scatter",
-                            ts_bin_gather_groups(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->bucket_ids,
-                                                 f->gaussian_ids_sorted, stream)));
-        else if (groups)
+                            ts_bin_gather_groups(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->bucket_ids, scratch,
+                                                 stream)));
+        break;
+    case ListForm::group:
+        if (listed)
             TS_TRY(TS_ENTRY("ts_bin_scatter",
                             ts_bin_scatter_groups(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, f->tile_bins,
-                                                  f->bucket_ids, f->gaussian_ids_sorted, stream)));
-        else
+                                                  f->bucket_ids, scratch, stream)));
+        break;
+    case ListForm::matrix:
+    case ListForm::direct:
+        if (listed)
             TS_TRY(TS_ENTRY("ts_bin_scatter",
                             ts_bin_scatter(f->n, f->xys, f->radii, tight, &f->cam, f->bin_ws, f->bucket_ids,
-                                           (f->flags & TS_FRAME_DIRECT_SCATTER) ? nullptr : f->gaussian_ids_sorted,
-                                           stream)));
+                                           form == ListForm::matrix ? scratch : nullptr, stream)));
+        break;
+    }
+    if (listed) {
         int32_t* counter = f->bin_ws + (ts_bin_ws_ints(f->n, num_tiles(f)) - 1);
-        // (group form: the first workgroup of the sort launch also reduces the fine hop's per-group maxima into the
-        // longest-list word)
-        int32_t* longest = groups ? longest_word(f) : nullptr;
+        // (group and one-walk forms: the first workgroup of the sort launch also reduces the fine hop's per-group maxima
+        // into the longest-list word)
+        int32_t* longest = (form == ListForm::group || form == ListForm::one_walk) ? longest_word(f) : nullptr;
         if (fused_sort)
             TS_TRY(TS_ENTRY("ts_sort_tiles",
                             ts_sort_tiles_above_stats(num_tiles(f), f->tile_bins, f->depths, f->bucket_ids,
@@ -380,8 +396,8 @@ int ts_shard_stripe_fwd_import(const ts_frame* fs, const float* records, void* s
         TS_TRY(TS_ENTRY("ts_import_pack",
                         ts_import_pack(fs->n, records, fs->cum_tiles_hit, &fs->cam, fs->splats, stream)));
     }
-    const float* tight = (fs->flags & TS_FRAME_TIGHT) ? fs->splats : nullptr;
-    TS_TRY(TS_ENTRY("ts_bin_count", ts_bin_count(fs->n, fs->xys, fs->radii, tight, &fs->cam, fs->bin_ws, stream)));
+    TS_TRY(TS_ENTRY("ts_bin_count",
+                    ts_bin_count(fs->n, fs->xys, fs->radii, tight_records(fs), &fs->cam, fs->bin_ws, stream)));
     return TS_ENTRY("ts_tile_offsets",
                     ts_tile_offsets(fs->n, num_tiles(fs), fs->bin_ws, fs->tile_bins, fs->cum_tiles_hit, fs->capacity,
                                     stream));
