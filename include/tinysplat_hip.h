@@ -1068,6 +1068,24 @@ int ts_jpeg_encode(const void* image, int32_t dtype, int32_t pixel_stride, int32
                    int32_t subsampling, int32_t restart_interval, void* workspace, uint8_t* out, int64_t out_capacity,
                    int32_t* size_word, int16_t* coefficients, void* stream);
 
+/* The quality of one image against one target (csrc/metrics_math.h).  Additive entries: the ABI
+ * version is unchanged.
+ * image: float32 [height, width, pixel_floats], pixel_floats 3 or 4 (channel 3, the compositing kernels' depth, is never
+ * read); target: [height, width, 3], float32 or, with target_is_u8 != 0, uint8 whose byte b stands for the float32
+ * quotient b / 255.0f - both targets of the same values give the same 32 bytes of output.  Byte rows need no alignment.
+ * out4 <- four device doubles {mse, l1, ssim, psnr}: the means of (x - y)^2 and |x - y| over the 3 H W elements (each
+ * difference one float32 subtraction, everything after it double), the SSIM of the training loss
+ * (pytorch_msssim.SSIM(data_range=1, size_average=True, channel=3): 11-tap sigma-1.5 window, valid filtering, K = (0.01,
+ * 0.03), mean over 3 (H-10)(W-10) - NOT the zero-padded SSIM of the 3DGS papers' tables), and -10 log10(mse), +inf
+ * where mse == 0.  Two launches, no allocation, no synchronisation, no atomics; the workspace size and the order of
+ * every sum depend on (height, width) alone, so the same inputs give the same bytes on every run and device.
+ * ws: >= ts_image_metrics_ws_bytes bytes (24 per wave of the first launch; 0 where height or width <= 10), and like out4
+ * 8-byte aligned.  TS_E_BADARG, before any launch: height or width <= 10, pixel_floats not 3 or 4, a NULL or misaligned
+ * pointer. */
+int64_t ts_image_metrics_ws_bytes(int32_t height, int32_t width);
+int ts_image_metrics(int32_t height, int32_t width, int32_t pixel_floats, const float* image, const void* target,
+                     int32_t target_is_u8, void* ws, double* out4, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

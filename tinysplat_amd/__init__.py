@@ -11,6 +11,7 @@ from .simplify import SimplifyConfig, simplify_mesh
 from .clean import CleanConfig, clean_mesh, mesh_components
 from .dataset import Dataset
 from .jpeg import JpegEncoder, encode_jpeg
+from .metrics import EvalResult, Evaluator, evaluate, holdout_split, image_metrics
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
 from .rasterizer import GaussianRasterizer
 from .scene import Scene
@@ -24,4 +25,5 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "read_point_cloud_ply", "SurfaceConfig", "SurfaceRegularizer", "opacity_entropy", "DensitySamples",
            "sample_points", "density_loss", "density_parts", "ExtractConfig", "SurfacePoints", "extract_surface_points",
            "level_set_points", "MeshConfig", "TriangleMesh", "extract_mesh", "vertex_colors", "SimplifyConfig",
-           "simplify_mesh", "CleanConfig", "clean_mesh", "mesh_components", "Dataset", "Viewer", "encode_jpeg", "JpegEncoder"]
+           "simplify_mesh", "CleanConfig", "clean_mesh", "mesh_components", "Dataset", "Viewer", "encode_jpeg", "JpegEncoder",
+           "image_metrics", "evaluate", "holdout_split", "Evaluator", "EvalResult"]

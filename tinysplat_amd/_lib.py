@@ -237,6 +237,8 @@ SIGNATURES = {
     "ts_jpeg_header": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int64]),
     "ts_jpeg_encode": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int64, _P,
                                  _P, _P]),
+    "ts_image_metrics_ws_bytes": (c_int64, [c_int32, c_int32]),
+    "ts_image_metrics": (c_int32, [c_int32, c_int32, c_int32, _P, _P, c_int32, _P, _P, _P]),
 }
 
 _lib = None

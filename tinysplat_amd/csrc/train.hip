@@ -17,6 +17,7 @@
 #include "../../include/tinysplat_hip.h"
 #include "host_util.h"
 #include "adam_math.h"
+#include "gauss_window.h"
 
 namespace {
 
@@ -26,10 +27,7 @@ constexpr int kPatch = kTile + kHalo;          // 42
 constexpr int kThreads = 256;
 constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
 
-// pytorch_msssim._fspecial_gauss_1d(11, 1.5) as torch evaluates it in float32 (exp(-(i-5)^2 / 4.5), normalised by the
-// float32 sum): the eleven values the reference's SSIM module holds, as literals
-#define TS_GAUSS_WINDOW 0x1.0d957p-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f, \
-                        0x1.b43c3ep-3f, 0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d957p-10f
+// (TS_GAUSS_WINDOW: gauss_window.h)
 __device__ __forceinline__ void gauss_window(float* g) {
     constexpr float w[kWin] = {TS_GAUSS_WINDOW};
 #pragma unroll

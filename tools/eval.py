@@ -1,0 +1,82 @@
+#!/usr/bin/env python
+"""Evaluates a saved scene on the views of a COLMAP dataset: PSNR, SSIM and L1 per view and their means.
+
+    python tools/eval.py scene.ply --dataset-dir datasets/train --holdout 8
+
+``SCENE`` is a 3DGS PLY (``.ply``), a checkpoint (``.pth`` / ``.pt``) or a ``.splat`` file, told apart by its extension.
+``--holdout N`` evaluates every N-th camera by image name - the views ``tools/train.py --eval-holdout N`` kept out of
+training; ``--holdout 0`` evaluates all views.  Every view is rendered on a black background and compared with its
+(undistorted) image; ``--max-image-dimension`` and ``--principal-point`` must be those the scene was trained with.  SSIM
+is the training loss's (pytorch_msssim: valid filtering), not the zero-padded SSIM of the 3DGS papers' tables.  Needs a
+GPU: there is no CPU path.
+"""
+import argparse
+import csv
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+READERS = {".ply": "load_ply", ".pth": "load_checkpoint", ".pt": "load_checkpoint", ".splat": "load_splat"}
+HEADER = ("view", "psnr", "ssim", "l1", "mse")
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("scene", type=str, help="scene.ply, scene.pth or scene.splat")
+    ap.add_argument("--device", type=str, default="cuda:0")
+    ap.add_argument("--dataset-dir", type=str, required=True)
+    ap.add_argument("--colmap-path", type=str, default="colmap/sparse/0", help="below --dataset-dir")
+    ap.add_argument("--images-path", type=str, default="images", help="below --dataset-dir")
+    ap.add_argument("--max-image-dimension", type=int, default=None,
+                    help="downscale the targets so that their longer side is at most this many pixels")
+    ap.add_argument("--principal-point", choices=("reference", "center"), default="reference")
+    ap.add_argument("--holdout", type=int, default=8, help="evaluate every N-th camera by image name; 0: all of them")
+    ap.add_argument("--csv", type=str, default=None, help="write the per-view table and the means to this CSV file")
+    args = ap.parse_args(argv)
+    if Path(args.scene).suffix.lower() not in READERS:
+        ap.error(f"SCENE must end in one of {', '.join(READERS)}")
+    if args.holdout < 0 or (args.max_image_dimension is not None and args.max_image_dimension < 1):
+        ap.error("--holdout must not be negative and --max-image-dimension must be at least 1")
+    return args
+
+
+def table_rows(result):
+    """(view, psnr, ssim, l1, mse) per view, then the means."""
+    rows = [(name, float(r[3]), float(r[2]), float(r[1]), float(r[0])) for name, r in zip(result.names, result.table)]
+    return rows + [("mean", result.psnr, result.ssim, result.l1, result.mse)]
+
+
+def main(argv=None):
+    args = parse(argv)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: tinysplat_amd has no CPU path")
+    from tinysplat_amd import Dataset, evaluate, formats, holdout_split
+    from tinysplat_amd.dataset import Targets
+    base = Path(args.dataset_dir)
+    dataset = Dataset(base / args.colmap_path, base / args.images_path, max_image_dimension=args.max_image_dimension,
+                      device=args.device, principal_point=args.principal_point)
+    model = getattr(formats, READERS[Path(args.scene).suffix.lower()])(args.scene, args.device)
+    train, test = holdout_split([c.name for c in dataset.cameras], args.holdout)
+    views = test if args.holdout else train
+    if not views:
+        raise SystemExit(f"--holdout {args.holdout} selects none of the {len(dataset.cameras)} cameras")
+    result = evaluate(model, [dataset.cameras[i] for i in views], Targets([dataset.targets.images_u8[i] for i in views]),
+                      args.device)
+    rows = table_rows(result)
+    width = max(len(r[0]) for r in rows)
+    print(f"{'view':<{width}}  {'PSNR':>9}  {'SSIM':>8}  {'L1':>8}")
+    for name, psnr, ssim, l1, _mse in rows:
+        print(f"{name:<{width}}  {psnr:9.4f}  {ssim:8.5f}  {l1:8.5f}")
+    print(f"{len(views)} views, {model.num_points} Gaussians")
+    if args.csv:
+        with open(args.csv, "w", newline="") as f:
+            writer = csv.writer(f)
+            writer.writerow(HEADER)
+            writer.writerows([r[0], *(repr(v) for v in r[1:])] for r in rows)
+
+
+if __name__ == "__main__":
+    main()

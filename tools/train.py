@@ -3,14 +3,17 @@
 
     python tools/train.py --dataset-dir datasets/train --max-iter 10000 --output scene.ply
 
-The flow of the reference's scripts/train.py without its depth prior and metrics table: ``Dataset`` reads
+The flow of the reference's scripts/train.py without its depth prior: ``Dataset`` reads
 ``<dataset-dir>/<colmap-path>`` (cameras.bin, images.bin, points3D.bin) and undistorts the images of
 ``<dataset-dir>/<images-path>`` on the GPU, ``from_pcd`` starts the model from the sparse points, ``fit`` trains it
 with densification every ``len(cameras)`` steps (train.py:277), and the result is written as a 3DGS PLY (``.ply``), a
 checkpoint (``.pth`` / ``.pt``) or a ``.splat`` file, told apart by the extension of ``--output``.  ``--viewer`` serves the
 scene while it trains (``tinysplat_amd.Viewer``, the reference's websocket protocol; it is off unless asked for): a pending
-request is rendered between two steps.  Flags the reference's parser has keep its names and defaults.  Needs a GPU: there
-is no CPU path.
+request is rendered between two steps.  ``--eval-holdout N`` keeps every N-th camera (by image name) out of training and
+prints the reference's metrics table for those views - PSNR, SSIM, L1 and the number of Gaussians - every
+``--eval-interval`` steps (default: one epoch of the training cameras) and after the last step; ``--metrics-csv`` also
+appends the rows to a file.  Flags the reference's parser has keep its names and defaults.  Needs a GPU: there is no CPU
+path.
 """
 import argparse
 import sys
@@ -38,11 +41,20 @@ def parse(argv=None):
     ap.add_argument("--viewer", action="store_true", help="serve the scene to a websocket viewer while it trains")
     ap.add_argument("--viewer-ip", type=str, default="127.0.0.1")
     ap.add_argument("--viewer-port", type=int, default=8765)
+    ap.add_argument("--eval-holdout", type=int, default=0,
+                    help="hold every N-th camera (sorted by image name) out of training and evaluate on them; 0: none")
+    ap.add_argument("--eval-interval", type=int, default=None,
+                    help="steps between two evaluations (default: the number of training cameras, one epoch)")
+    ap.add_argument("--metrics-csv", type=str, default=None, help="append the evaluation rows to this CSV file")
     args = ap.parse_args(argv)
     if Path(args.output).suffix.lower() not in WRITERS:
         ap.error(f"--output must end in one of {', '.join(WRITERS)}")
     if args.max_iter < 0 or (args.max_image_dimension is not None and args.max_image_dimension < 1):
         ap.error("--max-iter must not be negative and --max-image-dimension must be at least 1")
+    if args.eval_holdout < 0 or (args.eval_interval is not None and args.eval_interval < 1):
+        ap.error("--eval-holdout must not be negative and --eval-interval must be at least 1")
+    if args.eval_holdout == 0 and (args.eval_interval is not None or args.metrics_csv is not None):
+        ap.error("--eval-interval and --metrics-csv need --eval-holdout")
     return args
 
 
@@ -60,19 +72,39 @@ def main(argv=None):
     print(f"{len(dataset.cameras)} cameras ({sum(dataset.resampled)} resampled), {dataset.pcd.xyz.shape[0]} points, "
           f"extent {dataset.spatial_extent:.3f}")
     model = from_pcd(dataset.pcd, sh_degree=args.sh_degree, device=args.device)
-    densifier = Densifier(model, DensifyConfig(interval_densify=len(dataset.cameras)))      # train.py:277
+    cameras, targets, evaluator = dataset.cameras, dataset.targets, None
+    if args.eval_holdout:
+        from tinysplat_amd import Evaluator, holdout_split
+        from tinysplat_amd.dataset import Targets
+        train, test = holdout_split([c.name for c in cameras], args.eval_holdout)
+        if not train or not test:
+            raise SystemExit(f"--eval-holdout {args.eval_holdout} leaves {len(train)} training and {len(test)} held-out cameras")
+        held = ([cameras[i] for i in test], Targets([targets.images_u8[i] for i in test]))
+        cameras, targets = [cameras[i] for i in train], Targets([targets.images_u8[i] for i in train])
+        evaluator = Evaluator(model, *held, args.device, args.eval_interval or len(cameras),
+                              on_result=lambda row, _result: print(Evaluator.format(row), flush=True),
+                              csv_path=args.metrics_csv)
+        print(f"{len(cameras)} training cameras, {len(test)} held out")
+    densifier = Densifier(model, DensifyConfig(interval_densify=len(cameras)))      # train.py:277
     viewer = None
     if args.viewer:
         from tinysplat_amd import Viewer
         from tinysplat_amd.viewer import ViewRenderer
         viewer = Viewer(ViewRenderer(model, dataset.cameras[0], args.device), args.viewer_ip, args.viewer_port)
         print(f"viewer on ws://{args.viewer_ip}:{viewer.port}")
+    callbacks = [f for f in (evaluator, viewer.service if viewer else None) if f is not None]
+
+    def on_step(step, out):
+        for f in callbacks:
+            f(step, out)
     try:
-        out = fit(model, dataset.cameras, dataset.targets, args.device, args.max_iter, max_sh_degree=args.sh_degree,
-                  densifier=densifier, on_step=viewer.service if viewer else None)
+        out = fit(model, cameras, targets, args.device, args.max_iter, max_sh_degree=args.sh_degree,
+                  densifier=densifier, on_step=on_step if callbacks else None)
     finally:
         if viewer:
             viewer.stop()
+    if evaluator is not None:
+        evaluator.final(args.max_iter)
     if out is not None:
         print(f"step {args.max_iter}: loss {float(out['loss']):.6f}")
     getattr(formats, WRITERS[Path(args.output).suffix.lower()])(model, args.output)
