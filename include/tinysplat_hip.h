@@ -1086,6 +1086,37 @@ int64_t ts_image_metrics_ws_bytes(int32_t height, int32_t width);
 int ts_image_metrics(int32_t height, int32_t width, int32_t pixel_floats, const float* image, const void* target,
                      int32_t target_is_u8, void* ws, double* out4, void* stream);
 
+/* Depth priors: stored dense depth maps scale-matched to the SfM points (csrc/depth_prior_math.h:
+ * the arithmetic, the key's layout, the fit's row and its status codes).  Additive entries: the ABI version is unchanged.
+ * None allocates or synchronises; no atomics, the same bytes on every run.  All pointers are device pointers.
+ * ts_depth_prior_project: `cameras` <= 2^15 cameras whose visible points are spans of one list: offsets int64
+ * [cameras + 1], ascending from 0 to n, a span of at most 2^20 entries; indices int64 [n] into xyz float32 [points, 3] and
+ * errors float64 [points] (an index outside 0 .. points - 1 is a dropped point); cam_f float32 [cameras, 14]: the view
+ * matrix's 3 x 4 top row-major, f_x, f_y; cam_size int32 [cameras, 2]: width, height, width x height < 2^28 - 1.
+ * -> keys int64 [n], z float32 [n], w float64 [n] = 1 / error (0 for a dropped point).
+ * ts_depth_prior_mark: the keys sorted ascending -> flags int64 [n], 1 at the last entry of every (camera, pixel) run.
+ * ts_depth_prior_gather: order int64 [n]: the sort's permutation; running int64 [n]: the inclusive sums of flags; maps:
+ * NULL, or int64 [cameras]: the device address of every camera's float32 dense map (0: none, x = NaN) of map_size int32
+ * [cameras, 2] = rows, columns.  Survivor number j (0-based, in sorted order) -> pixel int32 [j] = py W + px, z [j],
+ * w [j] and, with maps, x float32 [j]: the map sampled at the pixel.  The outputs hold n entries.
+ * ts_depth_prior_fit: one fit per span of offsets int64 [cameras + 1] over x, z float32 and w float64; with disparity != 0
+ * y = 1 / z, else y = z.  fits float64 [cameras, 6] <- {s, t, f(s, t), m, evaluations, status}.
+ * ts_depth_prior_apply: out float32 [height, width] (16-byte aligned) <- float32(s sample + t), or its reciprocal with
+ * disparity != 0, of the map float32 [map_h, map_w] sampled at every pixel; fit: the device address of a fit's row.
+ * TS_E_BADARG, before any launch: a negative count, a NULL or misaligned pointer, a size out of range. */
+int ts_depth_prior_project(int32_t cameras, int64_t n, int64_t points, const int64_t* offsets, const int64_t* indices,
+                           const float* xyz, const double* errors, const float* cam_f, const int32_t* cam_size,
+                           int64_t* keys, float* z, double* w, void* stream);
+int ts_depth_prior_mark(int64_t n, const int64_t* sorted_keys, int64_t* flags, void* stream);
+int ts_depth_prior_gather(int64_t n, const int64_t* sorted_keys, const int64_t* order, const int64_t* flags,
+                          const int64_t* running, const float* z_in, const double* w_in, const int64_t* maps,
+                          const int32_t* map_size, const int32_t* cam_size, int32_t* pixel, float* z, double* w, float* x,
+                          void* stream);
+int ts_depth_prior_fit(int32_t cameras, const int64_t* offsets, const float* x, const float* z, const double* w,
+                       int32_t disparity, double* fits, void* stream);
+int ts_depth_prior_apply(const float* map, int32_t map_h, int32_t map_w, int32_t height, int32_t width, const double* fit,
+                         int32_t disparity, float* out, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

@@ -10,6 +10,7 @@ from .mesh import MeshConfig, TriangleMesh, extract_mesh, vertex_colors
 from .simplify import SimplifyConfig, simplify_mesh
 from .clean import CleanConfig, clean_mesh, mesh_components
 from .dataset import Dataset
+from .depth import DepthPriors, SparseDepth, match_scale, sparse_depth
 from .jpeg import JpegEncoder, encode_jpeg
 from .metrics import EvalResult, Evaluator, evaluate, holdout_split, image_metrics
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
@@ -26,4 +27,5 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "sample_points", "density_loss", "density_parts", "ExtractConfig", "SurfacePoints", "extract_surface_points",
            "level_set_points", "MeshConfig", "TriangleMesh", "extract_mesh", "vertex_colors", "SimplifyConfig",
            "simplify_mesh", "CleanConfig", "clean_mesh", "mesh_components", "Dataset", "Viewer", "encode_jpeg", "JpegEncoder",
-           "image_metrics", "evaluate", "holdout_split", "Evaluator", "EvalResult"]
+           "image_metrics", "evaluate", "holdout_split", "Evaluator", "EvalResult", "DepthPriors", "SparseDepth", "match_scale",
+           "sparse_depth"]

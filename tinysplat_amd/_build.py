@@ -57,6 +57,10 @@ SOURCES = [
     # and must give the same 32 bytes; with no contraction left to the compiler (the filters' fmas are written out) the
     # two cannot round a sum differently
     ("metrics.hip", ["-ffp-contract=off"]),
+    # depth_prior.hip: a point's pixel is rint of a float32 expression that the host build of depth_prior_math.h and the
+    # oracle round operation by operation, and a target is one float32 rounding of a double product and sum; the fit's
+    # residuals are written as fmas on purpose
+    ("depth_prior.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

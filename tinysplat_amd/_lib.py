@@ -239,6 +239,11 @@ SIGNATURES = {
                                  _P, _P]),
     "ts_image_metrics_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ts_image_metrics": (c_int32, [c_int32, c_int32, c_int32, _P, _P, c_int32, _P, _P, _P]),
+    "ts_depth_prior_project": (c_int32, [c_int32, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_depth_prior_mark": (c_int32, [c_int64, _P, _P, _P]),
+    "ts_depth_prior_gather": (c_int32, [c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_depth_prior_fit": (c_int32, [c_int32, _P, _P, _P, _P, c_int32, _P, _P]),
+    "ts_depth_prior_apply": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, _P]),
 }
 
 _lib = None

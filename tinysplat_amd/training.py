@@ -307,18 +307,19 @@ class TrainStep:
             # them in one pair of launches, gradients back as two planes
             values, v_rgb, v_depth = planes_loss_and_gradient(rgb, depth, target_rgb, target_depth, self.lambda_dssim,
                                                               self.lambda_depth)
-            loss, l1, ssim, _ = values.unbind(0)
+            loss, l1, ssim, depth_l1 = values.unbind(0)
             direct = ([rgb] + ([depth] if v_depth is not None else []), [v_rgb] + ([v_depth] if v_depth is not None else []))
         elif (frame is not None and frame.dim() == 3 and frame.shape[2] == 4 and frame.is_contiguous()
                 and extras["depth"]._base is frame):
             # the adapter's one-node path hands out views of ONE [H, W, 4] tensor: evaluate the
             # whole loss (train.py:58-69) on it in place, no slicing / re-packing of image or gradient
-            loss, l1, ssim, _ = frame_loss(frame, target_rgb, target_depth, self.lambda_dssim,
-                                           self.lambda_depth)
+            loss, l1, ssim, depth_l1 = frame_loss(frame, target_rgb, target_depth, self.lambda_dssim,
+                                                  self.lambda_depth)
         else:
             loss, l1, ssim = photometric_loss(rgb, target_rgb, self.lambda_dssim)
             if target_depth is not None:                          # train.py:65-69
-                loss = loss + self.lambda_depth * (extras["depth"] - target_depth).abs().mean()
+                depth_l1 = (extras["depth"] - target_depth).abs().mean()
+                loss = loss + self.lambda_depth * depth_l1
         if terms:                                              # train.py:71-75: loss += lambda * term
             extra = None
             for weight, term in terms.values():
@@ -347,6 +348,8 @@ class TrainStep:
             surface.after_step(self.model, step, self.optimizer, densifier)   # train.py:103-105
         self.optimizer.zero_grad()
         out = {"loss": loss.detach(), "l1": l1, "ssim": ssim, "radii": extras["radii"], "xys_grad": xys_grad}
+        if target_depth is not None:                           # the depth term's value, mean |depth - target|
+            out["depth_l1"] = depth_l1.detach()
         for name, (_, term) in terms.items():
             out[name] = term.detach()
         return out

@@ -3,7 +3,7 @@
 
     python tools/train.py --dataset-dir datasets/train --max-iter 10000 --output scene.ply
 
-The flow of the reference's scripts/train.py without its depth prior: ``Dataset`` reads
+The flow of the reference's scripts/train.py: ``Dataset`` reads
 ``<dataset-dir>/<colmap-path>`` (cameras.bin, images.bin, points3D.bin) and undistorts the images of
 ``<dataset-dir>/<images-path>`` on the GPU, ``from_pcd`` starts the model from the sparse points, ``fit`` trains it
 with densification every ``len(cameras)`` steps (train.py:277), and the result is written as a 3DGS PLY (``.ply``), a
@@ -12,8 +12,12 @@ scene while it trains (``tinysplat_amd.Viewer``, the reference's websocket proto
 request is rendered between two steps.  ``--eval-holdout N`` keeps every N-th camera (by image name) out of training and
 prints the reference's metrics table for those views - PSNR, SSIM, L1 and the number of Gaussians - every
 ``--eval-interval`` steps (default: one epoch of the training cameras) and after the last step; ``--metrics-csv`` also
-appends the rows to a file.  Flags the reference's parser has keep its names and defaults.  Needs a GPU: there is no CPU
-path.
+appends the rows to a file.  ``--regularize-depth`` adds the reference's depth term (train.py:65-69): the monocular depth
+maps ``<dataset-dir>/<depths-path>/<image name>.npy``, made with any model, are scale-matched to the SfM points on the GPU
+(``tinysplat_amd.DepthPriors``) and weigh in with ``--lambda-depth`` from step ``--regularize-depth-start`` to
+``--regularize-depth-end``; a camera without a usable map trains without the term, held-out views get none, and
+``--depth-fits-csv`` writes the table of fits.  Without the flag the run is what it was.  Flags the reference's parser has
+keep its names and defaults.  Needs a GPU: there is no CPU path.
 """
 import argparse
 import sys
@@ -25,8 +29,37 @@ sys.path.insert(0, str(ROOT))
 WRITERS = {".ply": "export_ply", ".pth": "save_checkpoint", ".pt": "save_checkpoint", ".splat": "export_splat"}
 
 
+def _depth_parser():
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    g = ap.add_argument_group("depth prior")
+    g.add_argument("--regularize-depth", action="store_true", help="train with scale-matched monocular depth targets")
+    g.add_argument("--depths-path", type=str, default="depths", help="below --dataset-dir: <image name>.npy per camera")
+    g.add_argument("--lambda-depth", type=float, default=0.2)
+    g.add_argument("--regularize-depth-start", type=int, default=1)
+    g.add_argument("--regularize-depth-end", type=int, default=15000)
+    g.add_argument("--depth-space", choices=("depth", "disparity"), default="depth",
+                   help="what the stored maps hold; disparity: the target is 1 / (s D + t)")
+    g.add_argument("--depth-fits-csv", type=str, default=None, help="write the per-camera fits to this CSV file")
+    return ap
+
+
+def parse_depth(argv=None):
+    """The depth prior's options, a namespace of their own: ``parse`` keeps returning the options it always has."""
+    ap = _depth_parser()
+    args, _rest = ap.parse_known_args(argv)
+    if args.lambda_depth < 0 or args.regularize_depth_start < 1 or args.regularize_depth_end < args.regularize_depth_start:
+        ap.error("--lambda-depth must not be negative, and 1 <= --regularize-depth-start <= --regularize-depth-end")
+    if args.depth_fits_csv is not None and not args.regularize_depth:
+        ap.error("--depth-fits-csv needs --regularize-depth")
+    return args
+
+
 def parse(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    depth_ap = _depth_parser()
+    parse_depth(argv)                                          # checks the depth prior's options
+    _depth, argv = depth_ap.parse_known_args(argv)
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter,
+                                 epilog=depth_ap.format_help().split("\n\n", 1)[-1])
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--max-iter", type=int, default=10_000)
@@ -59,7 +92,7 @@ def parse(argv=None):
 
 
 def main(argv=None):
-    args = parse(argv)
+    args, depth = parse(argv), parse_depth(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: tinysplat_amd has no CPU path")
@@ -73,6 +106,16 @@ def main(argv=None):
           f"extent {dataset.spatial_extent:.3f}")
     model = from_pcd(dataset.pcd, sh_degree=args.sh_degree, device=args.device)
     cameras, targets, evaluator = dataset.cameras, dataset.targets, None
+    depth_targets = depth_schedule = None
+    if depth.regularize_depth:
+        from tinysplat_amd import DepthPriors
+        from tinysplat_amd.training import Scheduler
+        priors = DepthPriors(dataset, dataset.pcd, base / depth.depths_path, space=depth.depth_space)
+        depth_targets = priors.targets
+        depth_schedule = Scheduler(True, depth.regularize_depth_start, depth.regularize_depth_end)
+        print(f"depth priors for {sum(t is not None for t in depth_targets)} of {len(cameras)} cameras")
+        if depth.depth_fits_csv:
+            priors.write_csv(depth.depth_fits_csv)
     if args.eval_holdout:
         from tinysplat_amd import Evaluator, holdout_split
         from tinysplat_amd.dataset import Targets
@@ -81,6 +124,7 @@ def main(argv=None):
             raise SystemExit(f"--eval-holdout {args.eval_holdout} leaves {len(train)} training and {len(test)} held-out cameras")
         held = ([cameras[i] for i in test], Targets([targets.images_u8[i] for i in test]))
         cameras, targets = [cameras[i] for i in train], Targets([targets.images_u8[i] for i in train])
+        depth_targets = None if depth_targets is None else [depth_targets[i] for i in train]
         evaluator = Evaluator(model, *held, args.device, args.eval_interval or len(cameras),
                               on_result=lambda row, _result: print(Evaluator.format(row), flush=True),
                               csv_path=args.metrics_csv)
@@ -98,8 +142,10 @@ def main(argv=None):
         for f in callbacks:
             f(step, out)
     try:
+        extra = {} if depth_targets is None else dict(depth_targets=depth_targets, lambda_depth=depth.lambda_depth,
+                                                      depth_schedule=depth_schedule)
         out = fit(model, cameras, targets, args.device, args.max_iter, max_sh_degree=args.sh_degree,
-                  densifier=densifier, on_step=on_step if callbacks else None)
+                  densifier=densifier, on_step=on_step if callbacks else None, **extra)
     finally:
         if viewer:
             viewer.stop()
@@ -107,6 +153,8 @@ def main(argv=None):
         evaluator.final(args.max_iter)
     if out is not None:
         print(f"step {args.max_iter}: loss {float(out['loss']):.6f}")
+        if depth_targets is not None and "depth_l1" in out:
+            print(f"step {args.max_iter}: depth l1 {float(out['depth_l1']):.6f}")
     getattr(formats, WRITERS[Path(args.output).suffix.lower()])(model, args.output)
     print(f"wrote {args.output}: {Path(args.output).stat().st_size} bytes from {model.num_points} Gaussians")
 
