@@ -55,11 +55,13 @@ typedef struct ts_camera {
     int32_t tile_row0, tile_rows;
     float glob_scale;
     float clip_thresh;
-    /* Tile shape of the LISTS (binning, sorting, compositing): 0 = gsplat's 16x16 tiles; 1 = wide 32x16
-     * tiles, each the union of two horizontally adjacent 16x16 tiles (column pairs 2j, 2j+1; the last one
-     * may be a single column).  Projection, num_tiles_hit / cum_tiles_hit and tile_row0 / tile_rows always
-     * count 16x16 tiles; images and gradients do not depend on the shape (a Gaussian is composited only
-     * into the 16x16 tiles of its tile box either way), only the number of list entries does. */
+    /* Tile shape of the LISTS only (binning, sorting): 0 = gsplat's 16x16 tiles; 1 = wide 32x16 tiles, each the
+     * union of two horizontally adjacent 16x16 tiles (column pairs 2j, 2j+1; the last one may be a single
+     * column).  Compositing always runs one wave per 16x16 tile: with wide lists ts_raster_fwd / _fwd_planes /
+     * _bwd / _bwd_planes need TS_RASTER_NARROW_WAVES (TS_E_BADARG without it).  Projection, num_tiles_hit /
+     * cum_tiles_hit and tile_row0 / tile_rows always count 16x16 tiles; images and gradients do not depend on the
+     * shape (a Gaussian is composited only into the 16x16 tiles of its tile box either way), only the number of
+     * list entries does. */
     int32_t wide_tiles;
     /* bits 0..7: performance hints (formerly `reserved`, 0 = none); results never depend on them.
      * TS_HINT_BALANCED_WALK: a Gaussian covers many tiles (>= ~10 bounding-box tiles on average): ts_bin_scatter
@@ -71,7 +73,7 @@ typedef struct ts_camera {
      * TS_RASTER_SPLIT_BLOCKS replays a cut tile's list as up to S independent one-wave work items (one row per pair,
      * the plain ts_reduce_partials).  Same image; gradients equal to the uncut pass's up to rounding (a segment
      * starts from the forward pass's own transmittance).  Both passes must see the same S and W16.  With
-     * TS_RASTER_SPLIT_BLOCKS, wide tiles or narrow waves ts_raster_bwd* ignores the field.
+     * TS_RASTER_SPLIT_BLOCKS or wide lists ts_raster_bwd* ignores the field.
      * bits 12..15: W16 (TS_CAM_WHOLE_TILES(W16), 0..15) - which tiles are cut: 0 = all of them (launches of fewer
      * tiles than the GPU has SIMDs: instead of TS_RASTER_SPLIT_BLOCKS in the backward pass); 1..15 = a HYBRID
      * launch for full frames: the tiles are handed out in eight bands (one per XCD) and the first W16/16 of every
@@ -297,8 +299,8 @@ int ts_sort_tiles_above_stats(int32_t num_tiles, const int32_t* tile_bins, const
  *   {x, y, opacity, conic.xx | conic.xy, conic.yy, c0, c1 | c2, c3, slot_base(int), bbox_w | bbox_minx << 16 (int)}
  * channels = 3 (colors[n,3]; c3 = 0) or 4 (colors[n,4]; or, with `depths` non-NULL, colors[n,3] and
  * c3 = depths[i]: the RGB + depth frame of rasterize.py:42-51 in one pass).  slot_base/bbox_w locate the
- * (tile,Gaussian) row of the backward partial buffer: slot = slot_base + ty*bbox_w + tx (16x16 tile column tx;
- * a wide tile uses the column of its left half, or of its right half where the box starts there). */
+ * (tile,Gaussian) row of the backward partial buffer: slot = slot_base + ty*bbox_w + tx (16x16 tile column tx,
+ * whatever the shape of the lists). */
 int ts_pack_splats(int32_t n, int32_t channels, int32_t flags, const float* xys, const int32_t* radii,
                    const float* conics, const float* colors, const float* opacity,
                    const int32_t* cum_tiles_hit, const ts_camera* cam_host, const float* depths,
@@ -316,7 +318,8 @@ int ts_pack_splats(int32_t n, int32_t channels, int32_t flags, const float* xys,
  * ts_raster_bwd / ts_reduce_partials the flag makes every (tile, Gaussian) own FOUR partial rows (slot
  * 4 s + block): partials must hold 4 * num_intersects rows and row_flags 4 * num_intersects bytes. */
 #define TS_RASTER_SPLIT_BLOCKS 4
-/* with ts_camera.wide_tiles: keep one wave per 16x16 tile; each walks the list of the wide tile it lies in */
+/* required with ts_camera.wide_tiles != 0 (TS_E_BADARG without it), meaningless otherwise: one wave per 16x16
+ * tile, each walks the list of the wide tile it lies in and skips the Gaussians whose tile box does not hold it */
 #define TS_RASTER_NARROW_WAVES 8
 /* ts_raster_bwd / ts_reduce_partials(_rows): ROW-FLAG GENERATION.  Without it (g = 0) ts_raster_bwd zeroes
  * row_flags and marks the rows it writes with 1.  A caller that keeps ONE row_flags array alive across passes

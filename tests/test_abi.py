@@ -81,6 +81,12 @@ def test_binding_covers_the_header_and_version_matches():
     assert ctypes.sizeof(_lib.TsStripes) == 4 * (_lib.MAX_RANKS + 2)
     assert lib.ts_frame_struct_bytes() == ctypes.sizeof(_lib.TsFrame)
     assert lib.ts_frame_fwd_project(None, None) == -1 and lib.ts_frame_bwd_params(None, None) == -1
+    # the binding's names for the header's flag bits and hints
+    defines = dict(re.findall(r"^#define TS_((?:FRAME|RASTER|HINT)_[A-Z_]+)[ \t]+(\d+|\(1 << \d+\))",
+                              HEADER.read_text(), flags=re.M))
+    assert len(defines) == 17 and defines["RASTER_NARROW_WAVES"] == defines["FRAME_NARROW_WAVES"] == "8"
+    for name, value in defines.items():
+        assert getattr(_lib, name) == eval(value), name
 
 
 def test_argument_errors_are_reported_without_a_gpu():
@@ -146,6 +152,14 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert lib.ts_raster_fwd_sort(3, 8, cam, *([None] * 12)) == -1                             # TS_RASTER_NARROW_WAVES
     assert lib.ts_raster_fwd_sort(3, 0, wide, *([None] * 12)) == -1                            # 32x16 lists
     assert lib.ts_raster_fwd_sort(3, 0, cam, *([None] * 12)) == -1                             # no buffers
+    # 32x16 lists are composited by one wave per 16x16 tile only: the flag is required with them, and its absence is
+    # reported before the early return of a launch with nothing to do (a camera with no tile rows)
+    none = _lib.TsCamera(1, 1, 0, 0, 80, 32, 5, 2, 0, 0, 1.0, 0.01, 1, 0)
+    for flags, want in ((0, -1), (_lib.RASTER_SPLIT_BLOCKS, -1), (_lib.RASTER_NARROW_WAVES, 0)):
+        assert lib.ts_raster_fwd(3, flags, none, *([None] * 9)) == want
+        assert lib.ts_raster_fwd_planes(3, flags, none, *([None] * 10)) == want
+        assert lib.ts_raster_bwd(3, flags, 1, none, *([None] * 12)) == want
+        assert lib.ts_raster_bwd_planes(3, flags, 1, none, *([None] * 8), 0, *([None] * 5)) == want
     assert lib.ts_sort_tiles_above(-1, *([None] * 7)) == -1 and lib.ts_sort_tiles_above(0, *([None] * 7)) == 0
     assert lib.ts_bin_scatter(-1, None, None, None, cam, None, None, None, None) == -1
 

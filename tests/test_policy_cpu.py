@@ -34,6 +34,21 @@ def test_list_shape_follows_pairs_per_tile_and_the_longest_list():
     assert frame._list_mode(0, t1080) == 0                                               # below MANY_TILES_FROM nothing changes
 
 
+def test_a_forced_list_shape_is_0_or_2(monkeypatch):
+    t1080, t4k = 120 * 68, 240 * 135
+    frame._pairs_per_tile[0] = 2490.0                                                    # the policy would say 2 ...
+    monkeypatch.setattr(frame, "WIDE_TILES", 0)
+    assert frame._list_mode(0, t4k) == 0                                                 # ... a forced value wins
+    monkeypatch.setattr(frame, "WIDE_TILES", 2)
+    assert frame._list_mode(0, t1080) == 2
+    for bad in (1, 3, -1, "1", "wide"):              # 1 was the 32x16 compositing wave (profiles/HISTORY.md): removed
+        monkeypatch.setattr(frame, "WIDE_TILES", bad)
+        with pytest.raises(ValueError, match="0, 2 and 'auto'"):
+            frame._list_mode(0, t1080)
+    monkeypatch.setattr(frame, "WIDE_TILES", "auto")
+    assert frame._list_mode(0, t4k) == 2 and frame._list_mode(1, t1080) == 0
+
+
 def test_a_skewed_scene_cuts_most_tiles_of_a_full_frame():
     t1080 = 120 * 68
     frame._pairs_per_tile[0] = 871.0

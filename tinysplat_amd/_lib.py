@@ -17,6 +17,22 @@ LIB_PATH = Path(os.environ["TS_LIB_PATH"]) if os.environ.get("TS_LIB_PATH") else
 ABI_VERSION = 8
 HINT_BALANCED_WALK = 1           # ts_camera.hints: TS_HINT_BALANCED_WALK
 HINT_COOP_SPLIT = 1 << 20        # ts_camera.hints: TS_HINT_COOP_SPLIT
+# the header's TS_RASTER_* and TS_FRAME_* flag bits under the same names (tests/test_abi.py compares them)
+RASTER_LOGIT_OPACITY = 1
+RASTER_CLAMP_RGB = 2
+RASTER_SPLIT_BLOCKS = 4
+RASTER_NARROW_WAVES = 8
+FRAME_TIGHT = 1
+FRAME_SPLIT = 2
+FRAME_NARROW_WAVES = 8
+FRAME_STRIPE = 16
+FRAME_DIRECT_SCATTER = 32
+FRAME_PLANES = 64
+FRAME_SEPARATE_SORT = 128
+FRAME_LIST_STATS = 256
+FRAME_SURVIVORS = 512
+FRAME_GROUP_COUNTS = 1024
+FRAME_ONE_WALK = 2048
 PARTIAL_ROW_FLOATS = 12          # TS_PARTIAL_ROW_FLOATS: floats per (tile, Gaussian) gradient row slot
 
 

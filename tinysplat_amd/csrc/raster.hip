@@ -51,18 +51,13 @@ namespace {
 #include "sort_network.h"
 
 // tuning knobs (overridable with -D for the ablation runs of tools/time_raster.py)
-#ifndef TS_FWD_MIN_WAVES
-#define TS_FWD_MIN_WAVES 1             // __launch_bounds__ 2nd argument = min waves per SIMD
-#endif
 #ifndef TS_FWD_MIN_WAVES_RGB
-#define TS_FWD_MIN_WAVES_RGB 5         // the 16x16, three-channel forward kernel keeps its five waves per SIMD (<= 96 VGPRs)
+#define TS_FWD_MIN_WAVES_RGB 5         // __launch_bounds__ 2nd argument = min waves per SIMD: the three-channel forward kernel
+                                       // with one wave per tile keeps its five waves per SIMD (<= 96 VGPRs)
 #endif
 #ifndef TS_FWD_MIN_WAVES_RGBD
 #define TS_FWD_MIN_WAVES_RGBD 5        // ... and so does the four-channel one since the next chunk's records land in LDS (dma_record):
                                        // the hybrid instantiation spills 160 bytes at chunk level, raster_fwd 327 -> 304 us (round 5)
-#endif
-#ifndef TS_BWD_MIN_WAVES
-#define TS_BWD_MIN_WAVES 1
 #endif
 #ifndef TS_BWD_MIN_WAVES_16
 #define TS_BWD_MIN_WAVES_16 5          // the 16x16 backward kernels at five waves per SIMD (96 VGPRs: 5 - 11 dwords spilled at
@@ -253,13 +248,13 @@ __device__ __forceinline__ bool mask_rect(unsigned long long m, int& xmin, int& 
     return true;
 }
 
-// Tile shapes.  NBX = 8x8 blocks per tile row: 2 -> the 16x16 tile of gsplat's lists (four blocks, four
-// pixels per lane); 4 -> a WIDE 32x16 tile (eight blocks, eight pixels per lane) made of two
-// horizontally adjacent 16x16 tiles whose lists were binned as one (ts_camera.wide_tiles).  A Gaussian
-// that reaches both halves is then listed, staged, reduced over the wave and written as a gradient row
-// ONCE instead of twice: on the random scenes the wide lists hold 0.73x the pairs, and the per-entry
-// cost (the cross-lane reduction of the backward pass above all) shrinks with them, while the number
-// of block bodies - the per-pixel work - is unchanged.  Block k sits at (bx, by) = (k % NBX, k / NBX).
+// Tile shape.  A wave composites the 16x16 tile of gsplat's lists: NBC x NBC 8x8 blocks, four pixels per lane.
+// Block k sits at (bx, by) = (k % NBC, k / NBC).  The LISTS may be those of WIDE 32x16 tiles - two horizontally
+// adjacent 16x16 tiles binned as one (ts_camera.wide_tiles): a Gaussian that reaches both halves is then binned
+// and sorted once instead of twice (0.73x the pairs on the random scenes).  Every 16x16 tile still has a wave of
+// its own, which reads the list of the wide tile it lies in (WL below, TS_RASTER_NARROW_WAVES).  A wave that
+// composites a whole 32x16 tile was built, measured and removed (profiles/HISTORY.md, "wide 32x16 tiles").
+constexpr int NBC = 2, NB = NBC * NBC;
 //
 // gather + exact cull against the NB 8x8 pixel blocks of the tile.
 // rects[k] = sample-position bounding rectangle of the pixels of block k that still matter (all of
@@ -279,7 +274,6 @@ __device__ __forceinline__ Staged stage_fields(const float4 q0, const float4 q1)
     s.mask = 0;
     return s;
 }
-template <int NB>
 __device__ __forceinline__ Staged stage_splat(bool have, const float4 q0, const float4 q1,
                                               const float4* __restrict__ rects, int blocks) {
     Staged s = stage_fields(q0, q1);
@@ -313,17 +307,16 @@ __device__ __forceinline__ Staged stage_splat(bool have, const float4 q0, const 
 
 // Writes rects[k] for the pixels selected by `sel[k]` (one bool per lane and block) and returns the
 // mask of non-empty blocks.  Lane 0 stores; callers fence before reading.
-template <int NBX>
-__device__ __forceinline__ int update_rects(const bool (&sel)[2 * NBX], float X0, float Y0, float4* rects,
+__device__ __forceinline__ int update_rects(const bool (&sel)[NB], float X0, float Y0, float4* rects,
                                             int lane) {
     int blocks = 0;
 #pragma unroll
-    for (int k = 0; k < 2 * NBX; ++k) {
+    for (int k = 0; k < NB; ++k) {
         const unsigned long long m = __ballot(sel[k]);
         int xmin, xmax, ymin, ymax;
         if (mask_rect(m, xmin, xmax, ymin, ymax)) {
             blocks |= (1 << k);
-            const float bx = X0 + (float)(8 * (k % NBX)), by = Y0 + (float)(8 * (k / NBX));
+            const float bx = X0 + (float)(8 * (k % NBC)), by = Y0 + (float)(8 * (k / NBC));
             if (lane == 0)
                 rects[k] = make_float4(bx + (float)xmin, bx + (float)xmax, by + (float)ymin,
                                        by + (float)ymax);
@@ -332,15 +325,13 @@ __device__ __forceinline__ int update_rects(const bool (&sel)[2 * NBX], float X0
     return blocks;
 }
 
-// Blocks of a wide tile a Gaussian may be composited into: gsplat lists a Gaussian in the 16x16 tiles
-// of its tile box only, so a half of the wide tile that lies outside the box [minx, minx + w) must not
-// see it even where its level set reaches in (record: bbox_w | bbox_minx << 16).  Bit NB is kept.
-// WL (16x16 waves reading WIDE lists): the wave's tile column tx must itself lie in the box.
-template <int NBX, bool WL>
+// WL (16x16 waves reading WIDE lists): gsplat lists a Gaussian in the 16x16 tiles of its tile box only, so a half
+// of the wide tile that lies outside the box [minx, minx + w) must not see it even where its level set reaches in
+// (record: bbox_w | bbox_minx << 16) - the wave's tile column tx must itself lie in the box.  All mask bits or none.
+template <bool WL>
 __device__ __forceinline__ int bbox_blocks(int wm, int tx) {
     const int minx = wm >> 16, w = wm & 0xffff;
-    if (NBX == 2) return (!WL || (tx >= minx && tx < minx + w)) ? ~0 : 0;
-    return ((2 * tx >= minx) ? 0x33 : 0) | ((2 * tx + 1 < minx + w) ? 0xCC : 0) | (1 << (2 * NBX));
+    return (!WL || (tx >= minx && tx < minx + w)) ? ~0 : 0;
 }
 
 using mask64 = unsigned long long;
@@ -540,10 +531,10 @@ __device__ __forceinline__ float fwd_update(float ae, float& T, int& fidx, int i
     return vis;
 }
 
-template <int CH, bool GENERAL, int NBX, class Loc>
-__device__ __forceinline__ void fwd_chunk(const float4* __restrict__ lds, int cnt, const float (&fpx)[NBX],
-                                          const float (&fpy)[2], float (&T)[2 * NBX], int (&fidx)[2 * NBX],
-                                          float (&acc)[2 * NBX][CH], Loc& loc TS_SEG_PARAM) {
+template <int CH, bool GENERAL, class Loc>
+__device__ __forceinline__ void fwd_chunk(const float4* __restrict__ lds, int cnt, const float (&fpx)[NBC],
+                                          const float (&fpy)[2], float (&T)[NB], int (&fidx)[NB],
+                                          float (&acc)[NB][CH], Loc& loc TS_SEG_PARAM) {
 #pragma clang fp contract(off)          // as in bwd_chunk: both instantiations must round alike
     constexpr bool LOC = Loc::on;
     TS_WORK(0, cnt);
@@ -561,16 +552,16 @@ __device__ __forceinline__ void fwd_chunk(const float4* __restrict__ lds, int cn
 #endif
         TS_SEG_ADD(ts_seg_, 1, tseg_a);
         TS_SEG_T0(tseg_b);
-        TS_WORK(1, __popc(bm & ((1 << (2 * NBX)) - 1)));
+        TS_WORK(1, __popc(bm & ((1 << NB) - 1)));
 #pragma unroll
-        for (int k = 0; k < 2 * NBX; ++k) {
+        for (int k = 0; k < NB; ++k) {
             if (!(bm & (1 << k))) continue;                           // wave-uniform
             if (TS_ABLATE == 5) { asm volatile("" ::: "memory"); continue; }
             TS_STAT(1, 1);
             // sgl = sigma*log2(e) - log2(opacity), so alpha = exp2(-sgl)
-            const float sgl = sigma_l2(r0.z, r0.w, r1.x, neg_lo, r0.x - fpx[k % NBX], r0.y - fpy[k / NBX]);
+            const float sgl = sigma_l2(r0.z, r0.w, r1.x, neg_lo, r0.x - fpx[k % NBC], r0.y - fpy[k / NBC]);
             if (TS_ABLATE == 8) {          // timing experiment: the exponent's nine instructions once more per body (result unused)
-                float dup = sigma_l2(r0.z, r0.w, r1.x, neg_lo, r0.y - fpx[k % NBX], r0.x - fpy[k / NBX]);
+                float dup = sigma_l2(r0.z, r0.w, r1.x, neg_lo, r0.y - fpx[k % NBC], r0.x - fpy[k / NBC]);
                 dup = __builtin_amdgcn_exp2f(-dup);
                 asm volatile("" ::"v"(dup));
             }
@@ -874,7 +865,7 @@ __device__ __forceinline__ void coop_fwd_tile(
         }
         if (i + 512 < range.y) id_next = from_lds ? (round == 0 ? idr[2] : idr[3]) : ids[i + 512];
         ++round;
-        Staged s = stage_splat<4>(have, q0, q1, rect_sh, live);
+        Staged s = stage_splat(have, q0, q1, rect_sh, live);
         const bool keep = (s.mask & 15) != 0;
         const unsigned long long kmask = __ballot(keep);
         if (keep) {
@@ -996,7 +987,7 @@ __device__ __forceinline__ void coop_fwd_tile(
 // Same list, same arithmetic per pixel; used when a launch has fewer tiles than the GPU has SIMDs (a
 // tile-row stripe of a multi-GPU frame, a small image), where one wave per tile leaves the vector ALUs
 // without a second wave to switch to and the launch takes as long as the longest tile list.
-// WL (NBX == 2 only): the lists are those of wide tiles (ts_camera.wide_tiles) but every 16x16 tile
+// WL: the lists are those of wide tiles (ts_camera.wide_tiles) but every 16x16 tile
 // keeps a wave of its own, which walks the list of the wide tile it belongs to and drops the Gaussians
 // whose tile box does not contain it - binning and sorting at the wide tiles' price, compositing at the
 // register footprint of four pixels per lane.
@@ -1009,16 +1000,15 @@ __device__ __forceinline__ void coop_fwd_tile(
 // mask (bit 4: the general per-pixel code) - at the tile's list offset, and sv_cnt[8 tile] = their number, sv_cnt[8 tile
 // + s] = the number in front of segment boundary s (cut tiles).  sv_id may be bucket_ids: a tile's own sort has read
 // its bucket before the first survivor is written.  raster_bwd_kernel<.., SURV> replays these lists.
-template <int CH, bool SPLIT, int NBX, bool WL, bool SORT = false, bool SEGS = false, bool SURV = false>
-__global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_MIN_WAVES_RGB : TS_FWD_MIN_WAVES_RGBD) : TS_FWD_MIN_WAVES) void raster_fwd_kernel(
+template <int CH, bool SPLIT, bool WL, bool SORT = false, bool SEGS = false, bool SURV = false>
+__global__ __launch_bounds__(kThreads, SPLIT ? 1 : (CH == 3 ? TS_FWD_MIN_WAVES_RGB : TS_FWD_MIN_WAVES_RGBD)) void raster_fwd_kernel(
     const ts_camera cam, const int num_tiles, const int* __restrict__ tile_bins,
     const int* __restrict__ ids_sorted, const int* __restrict__ bucket_ids, const float* __restrict__ depths,
     int* ids_rw, const float4* __restrict__ splats,
     const float* __restrict__ background, float* __restrict__ out_img, float* __restrict__ out_depth,
     float* __restrict__ final_Ts, int* __restrict__ final_index, const int clamp_rgb,
     unsigned char* __restrict__ clamp_mask, int* sv_id, int* sv_meta, int* sv_cnt) {
-    static_assert(!SURV || (!SPLIT && NBX == 2 && !WL), "survivor lists: one wave per 16x16 tile");
-    constexpr int NB = 2 * NBX;
+    static_assert(!SURV || (!SPLIT && !WL), "survivor lists: one wave per 16x16 tile");
     TS_LDS_PAD_DECL();
     __shared__ float4 lds_all[kWaves][64 * 3];
     __shared__ float4 rect_all[kWaves][NB];
@@ -1026,8 +1016,8 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int units = SPLIT ? NB * num_tiles : num_tiles;
     int unit = xcd_tile_group((units + kWaves - 1) / kWaves) * kWaves + wave;
-    constexpr bool kCoop = !SPLIT && NBX == 2 && !WL;
-    if constexpr (!SPLIT && NBX == 2 && !WL) {
+    constexpr bool kCoop = !SPLIT && !WL;
+    if constexpr (!SPLIT && !WL) {
         // hybrid launch: the cut tiles of a band - the ones that also keep their boundary state, the longest items of
         // this launch - are handed out FIRST here (the backward launch hands them out last, as small items); the
         // tiles handed out last - C16 / 16 of a band from its start - are composited by a workgroup each (COOPERATIVE
@@ -1055,15 +1045,15 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     const int only = SPLIT ? unit % NB : -1;
     float4* lds = lds_all[wave];
     float4* rects = rect_all[wave];
-    const int tbx = NBX == 2 ? cam.tile_bounds_x : (cam.tile_bounds_x + 1) >> 1;     // tiles of this shape per row
+    const int tbx = cam.tile_bounds_x;
     const int tx = tile % tbx, ty = tile / tbx + cam.tile_row0;
-    const int px0 = tx * (8 * NBX) + (lane & 7), py0 = ty * 16 + (lane >> 3);
+    const int px0 = tx * 16 + (lane & 7), py0 = ty * 16 + (lane >> 3);
     // sample positions of the lane's pixel in the block columns / the upper and lower block row
-    float fpx[NBX];
+    float fpx[NBC];
 #pragma unroll
-    for (int c = 0; c < NBX; ++c) fpx[c] = (float)(px0 + 8 * c) + ts::kPixOff;
+    for (int c = 0; c < NBC; ++c) fpx[c] = (float)(px0 + 8 * c) + ts::kPixOff;
     const float fpy[2] = {(float)py0 + ts::kPixOff, (float)(py0 + 8) + ts::kPixOff};
-    const float X0 = (float)(tx * (8 * NBX)) + ts::kPixOff, Y0 = (float)(ty * 16) + ts::kPixOff;
+    const float X0 = (float)(tx * 16) + ts::kPixOff, Y0 = (float)(ty * 16) + ts::kPixOff;
     const int W = cam.img_width, H = cam.img_height;
 
     // T > 0: transmittance of an unfinished pixel; T < 0: finished or outside, final value |T|
@@ -1073,7 +1063,7 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     int live = 0;                                   // blocks that still have unfinished pixels
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
-        inside[k] = (px0 + 8 * (k % NBX) < W) && (py0 + 8 * (k / NBX) < H) && (!SPLIT || k == only);
+        inside[k] = (px0 + 8 * (k % NBC) < W) && (py0 + 8 * (k / NBC) < H) && (!SPLIT || k == only);
         T[k] = inside[k] ? 1.0f : -1.0f;
         fidx[k] = 0;
 #pragma unroll
@@ -1088,7 +1078,7 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     if (SORT) {
         // one list per wave, or (SPLIT) per workgroup: its four waves composite the four 8x8 blocks of ONE tile,
         // wave 0 sorts the list and the others wait at the barrier
-        static_assert(!SORT || (!WL && NBX == 2), "16x16 lists");
+        static_assert(!SORT || !WL, "16x16 lists");
         TS_SEG_T0(tseg_s);                // (timeline builds: the sort is segment 3 of the forward kernel)
         const int n = range.y - range.x;
         if (TS_ABLATE == 6 && n <= kWaveSortMax && (!SPLIT || wave == 0)) {      // timing experiment: a copy instead of the sort
@@ -1126,7 +1116,7 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
     // list segments: this pass leaves the per-pixel state at the segment boundaries for the backward pass - in a SPLIT
     // launch for every tile (each of the four waves keeps the pixels of its block), with one wave per tile for the CUT
     // tiles of a hybrid launch (or, W16 = 0, for all of them)
-    constexpr bool kSegsF = SEGS && NBX == 2 && !WL;
+    constexpr bool kSegsF = SEGS && !WL;
     const int S_seg = max(1, min(TS_CAM_SEGS(cam), kSegMax));
     int ck_block = -1;                                               // the tile's checkpoint block, -1 = none
     if (kSegsF && final_Ts != nullptr && S_seg > 1 && range.y - range.x >= kSegMinList)
@@ -1186,12 +1176,12 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
             bool sel[NB];
 #pragma unroll
             for (int k = 0; k < NB; ++k) sel[k] = T[k] > 0.0f;
-            live = update_rects<NBX>(sel, X0, Y0, rects, lane);
+            live = update_rects(sel, X0, Y0, rects, lane);
             TS_WAVE_SYNC();
             if (live == 0) break;
         }
-        Staged s = stage_splat<NB>(have, q0, q1, rects, live);
-        s.mask &= bbox_blocks<NBX, WL>(__float_as_int(q2.w), tx);
+        Staged s = stage_splat(have, q0, q1, rects, live);
+        s.mask &= bbox_blocks<WL>(__float_as_int(q2.w), tx);
         const bool keep = (s.mask & ((1 << NB) - 1)) != 0;
         const unsigned long long mask = __ballot(keep);
         const int cnt = __popcll(mask);
@@ -1213,9 +1203,9 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
         // once per chunk so that the common case runs a loop without those tests
         TS_SEG_ADD(ts_wave_clock_.seg, 0, tseg_p);
         if (general)
-            fwd_chunk<CH, true, NBX>(lds, cnt, fpx, fpy, T, fidx, acc, loc_ TS_SEG_ARG);
+            fwd_chunk<CH, true>(lds, cnt, fpx, fpy, T, fidx, acc, loc_ TS_SEG_ARG);
         else
-            fwd_chunk<CH, false, NBX>(lds, cnt, fpx, fpy, T, fidx, acc, loc_ TS_SEG_ARG);
+            fwd_chunk<CH, false>(lds, cnt, fpx, fpy, T, fidx, acc, loc_ TS_SEG_ARG);
         TS_WAVE_SYNC();
     }
     };
@@ -1247,7 +1237,7 @@ __global__ __launch_bounds__(kThreads, (NBX == 2 && !SPLIT) ? (CH == 3 ? TS_FWD_
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
         if (!inside[k]) continue;
-        const size_t pix = (size_t)(py0 + 8 * (k / NBX) - row_off) * W + (px0 + 8 * (k % NBX));
+        const size_t pix = (size_t)(py0 + 8 * (k / NBC) - row_off) * W + (px0 + 8 * (k % NBC));
         const float Tf = __builtin_fabsf(T[k]);
         if (final_Ts) {             // null in the forward-only (viewer) mode: nothing is kept for backward
             final_Ts[pix] = Tf;
@@ -1451,10 +1441,10 @@ __device__ __forceinline__ void flush_row(float (&v)[6 + CH], int slot_i, long l
 // (ra = 1, fac = 0, v_sig = 0) and changes nothing.
 // `lds`: the chunk's staged records (STAGED RECORD).  Every entry that got a row leaves it parked in its own record;
 // the rows are stored to `partials` when the chunk is done (ROWS THROUGH LDS), and the records are dead on return.
-template <int CH, bool GENERAL, int NBX>
-__device__ __forceinline__ void bwd_chunk(float4* __restrict__ lds, int cnt, const float (&fpx)[NBX],
-                                          const float (&fpy)[2], float (&T)[2 * NBX], float (&R)[2 * NBX],
-                                          const float (&vo)[2 * NBX][CH], const int (&fidx)[2 * NBX],
+template <int CH, bool GENERAL>
+__device__ __forceinline__ void bwd_chunk(float4* __restrict__ lds, int cnt, const float (&fpx)[NBC],
+                                          const float (&fpy)[2], float (&T)[NB], float (&R)[NB],
+                                          const float (&vo)[NB][CH], const int (&fidx)[NB],
                                           float (&acc)[6 + CH], long long num_isects,
                                           float* __restrict__ partials,
                                           unsigned char* __restrict__ row_flags, int lane TS_SEG_PARAM) {
@@ -1483,15 +1473,15 @@ __device__ __forceinline__ void bwd_chunk(float4* __restrict__ lds, int cnt, con
 #endif
         TS_SEG_ADD(ts_seg_, 1, tseg_a);
         TS_SEG_T0(tseg_b);
-        TS_WORK(1, __popc(bm & ((1 << (2 * NBX)) - 1)));
+        TS_WORK(1, __popc(bm & ((1 << NB) - 1)));
 
         int any = 0;
 #pragma unroll
-        for (int k = 0; k < 2 * NBX; ++k) {
+        for (int k = 0; k < NB; ++k) {
             if (!(bm & (1 << k))) continue;                           // wave-uniform
             if (TS_ABLATE == 5) { asm volatile("" ::: "memory"); continue; }
             TS_STAT(3, 1);
-            const float dx = r0.x - fpx[k % NBX], dy = r0.y - fpy[k / NBX];
+            const float dx = r0.x - fpx[k % NBC], dy = r0.y - fpy[k / NBC];
             const float sgl = sigma_l2(r0.z, r0.w, r1.x, neg_lo, dx, dy);
             const float araw = __builtin_amdgcn_exp2f(-sgl);           // opacity * exp(-sigma)
             float a = araw;
@@ -1601,8 +1591,8 @@ constexpr int kBwdWaves = 1;
 // cull, and no rectangles, exact tests or tile-box masks of its own.  A block the forward mask adds beyond what the
 // rectangles of the started pixels would keep finds no valid lane (the body's per-pixel test), so the same rows are
 // written with the same values.
-template <int CH, bool SPLIT, int NBX, bool WL, bool SURV = false>
-__global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS_BWD_MIN_WAVES) void raster_bwd_kernel(
+template <int CH, bool SPLIT, bool WL, bool SURV = false>
+__global__ __launch_bounds__(64 * kBwdWaves, TS_BWD_MIN_WAVES_16) void raster_bwd_kernel(
     const ts_camera cam, const int num_tiles, const long long num_isects,
     const int* __restrict__ tile_bins, const int* __restrict__ ids_sorted,
     const float4* __restrict__ splats, const float* __restrict__ background,
@@ -1611,8 +1601,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
     const float* __restrict__ v_out_alpha, const unsigned char* __restrict__ clamp_mask,
     float* __restrict__ partials, unsigned char* __restrict__ row_flags,
     const int* __restrict__ sv_id, const int* __restrict__ sv_meta, const int* __restrict__ sv_cnt) {
-    static_assert(!SURV || (!SPLIT && NBX == 2 && !WL), "survivor lists: one wave per 16x16 tile");
-    constexpr int NB = 2 * NBX;
+    static_assert(!SURV || (!SPLIT && !WL), "survivor lists: one wave per 16x16 tile");
     TS_LDS_PAD_DECL();
     __shared__ float4 lds_all[kBwdWaves][64 * 4];
     __shared__ float4 rect_all[kBwdWaves][NB];
@@ -1621,7 +1610,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
     // list segments: S work items per cut tile, item `seg` replays the entries [sb, se) of the list; whole tiles (hybrid
     // launch: the first `whole` of every band) are one item.  Work items are handed out band by band: workgroup b
     // runs on XCD b % 8 and takes item b / 8 of band b % 8 - whole tiles first, the small items last
-    constexpr bool kSegs = !SPLIT && NBX == 2 && !WL;
+    constexpr bool kSegs = !SPLIT && !WL;
     const int S_cam = kSegs ? max(1, min(TS_CAM_SEGS(cam), kSegMax)) : 1;
     int S_seg = S_cam, tile, seg = 0, only = -1, ck_block = -1;
     if (kSegs && S_cam > 1) {
@@ -1650,7 +1639,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
         only = SPLIT ? unit % NB : -1;            // SPLIT: this wave owns block `only`, row slot*NB + only
     }
     float4* rects = rect_all[wave];
-    const int tbx = NBX == 2 ? cam.tile_bounds_x : (cam.tile_bounds_x + 1) >> 1;
+    const int tbx = cam.tile_bounds_x;
     const int tx = tile % tbx, ty = tile / tbx + cam.tile_row0;
     const int list = WL ? (ty - cam.tile_row0) * ((tbx + 1) >> 1) + (tx >> 1) : tile;
     const int2 range = reinterpret_cast<const int2*>(tile_bins)[list];
@@ -1672,13 +1661,13 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
     }
     TS_WAVE_CLOCK(1, (int)blockIdx.x * kBwdWaves + wave, se - sb);
     float4* lds = lds_all[wave];
-    const int px0 = tx * (8 * NBX) + (lane & 7), py0 = ty * 16 + (lane >> 3);
+    const int px0 = tx * 16 + (lane & 7), py0 = ty * 16 + (lane >> 3);
     // sample positions of the lane's pixel in the block columns / the upper and lower block row
-    float fpx[NBX];
+    float fpx[NBC];
 #pragma unroll
-    for (int c = 0; c < NBX; ++c) fpx[c] = (float)(px0 + 8 * c) + ts::kPixOff;
+    for (int c = 0; c < NBC; ++c) fpx[c] = (float)(px0 + 8 * c) + ts::kPixOff;
     const float fpy[2] = {(float)py0 + ts::kPixOff, (float)(py0 + 8) + ts::kPixOff};
-    const float X0 = (float)(tx * (8 * NBX)) + ts::kPixOff, Y0 = (float)(ty * 16) + ts::kPixOff;
+    const float X0 = (float)(tx * 16) + ts::kPixOff, Y0 = (float)(ty * 16) + ts::kPixOff;
     const int W = cam.img_width, H = cam.img_height;
     const int row_off = cam.tile_row0 * 16;
 
@@ -1693,7 +1682,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
     int fmax = -1;
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
-        const int px = px0 + 8 * (k % NBX), py = py0 + 8 * (k / NBX);
+        const int px = px0 + 8 * (k % NBC), py = py0 + 8 * (k / NBC);
         const bool inside = (px < W) && (py < H) && (!SPLIT || k == only);
         fidx[k] = -1;
         T[k] = 1.0f;
@@ -1829,10 +1818,10 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
             TS_SEG_ADD(ts_wave_clock_.seg, 0, tseg_p);
             const bool general = __ballot(keep && (mask & (1 << NB))) != 0ull;
             if (general)
-                bwd_chunk<CH, true, NBX>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
+                bwd_chunk<CH, true>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
                                          row_flags, lane TS_SEG_ARG);
             else
-                bwd_chunk<CH, false, NBX>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
+                bwd_chunk<CH, false>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
                                           row_flags, lane TS_SEG_ARG);
             TS_WAVE_SYNC();
         }
@@ -1859,11 +1848,11 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
             bool sel[NB];
 #pragma unroll
             for (int k = 0; k < NB; ++k) sel[k] = fidx[k] >= hi - 63;
-            blocks = update_rects<NBX>(sel, X0, Y0, rects, lane);
+            blocks = update_rects(sel, X0, Y0, rects, lane);
             TS_WAVE_SYNC();
         }
-        Staged s = stage_splat<NB>(have, q0, q1, rects, blocks);
-        s.mask &= bbox_blocks<NBX, WL>(__float_as_int(q2.w), tx);
+        Staged s = stage_splat(have, q0, q1, rects, blocks);
+        s.mask &= bbox_blocks<WL>(__float_as_int(q2.w), tx);
 #pragma unroll
         for (int k = 0; k < NB; ++k)
             if (i > bmax[k]) s.mask &= ~(1 << k);   // nothing in block k got this far in forward
@@ -1873,15 +1862,11 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
         if (keep) {
             const int pos = __popcll(mask & ((1ull << lane) - 1ull));
             // row of this (tile, Gaussian): the slot gsplat's count reserves for the 16x16 tile (column
-            // tx16, row ty) of the Gaussian's tile box; a wide tile uses the slot of its left half, or of
-            // its right half where the box starts there (record: bbox_w | bbox_minx << 16)
-            // SPLIT: one row per (16x16 tile, Gaussian, block of that tile) - block `only` of a wide tile
-            // lies in its half (only % NBX) >> 1 and is block lb of that 16x16 tile
+            // tx, row ty) of the Gaussian's tile box (record: bbox_w | bbox_minx << 16)
+            // SPLIT: one row per (16x16 tile, Gaussian, block of that tile)
             const int wm = __float_as_int(q2.w);
-            const int half = SPLIT ? ((only % NBX) >> 1) : 0;
-            const int tx16 = NBX == 2 ? tx : (SPLIT ? 2 * tx + half : max(2 * tx, wm >> 16));
-            int slot = __float_as_int(q2.z) + ty * (wm & 0xffff) + tx16;
-            if (SPLIT) slot = 4 * slot + (NBX == 2 ? only : ((only % NBX) & 1) + 2 * (only / NBX));
+            int slot = __float_as_int(q2.z) + ty * (wm & 0xffff) + tx;
+            if (SPLIT) slot = 4 * slot + only;
             constexpr int RS = CH == 3 ? 3 : 4;           // see bwd_chunk
             lds[RS * pos] = make_float4(s.gx, s.gy, s.hA, s.B);
             lds[RS * pos + 1] = make_float4(s.hC, s.lo, q1.z, q1.w);
@@ -1894,10 +1879,10 @@ __global__ __launch_bounds__(64 * kBwdWaves, NBX == 2 ? TS_BWD_MIN_WAVES_16 : TS
         TS_SEG_ADD(ts_wave_clock_.seg, 0, tseg_p);
         const bool general = __ballot(keep && (s.mask & (1 << NB))) != 0ull;
         if (general)
-            bwd_chunk<CH, true, NBX>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
+            bwd_chunk<CH, true>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
                                      row_flags, lane TS_SEG_ARG);
         else
-            bwd_chunk<CH, false, NBX>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
+            bwd_chunk<CH, false>(lds, cnt, fpx, fpy, T, R, vo, fidx, acc, num_isects, partials,
                                       row_flags, lane TS_SEG_ARG);
         TS_WAVE_SYNC();
     }
@@ -2072,37 +2057,36 @@ int ts_raster_fwd_planes(int32_t channels, int32_t flags, const ts_camera* cam, 
                          float* out_img, float* out_depth, float* final_Ts, int32_t* final_index,
                          uint8_t* clamp_mask, void* stream) {
     if (!cam || (channels != 3 && channels != 4) || (out_depth && channels != 4)) return TS_E_BADARG;
-    const bool narrow = cam->wide_tiles != 0 && (flags & TS_RASTER_NARROW_WAVES) != 0;   // 16x16 waves, wide lists
+    const bool narrow = cam->wide_tiles != 0;                   // 16x16 waves, wide lists: the one mapping for them
+    if (narrow && !(flags & TS_RASTER_NARROW_WAVES)) return TS_E_BADARG;
     const int nt = narrow ? cam->tile_rows * cam->tile_bounds_x : ts_num_tiles(cam);
     if (nt <= 0) return 0;
     if (!tile_bins || !background || !out_img || (!final_Ts != !final_index)) return TS_E_BADARG;
     bool split = (flags & TS_RASTER_SPLIT_BLOCKS) != 0;
-    const bool wide = cam->wide_tiles != 0 && !narrow;
     ts_camera kcam = *cam;
     kcam.hints &= ~kHintCoopAll;
-    if (split && !wide && !narrow && (cam->hints & TS_HINT_COOP_SPLIT)) {
+    if (split && !narrow && (cam->hints & TS_HINT_COOP_SPLIT)) {
         split = false;                          // four waves per tile with SHARED staging instead (COOPERATIVE TILES)
         kcam.hints |= kHintCoopAll;
     }
-    const int units = split ? (wide ? 8 : 4) * nt : nt;
+    const int units = split ? 4 * nt : nt;
     int grid = 8 * (((units + kWaves - 1) / kWaves + 7) / 8);      // see xcd_tile_group
     hipStream_t s = (hipStream_t)stream;
     const float4* sp = reinterpret_cast<const float4*>(splats);
     const int clamp = (flags & TS_RASTER_CLAMP_RGB) ? 1 : 0;
     // list segments (ts_camera.hints bits 8..11): a launch on 16x16 lists also keeps the boundary state of the cut tiles
-    const bool segs = !wide && !narrow && final_Ts && TS_CAM_SEGS(*cam) > 1;
-    if (!split && !wide && !narrow) grid = fwd_plan(nt, kcam.hints, segs, true).grid();      // COOPERATIVE TILES
-#define TS_LAUNCH_FWD(C, S, X, L, G)                                                               \
-    hipLaunchKernelGGL((raster_fwd_kernel<C, S, X, L, false, G>), dim3(grid), dim3(kThreads), 0, s, kcam, nt, \
+    const bool segs = !narrow && final_Ts && TS_CAM_SEGS(*cam) > 1;
+    if (!split && !narrow) grid = fwd_plan(nt, kcam.hints, segs, true).grid();      // COOPERATIVE TILES
+#define TS_LAUNCH_FWD(C, S, L, G)                                                                  \
+    hipLaunchKernelGGL((raster_fwd_kernel<C, S, L, false, G>), dim3(grid), dim3(kThreads), 0, s, kcam, nt, \
                        tile_bins, gaussian_ids_sorted, (const int*)nullptr, (const float*)nullptr,   \
                        (int*)nullptr, sp, background, out_img, out_depth, final_Ts,                  \
                        final_index, clamp, clamp ? clamp_mask : nullptr, (int*)nullptr, (int*)nullptr, (int*)nullptr)
 #define TS_LAUNCH_FWD_X(C, S)                                                                      \
     do {                                                                                           \
-        if (wide) TS_LAUNCH_FWD(C, S, 4, false, false);                                            \
-        else if (narrow) TS_LAUNCH_FWD(C, S, 2, true, false);                                      \
-        else if (segs) TS_LAUNCH_FWD(C, S, 2, false, true);                                        \
-        else TS_LAUNCH_FWD(C, S, 2, false, false);                                                 \
+        if (narrow) TS_LAUNCH_FWD(C, S, true, false);                                              \
+        else if (segs) TS_LAUNCH_FWD(C, S, false, true);                                           \
+        else TS_LAUNCH_FWD(C, S, false, false);                                                    \
     } while (0)
     if (channels == 3) { if (split) TS_LAUNCH_FWD_X(3, true); else TS_LAUNCH_FWD_X(3, false); }
     else { if (split) TS_LAUNCH_FWD_X(4, true); else TS_LAUNCH_FWD_X(4, false); }
@@ -2176,7 +2160,7 @@ int raster_fwd_sort(int32_t channels, int32_t flags, const ts_camera* cam, const
     int* sv_cnt = survivors;
     int* sv_meta = survivors ? survivors + survivor_counts(nt) : nullptr;
 #define TS_LAUNCH_FWD_SORT(C, S, G, V)                                                                            \
-    hipLaunchKernelGGL((raster_fwd_kernel<C, S, 2, false, true, G, V>), dim3(grid), dim3(kThreads), 0, s, kcam, nt, \
+    hipLaunchKernelGGL((raster_fwd_kernel<C, S, false, true, G, V>), dim3(grid), dim3(kThreads), 0, s, kcam, nt,    \
                        tile_bins, (const int*)nullptr, bucket_ids, depths, gaussian_ids_sorted, sp, background, \
                        out_img, out_depth, final_Ts, final_index, clamp, clamp ? clamp_mask : nullptr, sv_id, sv_meta, \
                        sv_cnt)
@@ -2210,7 +2194,8 @@ int raster_bwd(int32_t channels, int32_t flags, int64_t num_intersects, const ts
     if (survivors && (!bucket_ids || (flags & (TS_RASTER_SPLIT_BLOCKS | TS_RASTER_NARROW_WAVES)) || cam->wide_tiles))
         return TS_E_BADARG;
     if (planes ? channels != 4 : v_out_depth != nullptr) return TS_E_BADARG;
-    const bool narrow = cam->wide_tiles != 0 && (flags & TS_RASTER_NARROW_WAVES) != 0;
+    const bool narrow = cam->wide_tiles != 0;                   // see ts_raster_fwd_planes
+    if (narrow && !(flags & TS_RASTER_NARROW_WAVES)) return TS_E_BADARG;
     const int nt = narrow ? cam->tile_rows * cam->tile_bounds_x : ts_num_tiles(cam);
     if (nt <= 0 || num_intersects == 0) return 0;
     if (!tile_bins || !gaussian_ids_sorted || !splats || !background || !final_Ts || !final_index ||
@@ -2218,7 +2203,6 @@ int raster_bwd(int32_t channels, int32_t flags, int64_t num_intersects, const ts
         return TS_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const bool split = (flags & TS_RASTER_SPLIT_BLOCKS) != 0;
-    const bool wide = cam->wide_tiles != 0 && !narrow;
     // row flags: legacy = zero the array, rows written in this pass get 1; with TS_RASTER_FLAG_GEN(g) the caller keeps
     // ONE flag array alive across passes and hands every pass a fresh value g in 1..255 (zeroing the array itself
     // when the values wrap) - no 1-byte-per-pair memset per frame
@@ -2230,29 +2214,28 @@ int raster_bwd(int32_t channels, int32_t flags, int64_t num_intersects, const ts
     const long long isects_tagged = (long long)(((unsigned long long)(gen ? gen : 1) << 56) |
                                                 ((unsigned long long)num_intersects & 0x00ffffffffffffffull));
     if (TS_CAM_SEGS(*cam) < 0 || TS_CAM_SEGS(*cam) > kSegMax) return TS_E_BADARG;
-    const int segs = (!split && !wide && !narrow && TS_CAM_SEGS(*cam) > 1) ? TS_CAM_SEGS(*cam) : 1;
+    const int segs = (!split && !narrow && TS_CAM_SEGS(*cam) > 1) ? TS_CAM_SEGS(*cam) : 1;
     int grid;
     if (segs > 1) {                       // band by band, whole tiles first (see raster_bwd_kernel)
         const CutTiles m = cut_tiles(nt, cam->hints);
         grid = 8 * ((m.items(segs) + kBwdWaves - 1) / kBwdWaves);
     } else {
-        const int units = split ? (wide ? 8 : 4) * nt : nt;
+        const int units = split ? 4 * nt : nt;
         grid = 8 * (((units + kBwdWaves - 1) / kBwdWaves + 7) / 8);            // see xcd_tile_group
     }
     const float4* sp = reinterpret_cast<const float4*>(splats);
     const int* sv_cnt = survivors;
     const int* sv_meta = survivors ? survivors + survivor_counts(nt) : nullptr;
-#define TS_LAUNCH_BWD(C, S, X, L, V)                                                               \
-    hipLaunchKernelGGL((raster_bwd_kernel<C, S, X, L, V>), dim3(grid), dim3(64 * kBwdWaves), 0, s, *cam, nt, \
+#define TS_LAUNCH_BWD(C, S, L, V)                                                                  \
+    hipLaunchKernelGGL((raster_bwd_kernel<C, S, L, V>), dim3(grid), dim3(64 * kBwdWaves), 0, s, *cam, nt, \
                        isects_tagged, tile_bins, gaussian_ids_sorted, sp, background,              \
                        final_Ts, final_index, v_out_img, v_out_depth, planes ? 1 : 0, v_out_alpha,  \
                        clamp_mask, partials, row_flags, bucket_ids, sv_meta, sv_cnt)
 #define TS_LAUNCH_BWD_X(C, S)                                                                      \
     do {                                                                                           \
-        if (wide) TS_LAUNCH_BWD(C, S, 4, false, false);                                            \
-        else if (narrow) TS_LAUNCH_BWD(C, S, 2, true, false);                                      \
-        else if (survivors) TS_LAUNCH_BWD(C, false, 2, false, true);       /* (never split) */     \
-        else TS_LAUNCH_BWD(C, S, 2, false, false);                                                 \
+        if (narrow) TS_LAUNCH_BWD(C, S, true, false);                                              \
+        else if (survivors) TS_LAUNCH_BWD(C, false, false, true);          /* (never split) */     \
+        else TS_LAUNCH_BWD(C, S, false, false);                                                    \
     } while (0)
     if (channels == 3) { if (split) TS_LAUNCH_BWD_X(3, true); else TS_LAUNCH_BWD_X(3, false); }
     else { if (split) TS_LAUNCH_BWD_X(4, true); else TS_LAUNCH_BWD_X(4, false); }

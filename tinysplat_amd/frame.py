@@ -151,11 +151,9 @@ def backward_segments(cam, segs: int, total: int, dev_index: int = 0) -> int:
 # config 5 (5 M, 4K) 5.71 -> 5.01 ms, 5.03 -> 4.33 ms in Morton order (sort 0.94 -> 0.55, scatter 0.88 -> 0.70,
 # count 0.23 -> 0.13 ms; compositing +1 %); config 3 1.316 -> 1.305 ms (sort 79 -> 64 us, scatter 64 -> 48 us,
 # offsets 27 -> 19 us against raster_bwd 545 -> 566 us for the longer lists it stages).
-# Mode 1 also gives each wave the whole wide tile (eight pixels per lane: the "super-tile" mapping, one
-# butterfly reduction and one gradient row per Gaussian and wide tile): built, bit-identical, and slower -
-# raster_fwd 0.25 -> 0.39 ms, raster_bwd 0.55 -> 0.71 ms on config 3, because 150-170 VGPRs leave 3 waves per
-# SIMD instead of 4-5.  The drop-in op keeps gsplat's 16x16 lists.
-# TS_WIDE_TILES = 0 | 1 | 2 | auto (default): mode 2 where the lists are long - the previous frame on the
+# A mode 1, in which one wave composited the whole wide tile, was built, measured slower and removed
+# (profiles/HISTORY.md, "wide 32x16 tiles").  The drop-in op keeps gsplat's 16x16 lists.
+# TS_WIDE_TILES = 0 | 2 | auto (default): mode 2 where the lists are long - the previous frame on the
 # device averaged >= WIDE_LISTS_FROM bounding-box pairs per 16x16 tile (config 5: 2 490; config 3: 766).  The
 # threshold was 1 000 until the hybrid backward launch and the cooperative forward tiles (16x16 lists only) existed;
 # with them mode 0 wins up to ~2 200 pairs per tile (tools/list_mode_check.sh: 1 M / 2 M at 1280x720 0.96 -> 0.92,
@@ -163,7 +161,7 @@ def backward_segments(cam, segs: int, total: int, dev_index: int = 0) -> int:
 # mode 0 otherwise; a first frame goes by its tile count (4K-class frames start wide).  Modes 0 and 2 run the
 # same per-tile arithmetic on the same Gaussians in the same order, so switching never changes a result.
 _wt = os.environ.get("TS_WIDE_TILES", "auto")
-WIDE_TILES = _wt if _wt == "auto" else int(_wt)
+WIDE_TILES = int(_wt) if _wt.lstrip("+-").isdigit() else _wt      # checked by _list_mode: tests and tools assign it too
 WIDE_LISTS_FROM = int(os.environ.get("TS_WIDE_LISTS_FROM", "2300"))
 BALANCED_WALK_FROM = float(os.environ.get("TS_BALANCED_WALK_FROM", "10"))     # bounding-box tiles per Gaussian
 _pairs_per_tile = {}    # device index -> bounding-box pairs per 16x16 tile of the most recent frame
@@ -189,6 +187,8 @@ _longest_list = {}      # device index -> (longest list of the most recent frame
 
 def _list_mode(dev_index: int, tiles16: int) -> int:
     if WIDE_TILES != "auto":
+        if WIDE_TILES not in (0, 2):
+            raise ValueError(f"TS_WIDE_TILES / frame.WIDE_TILES = {WIDE_TILES!r}: accepted values are 0, 2 and 'auto'")
         return int(WIDE_TILES)
     prev = _pairs_per_tile.get(dev_index)
     if prev is None:
@@ -464,16 +464,18 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
         # a proper stripe of the frame (one rank of a multi-GPU frame): TS_FRAME_STRIPE
         stripe = STRIPE_SPARSE and cam.tile_rows < cam.tile_bounds_y
         full = cam.tile_rows == cam.tile_bounds_y
-        fr.flags = ((1 if TIGHT_BINNING else 0) | (2 if F.split else 0) | (8 if mode == 2 else 0) | (16 if stripe else 0)
-                    | (0 if TWO_HOP_SCATTER else 32) | (64 if F.planes else 0) | (0 if INLINE_SORT else 128)
-                    | (256 if full else 0))                             # TS_FRAME_LIST_STATS (the slot holds four words)
+        fr.flags = ((_lib.FRAME_TIGHT if TIGHT_BINNING else 0) | (_lib.FRAME_SPLIT if F.split else 0)
+                    | (_lib.FRAME_NARROW_WAVES if mode == 2 else 0) | (_lib.FRAME_STRIPE if stripe else 0)
+                    | (0 if TWO_HOP_SCATTER else _lib.FRAME_DIRECT_SCATTER) | (_lib.FRAME_PLANES if F.planes else 0)
+                    | (0 if INLINE_SORT else _lib.FRAME_SEPARATE_SORT)
+                    | (_lib.FRAME_LIST_STATS if full else 0))           # (the slot holds four words)
         surv = SURVIVORS and keep and full and mode == 0 and not F.split and INLINE_SORT
         if surv:
-            fr.flags |= 512                                               # TS_FRAME_SURVIVORS
+            fr.flags |= _lib.FRAME_SURVIVORS
         if GROUP_COUNTS:
-            fr.flags |= 1024                                              # TS_FRAME_GROUP_COUNTS (the executor decides where it applies)
+            fr.flags |= _lib.FRAME_GROUP_COUNTS                           # (the executor decides where it applies)
         if ONE_WALK:
-            fr.flags |= 2048                                              # TS_FRAME_ONE_WALK (the executor decides where it applies)
+            fr.flags |= _lib.FRAME_ONE_WALK                               # (the executor decides where it applies)
         if full:
             _stats_mode[dev.index] = mode
         fr.cam = cam

@@ -541,8 +541,9 @@ def _stripe_stage(lib, s, dev, layout: ShardLayout, records: Tensor, background:
     host, event, lock = _frame._total_slot(dev)
     fr = TsFrame()
     fr.n, fr.num_bases, fr.sh_degree, fr.channels = m, 1, 0, ch
-    fr.flags = ((1 if _frame.TIGHT_BINNING else 0) | (2 if S.split else 0) | (8 if S.mode == 2 else 0)
-                | (0 if _frame.TWO_HOP_SCATTER else 32))
+    fr.flags = ((_lib.FRAME_TIGHT if _frame.TIGHT_BINNING else 0) | (_lib.FRAME_SPLIT if S.split else 0)
+                | (_lib.FRAME_NARROW_WAVES if S.mode == 2 else 0)
+                | (0 if _frame.TWO_HOP_SCATTER else _lib.FRAME_DIRECT_SCATTER))
     fr.cam, fr.capacity = cam, -1
     fr.background = S.bg.data_ptr()
     fr.xys, fr.depths, fr.radii, fr.num_tiles_hit, fr.cum_tiles_hit, fr.splats = ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], ptr[5]
@@ -775,8 +776,9 @@ class _RankState:
         self.bucket = torch.empty((2 * self.list_cap,), **i32)
         fs = TsFrame()
         fs.n, fs.num_bases, fs.sh_degree, fs.channels = m, 1, 0, ch
-        fs.flags = ((1 if _frame.TIGHT_BINNING else 0) | (2 if self.split else 0) | (8 if self.mode == 2 else 0)
-                    | (0 if _frame.TWO_HOP_SCATTER else 32))
+        fs.flags = ((_lib.FRAME_TIGHT if _frame.TIGHT_BINNING else 0) | (_lib.FRAME_SPLIT if self.split else 0)
+                    | (_lib.FRAME_NARROW_WAVES if self.mode == 2 else 0)
+                    | (0 if _frame.TWO_HOP_SCATTER else _lib.FRAME_DIRECT_SCATTER))
         fs.cam = self.s_cam
         fs.xys, fs.depths, fs.radii, fs.num_tiles_hit, fs.cum_tiles_hit, fs.splats = ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], ptr[5]
         fs.scan_ws, fs.bin_ws, fs.tile_bins = ptr[6], ptr[7], ptr[8]
