@@ -95,7 +95,10 @@ def _binning_case(n, w, h, seed, mult):
 def test_binning_bit_exact(n, w, h, seed, mult):
     """tile_bins and gaussian_ids_sorted equal the stable (tile, depth-bits) sort of the oracle.
     Tile sizes span the register network (<= 1024 keys), the per-tile sample sort with 256 samples
-    (60000 / 40000 cases: ~1.5k-5k keys per tile) and with 1024 samples (200000 case: > 8192)."""
+    (60000 / 40000 cases: ~1.5k-5k keys per tile) and with 1024 samples (200000 case: > 8192).
+    The list lengths are whatever the scenes give: the lengths at which the sort changes its form (64, 128, ... 1024,
+    4096, 8192, 49152), every E of the networks and the sample sort's oversized sub-buckets (the global-memory network,
+    which no random bucket order reaches) are pinned by tests/test_gpu_sort_forms.py."""
     _, _, f = _binning_case(n, w, h, seed, mult)
     xys, depths, radii, nth = f["xys"].detach(), f["depths"].detach(), f["radii"], f["nth"]
     tb = tile_bounds((w, h))
