@@ -918,6 +918,44 @@ int ts_mesh_emit(int32_t bricks, const int64_t* brick_ids, const float* grid_hos
                  float level, const float* density, const int64_t* offsets, int64_t* keys, float* positions,
                  int64_t* cells, void* stream);
 
+/* Truncated signed distance fusion of depth maps on the same brick grid (csrc/tsdf_math.h).
+ * Additive entries: the ABI version is unchanged.  None allocates or synchronises; all are deterministic (plain
+ * stores, no atomics).  camera_table: device memory, `cameras` records of struct ts_tsdf_camera (csrc/tsdf_math.h,
+ * ts_tsdf_camera_bytes() bytes each, 8-byte aligned): the view matrix's 3 x 4 top, rows 0, 1 and 3 of proj @ view, six
+ * culling planes {n xyz, d, |n|}, width, height and the device pointer of the float32 [height, width] map of view-space
+ * z (not finite or <= 0: no depth).  trunc > 0 in world units; depth_max > 0 (+inf: no limit).
+ * ts_tsdf_mark: flags uint8 [number of bricks] (zeroed by the caller) <- 1 for every brick that touches the box of a
+ * pixel's frustum piece (its four corner rays at the depths d and d + trunc, in double), widened by one cell edge;
+ * max_pixels: the largest width * height of the table.  TS_E_BADARG: cameras outside 1..65535, max_pixels outside
+ * 1..2^31 - 1, a bad grid, trunc or depth_max, a NULL pointer.
+ * ts_tsdf_chunk_bytes: the bytes of one chunk of `bricks` bricks: 256-byte aligned sums (double), counts (int32) and
+ * field (float32) of bricks * 729 corners, and per brick a triangle count (int32) and an offset (int64).  TS_E_BADARG:
+ * bricks < 1 or bricks * 729 >= 2^31.
+ * ts_tsdf_integrate: sum double [bricks * 729] and count int32 [bricks * 729] (zeroed by the caller before the first
+ * batch) += the observations min(1, (d - z) / trunc) of the cameras [c0, c1) of the table at every corner of the listed
+ * bricks, in the table's order; a corner beyond the grid's last cell observes nothing.  One workgroup of 256 threads per
+ * brick; flags: TS_TSDF_NO_CULL projects every corner for every camera instead of testing the brick's bounding sphere
+ * against the camera first (the same result).  c0 == c1: returns 0, launches nothing.  TS_E_BADARG: bricks out of range,
+ * a bad grid, c0 < 0, c1 < c0, a bad trunc, znear or depth_max, an unknown flag, a NULL or misaligned pointer.
+ * ts_tsdf_field: field float32 [bricks * 729] <- -(float)(sum / count), NaN where count < min_observations (>= 1).
+ * ts_mesh_count_observed, ts_mesh_emit_observed: ts_mesh_count and ts_mesh_emit over a field that may hold NaN: a cell
+ * with a NaN corner emits nothing; everything else as there. */
+#define TS_TSDF_NO_CULL 1
+int32_t ts_tsdf_camera_bytes(void);
+int ts_tsdf_mark(int32_t cameras, const void* camera_table, int64_t max_pixels, const float* grid_host,
+                 const int32_t* cells_host, float trunc, float depth_max, uint8_t* flags, void* stream);
+int64_t ts_tsdf_chunk_bytes(int32_t bricks);
+int ts_tsdf_integrate(int32_t bricks, const int64_t* brick_ids, const float* grid_host, const int32_t* cells_host,
+                      const void* camera_table, int32_t c0, int32_t c1, float trunc, float znear, float depth_max,
+                      int32_t flags, double* sum, int32_t* count, void* stream);
+int ts_tsdf_field(int32_t bricks, const double* sum, const int32_t* count, int32_t min_observations, float* field,
+                  void* stream);
+int ts_mesh_count_observed(int32_t bricks, const int64_t* brick_ids, const float* grid_host, const int32_t* cells_host,
+                           float level, const float* field, int32_t* counts, void* stream);
+int ts_mesh_emit_observed(int32_t bricks, const int64_t* brick_ids, const float* grid_host, const int32_t* cells_host,
+                          float level, const float* field, const int64_t* offsets, int64_t* keys, float* positions,
+                          int64_t* cells, void* stream);
+
 /* The colour of points of the same density field from the Gaussians' spherical harmonics.  An
  * additive entry: the ABI version is unchanged.  points float32 [m,3] with their own neighbours knn int32
  * [m, TS_EXTRACT_K] (ts_knn's: ascending in distance), normals float32 [m,3] (unit, outward) or NULL, records as

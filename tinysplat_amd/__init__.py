@@ -13,6 +13,7 @@ from .dataset import Dataset
 from .depth import DepthPriors, SparseDepth, match_scale, sparse_depth
 from .jpeg import JpegEncoder, encode_jpeg
 from .metrics import EvalResult, Evaluator, evaluate, holdout_split, image_metrics
+from .fusion import FusionConfig, extract_mesh_tsdf, fuse_depth_maps, render_depth_alpha
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
 from .rasterizer import GaussianRasterizer
 from .scene import Scene
@@ -28,4 +29,4 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "level_set_points", "MeshConfig", "TriangleMesh", "extract_mesh", "vertex_colors", "SimplifyConfig",
            "simplify_mesh", "CleanConfig", "clean_mesh", "mesh_components", "Dataset", "Viewer", "encode_jpeg", "JpegEncoder",
            "image_metrics", "evaluate", "holdout_split", "Evaluator", "EvalResult", "DepthPriors", "SparseDepth", "match_scale",
-           "sparse_depth"]
+           "sparse_depth", "FusionConfig", "fuse_depth_maps", "render_depth_alpha", "extract_mesh_tsdf"]

@@ -61,6 +61,10 @@ SOURCES = [
     # oracle round operation by operation, and a target is one float32 rounding of a double product and sum; the fit's
     # residuals are written as fmas on purpose
     ("depth_prior.hip", ["-ffp-contract=off"]),
+    # tsdf.hip: a corner's pixel is rint of a float32 expression and its observation a float32 difference and quotient
+    # that the host build of tsdf_math.h rounds operation by operation; an fma would move a corner across a pixel border
+    # in one brick and not in its neighbour's host restatement, and the corner positions are mesh.hip's, bit for bit
+    ("tsdf.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

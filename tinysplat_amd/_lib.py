@@ -110,6 +110,15 @@ class TsRankStep(ctypes.Structure):
 
 _RANK = POINTER(TsRankStep)
 
+TSDF_NO_CULL = 1                 # TS_TSDF_NO_CULL
+TSDF_PLANES = 6                  # TS_TSDF_PLANES, of TS_TSDF_PLANE_FLOATS = 5 floats each
+
+
+class TsTsdfCamera(ctypes.Structure):
+    """struct ts_tsdf_camera of csrc/tsdf_math.h: one record of the fusion's device table."""
+    _fields_ = [("view", c_float * 12), ("proj", c_float * 12), ("planes", c_float * (TSDF_PLANES * 5)),
+                ("width", c_int32), ("height", c_int32), ("depth", c_void_p)]
+
 ENTRY_PROBE = ctypes.CFUNCTYPE(None, ctypes.c_char_p, c_int32, c_void_p)      # ts_entry_probe
 
 # name -> (restype, argtypes); mirrors include/tinysplat_hip.h declaration by declaration
@@ -230,6 +239,14 @@ SIGNATURES = {
     "ts_mesh_density": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ts_mesh_count": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P, _P]),
     "ts_mesh_emit": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P]),
+    "ts_tsdf_camera_bytes": (c_int32, []),
+    "ts_tsdf_mark": (c_int32, [c_int32, _P, c_int64, _P, _P, c_float, c_float, _P, _P]),
+    "ts_tsdf_chunk_bytes": (c_int64, [c_int32]),
+    "ts_tsdf_integrate": (c_int32, [c_int32, _P, _P, _P, _P, c_int32, c_int32, c_float, c_float, c_float, c_int32, _P, _P,
+                                    _P]),
+    "ts_tsdf_field": (c_int32, [c_int32, _P, _P, c_int32, _P, _P]),
+    "ts_mesh_count_observed": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P, _P]),
+    "ts_mesh_emit_observed": (c_int32, [c_int32, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P]),
     "ts_field_colors": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P]),
     "ts_simplify_count": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
     "ts_simplify_keys": (c_int32, [c_int32, _P, _P, _P, _P, _P]),
@@ -298,6 +315,8 @@ def load() -> ctypes.CDLL:
         raise HipLibraryError("struct ts_frame: the ctypes mirror does not match the library's layout")
     if lib.ts_rank_step_struct_bytes() != ctypes.sizeof(TsRankStep):
         raise HipLibraryError("struct ts_rank_step: the ctypes mirror does not match the library's layout")
+    if lib.ts_tsdf_camera_bytes() != ctypes.sizeof(TsTsdfCamera):
+        raise HipLibraryError("struct ts_tsdf_camera: the ctypes mirror does not match the library's layout")
     _lib = lib
     return lib
 

@@ -15,6 +15,7 @@
 //   emit      (mesh_cells.h), an exclusive prefix over the workgroup (ballots of the count's four bits inside a wave,
 //             LDS across the eight waves); count stores the brick total, emit the triangles at offsets[brick] + prefix:
 //             three edge keys and three interpolated positions each, in (brick, cell, tetrahedron, triangle) order.
+//   observed  count and emit over a field with NaN corners (section 6p, tsdf.hip): a cell with one emits nothing.
 // Plain stores only: every output is a fixed function of the inputs.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -135,7 +136,8 @@ __global__ __launch_bounds__(kThreads) void density_kernel(int n, int64_t total,
     density[e] = d;
 }
 
-template <bool kEmit>
+// kObserved (section 6p): the field may hold NaN (a corner nothing observed), and a cell with such a corner emits nothing
+template <bool kEmit, bool kObserved = false>
 __global__ __launch_bounds__(kCells) void cells_kernel(Grid g, float level, const int64_t* __restrict__ bricks,
                                                        const float* __restrict__ density, int32_t* __restrict__ counts,
                                                        const int64_t* __restrict__ offsets, int64_t* __restrict__ keys,
@@ -156,6 +158,12 @@ __global__ __launch_bounds__(kCells) void cells_kernel(Grid g, float level, cons
     if (inside) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) above |= (corner_d(k) > level ? 1u : 0u) << k;
+        if (kObserved) {
+            bool unseen = false;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) unseen = unseen || corner_d(k) != corner_d(k);
+            if (unseen) above = 0u;
+        }
     }
     const int cnt = (above != 0u && above != 255u) ? ts_mesh_cell_count(above) : 0;        // 0..12: four bits
     // exclusive prefix of cnt over the workgroup, in thread order
@@ -302,6 +310,28 @@ int ts_mesh_emit(int32_t bricks, const int64_t* brick_ids, const float* grid_hos
     if (!brick_ids || !density || !offsets || !keys || !positions) return TS_E_BADARG;
     hipLaunchKernelGGL(cells_kernel<true>, dim3((unsigned)bricks), dim3(kCells), 0, (hipStream_t)stream, g, level,
                        brick_ids, density, (int32_t*)nullptr, offsets, keys, positions, cells);
+    return launch_status();
+}
+
+int ts_mesh_count_observed(int32_t bricks, const int64_t* brick_ids, const float* grid_host, const int32_t* cells_host,
+                           float level, const float* field, int32_t* counts, void* stream) {
+    Grid g;
+    if (!bricks_ok(bricks) || !isfinite(level) || !read_grid(grid_host, cells_host, &g)) return TS_E_BADARG;
+    if (!brick_ids || !field || !counts) return TS_E_BADARG;
+    hipLaunchKernelGGL((cells_kernel<false, true>), dim3((unsigned)bricks), dim3(kCells), 0, (hipStream_t)stream, g, level,
+                       brick_ids, field, counts, (const int64_t*)nullptr, (int64_t*)nullptr, (float*)nullptr,
+                       (int64_t*)nullptr);
+    return launch_status();
+}
+
+int ts_mesh_emit_observed(int32_t bricks, const int64_t* brick_ids, const float* grid_host, const int32_t* cells_host,
+                          float level, const float* field, const int64_t* offsets, int64_t* keys, float* positions,
+                          int64_t* cells, void* stream) {
+    Grid g;
+    if (!bricks_ok(bricks) || !isfinite(level) || !read_grid(grid_host, cells_host, &g)) return TS_E_BADARG;
+    if (!brick_ids || !field || !offsets || !keys || !positions) return TS_E_BADARG;
+    hipLaunchKernelGGL((cells_kernel<true, true>), dim3((unsigned)bricks), dim3(kCells), 0, (hipStream_t)stream, g, level,
+                       brick_ids, field, (int32_t*)nullptr, offsets, keys, positions, cells);
     return launch_status();
 }
 

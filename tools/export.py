@@ -2,6 +2,7 @@
 """Exports a trained scene to a file other tools read.
 
     python tools/export.py input_file output_file --filetype PLY|SPLAT|OBJ|MESH_PLY [options]
+    python tools/export.py scene.ply mesh.ply --filetype MESH_PLY --mesher tsdf --dataset-dir DATASET
 
 ``input_file``: a checkpoint (``.pth`` / ``.pt``, what training saves) or a 3DGS PLY (``.ply``), told apart by the
 extension.  File types:
@@ -13,7 +14,11 @@ extension.  File types:
   MESH_PLY  the same mesh as a binary PLY
 
 The mesh types take ``--resolution`` (cells along the longest axis), ``--target-faces`` (simplify to a budget) and
-``--colors`` (vertex colours from the spherical harmonics).  Needs a GPU: there is no CPU path.
+``--colors`` (vertex colours from the spherical harmonics).  ``--mesher density`` (the default) meshes the SuGaR density,
+a surface only for a scene trained with ``--regularize-density``; ``--mesher tsdf`` fuses the depth renders of the
+cameras of ``--dataset-dir`` (its COLMAP reconstruction below ``--colmap-path``) into a truncated signed distance volume
+and meshes that (``extract_mesh_tsdf``: any scene that renders good depth; no vertex colours).  Needs a GPU: there is no
+CPU path.
 """
 import argparse
 import sys
@@ -35,6 +40,10 @@ def parse(argv=None):
     ap.add_argument("--resolution", type=int, default=None, help="OBJ, MESH_PLY: cells along the longest axis")
     ap.add_argument("--target-faces", type=int, default=None, help="OBJ, MESH_PLY: simplify to at most this many faces")
     ap.add_argument("--colors", action="store_true", help="OBJ, MESH_PLY: vertex colours")
+    ap.add_argument("--mesher", choices=("density", "tsdf"), default="density",
+                    help="OBJ, MESH_PLY: the density's level set, or the fusion of the cameras' depth renders")
+    ap.add_argument("--dataset-dir", type=str, default=None, help="--mesher tsdf: the reconstruction whose cameras render")
+    ap.add_argument("--colmap-path", type=str, default="colmap/sparse/0", help="below --dataset-dir")
     args = ap.parse_args(argv)
     mesh = args.filetype in ("OBJ", "MESH_PLY")
     if args.limit is not None and args.filetype != "SPLAT":
@@ -43,7 +52,25 @@ def parse(argv=None):
         ap.error("--limit must not be negative")
     if not mesh and (args.resolution is not None or args.target_faces is not None or args.colors):
         ap.error("--resolution, --target-faces and --colors go with --filetype OBJ or MESH_PLY")
+    if args.mesher == "tsdf" and not mesh:
+        ap.error("--mesher goes with --filetype OBJ or MESH_PLY")
+    if (args.mesher == "tsdf") != (args.dataset_dir is not None):
+        ap.error("--mesher tsdf and --dataset-dir go together")
+    if args.mesher == "tsdf" and args.colors:
+        ap.error("--colors goes with --mesher density")
     return args
+
+
+def dataset_cameras(dataset_dir, colmap_path):
+    """One camera per image of the reconstruction, in the order of images.bin; no image is read."""
+    from tinysplat_amd.colmap import read_reconstruction
+    from tinysplat_amd.dataset import camera_from_colmap
+    rec = read_reconstruction(Path(dataset_dir) / colmap_path)
+    cameras = []
+    for image in rec.images.values():
+        cam = rec.cameras[image.camera_id]
+        cameras.append(camera_from_colmap(cam, image, (cam.width, cam.height)).camera)
+    return cameras
 
 
 def load_model(path, device):
@@ -68,9 +95,13 @@ def main(argv=None):
     elif args.filetype == "SPLAT":
         formats.export_splat(model, args.output_file, limit=args.limit)
     else:
-        cfg = MeshConfig(colors=args.colors, target_faces=args.target_faces,
-                         **({} if args.resolution is None else {"resolution": args.resolution}))
-        mesh = extract_mesh(model, cfg)
+        res = {} if args.resolution is None else {"resolution": args.resolution}
+        if args.mesher == "tsdf":
+            from tinysplat_amd import FusionConfig, extract_mesh_tsdf
+            cameras = dataset_cameras(args.dataset_dir, args.colmap_path)
+            mesh = extract_mesh_tsdf(model, cameras, FusionConfig(target_faces=args.target_faces, **res), args.device)
+        else:
+            mesh = extract_mesh(model, MeshConfig(colors=args.colors, target_faces=args.target_faces, **res))
         write = formats.export_mesh_obj if args.filetype == "OBJ" else formats.export_mesh_ply
         write(mesh, args.output_file)
         print(f"{int(mesh.vertices.shape[0])} vertices, {int(mesh.faces.shape[0])} faces")
