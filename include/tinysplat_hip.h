@@ -1158,6 +1158,29 @@ int ts_depth_prior_fit(int32_t cameras, const int64_t* offsets, const float* x, 
 int ts_depth_prior_apply(const float* map, int32_t map_h, int32_t map_w, int32_t height, int32_t width, const double* fit,
                          int32_t disparity, float* out, void* stream);
 
+/* Label votes: which class every Gaussian belongs to, from per-view label maps (DESIGN.md section 6q,
+ * csrc/vote_math.h).  Additive entries: the ABI version is unchanged.  Neither allocates or synchronises.
+ * ts_label_votes: one view.  cam, tile_bins, gaussian_ids_sorted, splats: the 16x16 lists and 48-byte records of the
+ * forward compositing launch (ts_sort_tiles, ts_pack_splats); the colours of the records are not read.  labels: uint8
+ * [img_height, img_width] with class_map uint8 [256] (both device pointers, both or neither): a pixel of label l votes
+ * in column class_map[l], or not at all where that is 255 (or >= num_classes).  Without them every pixel of the image
+ * votes in column 0.  votes int64 [n, num_classes], n > every listed id, is ACCUMULATED into:
+ *   votes[g, c] += sum over the pixels p of column c of rint(2^24 vis_g(p))
+ * with vis_g(p) the float32 weight ts_raster_fwd blends g into p with, bit for bit.  Integer atomics only: the same
+ * bytes whatever the order of tiles, views and calls.  flags: 0.  TS_E_BADARG, before any launch: flags != 0, a NULL
+ * cam, cam->wide_tiles != 0, num_classes outside 1..255, one of labels / class_map without the other, an image size
+ * < 1 or tile bounds that are not the image's, and (where the camera has tiles) a NULL tile_bins,
+ * gaussian_ids_sorted, splats or votes.
+ * ts_votes_labels: labels_out uint8 [n] <- the first largest column of every row where the row's sum is positive and
+ * double(top) >= min_share * double(sum), else 255; confidence_out float32 [n] (may be NULL) <- float32(double(top) /
+ * double(sum)), 0 for an empty row.  n == 0: returns 0, launches nothing.  TS_E_BADARG: n < 0, num_classes outside
+ * 1..255, a NaN min_share, a NULL votes or labels_out with n > 0. */
+int ts_label_votes(int32_t flags, const ts_camera* cam_host, const int32_t* tile_bins, const int32_t* gaussian_ids_sorted,
+                   const float* splats, const uint8_t* labels, const uint8_t* class_map, int32_t num_classes,
+                   int64_t* votes, void* stream);
+int ts_votes_labels(int32_t n, int32_t num_classes, const int64_t* votes, double min_share, uint8_t* labels_out,
+                    float* confidence_out, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

@@ -17,6 +17,8 @@ from .fusion import FusionConfig, extract_mesh_tsdf, fuse_depth_maps, render_dep
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
 from .rasterizer import GaussianRasterizer
 from .scene import Scene
+from .semantic import (LiftResult, SemanticMaps, gaussian_contributions, label_iou, labels_from_votes, lift_labels,
+                       render_labels, select_gaussians)
 from .surface import (DensitySamples, SurfaceConfig, SurfaceRegularizer, density_loss, density_parts, opacity_entropy,
                       sample_points)
 from .synthetic import RGB2SH, SH2RGB
@@ -29,4 +31,6 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "level_set_points", "MeshConfig", "TriangleMesh", "extract_mesh", "vertex_colors", "SimplifyConfig",
            "simplify_mesh", "CleanConfig", "clean_mesh", "mesh_components", "Dataset", "Viewer", "encode_jpeg", "JpegEncoder",
            "image_metrics", "evaluate", "holdout_split", "Evaluator", "EvalResult", "DepthPriors", "SparseDepth", "match_scale",
-           "sparse_depth", "FusionConfig", "fuse_depth_maps", "render_depth_alpha", "extract_mesh_tsdf"]
+           "sparse_depth", "FusionConfig", "fuse_depth_maps", "render_depth_alpha", "extract_mesh_tsdf", "SemanticMaps",
+           "LiftResult", "lift_labels", "labels_from_votes", "gaussian_contributions", "select_gaussians", "render_labels",
+           "label_iou"]

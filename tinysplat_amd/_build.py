@@ -65,6 +65,9 @@ SOURCES = [
     # that the host build of tsdf_math.h rounds operation by operation; an fma would move a corner across a pixel border
     # in one brick and not in its neighbour's host restatement, and the corner positions are mesh.hip's, bit for bit
     ("tsdf.hip", ["-ffp-contract=off"]),
+    # votes.hip: its staging culls are raster.hip's and are compiled as raster.hip compiles them (no file-wide contraction
+    # switch); the per-pixel body that must give the forward's bits turns contraction off itself, as fwd_chunk does
+    ("votes.hip", []),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -277,6 +277,8 @@ SIGNATURES = {
     "ts_depth_prior_gather": (c_int32, [c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ts_depth_prior_fit": (c_int32, [c_int32, _P, _P, _P, _P, c_int32, _P, _P]),
     "ts_depth_prior_apply": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, _P]),
+    "ts_label_votes": (c_int32, [c_int32, _CAM, _P, _P, _P, _P, _P, c_int32, _P, _P]),
+    "ts_votes_labels": (c_int32, [c_int32, c_int32, _P, c_double, _P, _P, _P]),
 }
 
 _lib = None

@@ -7,8 +7,10 @@
 ``--holdout N`` evaluates every N-th camera by image name - the views ``tools/train.py --eval-holdout N`` kept out of
 training; ``--holdout 0`` evaluates all views.  Every view is rendered on a black background and compared with its
 (undistorted) image; ``--max-image-dimension`` and ``--principal-point`` must be those the scene was trained with.  SSIM
-is the training loss's (pytorch_msssim: valid filtering), not the zero-padded SSIM of the 3DGS papers' tables.  Needs a
-GPU: there is no CPU path.
+is the training loss's (pytorch_msssim: valid filtering), not the zero-padded SSIM of the 3DGS papers' tables.
+``--semantic-dir D`` additionally lifts the label maps ``D/<image name>.npy`` of the TRAINING views onto the Gaussians
+(``semantic.lift_labels``), renders the labels at the evaluated views and prints their mean IoU against those views'
+maps.  Needs a GPU: there is no CPU path.
 """
 import argparse
 import csv
@@ -34,7 +36,13 @@ def parse(argv=None):
     ap.add_argument("--principal-point", choices=("reference", "center"), default="reference")
     ap.add_argument("--holdout", type=int, default=8, help="evaluate every N-th camera by image name; 0: all of them")
     ap.add_argument("--csv", type=str, default=None, help="write the per-view table and the means to this CSV file")
+    ap.add_argument("--semantic-dir", type=str, default=None,
+                    help="label maps <image name>.npy: also print the mIoU of the rendered labels on the evaluated views")
+    ap.add_argument("--semantic-classes", type=int, default=150, help="labels of the maps: 0 .. this - 1, 255 ignored")
+    ap.add_argument("--min-share", type=float, default=0.0, help="least share of a Gaussian's votes its class must have")
     args = ap.parse_args(argv)
+    if not 1 <= args.semantic_classes <= 255 or not 0.0 <= args.min_share <= 1.0:
+        ap.error("--semantic-classes must be in 1..255 and --min-share in [0, 1]")
     if Path(args.scene).suffix.lower() not in READERS:
         ap.error(f"SCENE must end in one of {', '.join(READERS)}")
     if args.holdout < 0 or (args.max_image_dimension is not None and args.max_image_dimension < 1):
@@ -46,6 +54,24 @@ def table_rows(result):
     """(view, psnr, ssim, l1, mse) per view, then the means."""
     rows = [(name, float(r[3]), float(r[2]), float(r[1]), float(r[0])) for name, r in zip(result.names, result.table)]
     return rows + [("mean", result.psnr, result.ssim, result.l1, result.mse)]
+
+
+def semantic_line(model, cameras, train, views, args):
+    """Lifts the TRAINING views' label maps onto the Gaussians, renders the labels at the evaluated views and compares
+    them with those views' maps -> the line to print."""
+    import torch
+    from tinysplat_amd.semantic import SemanticMaps, label_iou, lift_labels, render_labels
+    used = sorted(set(train) | set(views))
+    maps = SemanticMaps([cameras[i] for i in used], args.semantic_dir, num_classes=args.semantic_classes,
+                        device=args.device)
+    at = {i: k for k, i in enumerate(used)}
+    lifted = lift_labels(model, [cameras[i] for i in train], maps, min_share=args.min_share)
+    pred = torch.cat([render_labels(model, cameras[i], lifted.labels, args.semantic_classes).reshape(-1) for i in views])
+    target = torch.cat([maps.maps[at[i]].reshape(-1) for i in views])
+    iou, mean = label_iou(pred, target, args.semantic_classes)
+    present = int((~torch.isnan(iou)).sum())
+    return (f"semantic: mIoU {mean:.5f} over the classes of {len(views)} views' maps ({present} classes with pixels), "
+            f"labels lifted from {len(train)} training views")
 
 
 def main(argv=None):
@@ -71,6 +97,8 @@ def main(argv=None):
     for name, psnr, ssim, l1, _mse in rows:
         print(f"{name:<{width}}  {psnr:9.4f}  {ssim:8.5f}  {l1:8.5f}")
     print(f"{len(views)} views, {model.num_points} Gaussians")
+    if args.semantic_dir:
+        print(semantic_line(model, dataset.cameras, train, views, args))
     if args.csv:
         with open(args.csv, "w", newline="") as f:
             writer = csv.writer(f)

@@ -17,8 +17,13 @@ The mesh types take ``--resolution`` (cells along the longest axis), ``--target-
 ``--colors`` (vertex colours from the spherical harmonics).  ``--mesher density`` (the default) meshes the SuGaR density,
 a surface only for a scene trained with ``--regularize-density``; ``--mesher tsdf`` fuses the depth renders of the
 cameras of ``--dataset-dir`` (its COLMAP reconstruction below ``--colmap-path``) into a truncated signed distance volume
-and meshes that (``extract_mesh_tsdf``: any scene that renders good depth; no vertex colours).  Needs a GPU: there is no
-CPU path.
+and meshes that (``extract_mesh_tsdf``: any scene that renders good depth; no vertex colours).
+
+``--semantic-dir D`` (with ``--dataset-dir``) cuts the scene by class before any of this: the label maps
+``D/<image name>.npy`` (``semantic.SemanticMaps``) of the dataset's cameras are lifted onto the Gaussians
+(``lift_labels``, all ``--semantic-classes`` classes voting) and only the Gaussians whose class is one of
+``--keep-classes a,b,...`` - or all but those of ``--drop-classes a,b,...``, unlabelled ones included - are exported; ``--min-share S`` leaves a Gaussian unlabelled whose top class has less than
+that share of its votes.  Needs a GPU: there is no CPU path.
 """
 import argparse
 import sys
@@ -42,8 +47,13 @@ def parse(argv=None):
     ap.add_argument("--colors", action="store_true", help="OBJ, MESH_PLY: vertex colours")
     ap.add_argument("--mesher", choices=("density", "tsdf"), default="density",
                     help="OBJ, MESH_PLY: the density's level set, or the fusion of the cameras' depth renders")
-    ap.add_argument("--dataset-dir", type=str, default=None, help="--mesher tsdf: the reconstruction whose cameras render")
+    ap.add_argument("--dataset-dir", type=str, default=None, help="--mesher tsdf, --semantic-dir: the reconstruction whose cameras render")
     ap.add_argument("--colmap-path", type=str, default="colmap/sparse/0", help="below --dataset-dir")
+    ap.add_argument("--semantic-dir", type=str, default=None, help="label maps <image name>.npy; needs --dataset-dir")
+    ap.add_argument("--semantic-classes", type=int, default=150, help="labels of the maps: 0 .. this - 1, 255 ignored")
+    ap.add_argument("--keep-classes", type=class_list, default=None, help="a,b,...: export the Gaussians of these classes")
+    ap.add_argument("--drop-classes", type=class_list, default=None, help="a,b,...: export all but these classes")
+    ap.add_argument("--min-share", type=float, default=0.0, help="least share of a Gaussian's votes its class must have")
     args = ap.parse_args(argv)
     mesh = args.filetype in ("OBJ", "MESH_PLY")
     if args.limit is not None and args.filetype != "SPLAT":
@@ -54,11 +64,49 @@ def parse(argv=None):
         ap.error("--resolution, --target-faces and --colors go with --filetype OBJ or MESH_PLY")
     if args.mesher == "tsdf" and not mesh:
         ap.error("--mesher goes with --filetype OBJ or MESH_PLY")
-    if (args.mesher == "tsdf") != (args.dataset_dir is not None):
-        ap.error("--mesher tsdf and --dataset-dir go together")
+    if args.semantic_dir is not None and args.dataset_dir is None:
+        ap.error("--semantic-dir needs --dataset-dir")
+    if args.keep_classes is not None and args.drop_classes is not None:
+        ap.error("--keep-classes and --drop-classes exclude each other")
+    if (args.semantic_dir is not None) != (args.keep_classes is not None or args.drop_classes is not None):
+        ap.error("--semantic-dir goes with --keep-classes or --drop-classes")
+    if args.semantic_dir is None and args.min_share != 0.0:
+        ap.error("--min-share goes with --semantic-dir")
+    if not 0.0 <= args.min_share <= 1.0 or not 1 <= args.semantic_classes <= 255:
+        ap.error("--min-share must be in [0, 1] and --semantic-classes in 1..255")
+    for c in (args.keep_classes or []) + (args.drop_classes or []):
+        if not 0 <= c < args.semantic_classes:
+            ap.error(f"class {c} is outside [0, {args.semantic_classes})")
+    if (args.mesher == "tsdf" or args.semantic_dir is not None) != (args.dataset_dir is not None):
+        ap.error("--dataset-dir goes with --mesher tsdf or --semantic-dir")
     if args.mesher == "tsdf" and args.colors:
         ap.error("--colors goes with --mesher density")
     return args
+
+
+def class_list(text):
+    """'a,b,...' -> [a, b, ...], distinct."""
+    try:
+        ids = [int(t) for t in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r}: a comma-separated list of class numbers expected")
+    if len(set(ids)) != len(ids):
+        raise argparse.ArgumentTypeError(f"{text!r}: a class is named twice")
+    return ids
+
+
+def cut_by_class(model, cameras, args):
+    """The Gaussians of --keep-classes, or all but those of --drop-classes, by the lifted labels."""
+    import torch
+    from tinysplat_amd.semantic import SemanticMaps, lift_labels, select_gaussians
+    named = args.keep_classes if args.keep_classes is not None else args.drop_classes
+    # every class votes (a Gaussian belongs to a named class only if that class beats all the others): column = label
+    maps = SemanticMaps(cameras, args.semantic_dir, num_classes=args.semantic_classes, device=args.device)
+    lifted = lift_labels(model, None, maps, min_share=args.min_share)
+    of_named = torch.isin(lifted.labels, torch.tensor(named, dtype=torch.uint8, device=lifted.labels.device))
+    mask = of_named if args.keep_classes is not None else ~of_named
+    print(f"{int(of_named.sum())} of {model.num_points} Gaussians carry one of the classes {named}; keeping {int(mask.sum())}")
+    return select_gaussians(model, mask)
 
 
 def dataset_cameras(dataset_dir, colmap_path):
@@ -90,6 +138,8 @@ def main(argv=None):
         raise SystemExit("no GPU: tinysplat_amd has no CPU path")
     from tinysplat_amd import MeshConfig, extract_mesh, formats
     model = load_model(args.input_file, args.device)
+    if args.semantic_dir is not None:
+        model = cut_by_class(model, dataset_cameras(args.dataset_dir, args.colmap_path), args)
     if args.filetype == "PLY":
         formats.export_ply(model, args.output_file)
     elif args.filetype == "SPLAT":
