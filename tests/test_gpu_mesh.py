@@ -327,3 +327,95 @@ def test_mesh_and_march_evaluate_one_density():
     print(f"\n{int(sel.sum())} corners compared, {above} above the level, {below} in (1e-6, level)")
     assert int(sel.sum()) >= 600 and above >= 20 and below >= 20
     assert torch.equal(march_d, mesh_d)
+
+
+def _record_entries(monkeypatch):
+    """-> the list that receives, in order, the name of every C-ABI entry ``_lib.check`` is handed a status of."""
+    from tinysplat_amd import _lib
+    names, check = [], _lib.check
+
+    def spy(code, what):
+        names.append(what)
+        check(code, what)
+    monkeypatch.setattr(_lib, "check", spy)
+    return names
+
+
+def test_the_launches_of_a_chunked_run_in_order(monkeypatch):
+    """What ``extract_mesh`` launches, entry by entry, with a cap that takes at least 3 chunks: the model's records, the
+    boxes, the marking; per chunk the corners, one neighbour search, the densities and - where a corner is above the
+    level - the count, and the emit where the count is not zero; then the normals per chunk of vertices.  Which chunks
+    count and emit follows from the densities and the triangles' cells of an uncapped run."""
+    from tinysplat_amd import _lib
+    from tinysplat_amd.mesh import MeshConfig, extract_mesh
+    params = MO.sheet_scene(SEED)
+    n = int(params["means"].shape[0])
+    whole, d0 = _extract(params, resolution=16, bounds=BOUNDS)
+    a = int(d0["active_bricks"].shape[0])
+    per = a // 3
+    assert n == 300 and per >= 1 and d0["chunks"] == 1
+    cap = int(_lib.load().ts_mesh_chunk_bytes(n, per))
+    # the triangles of each active brick, from their cells: cell = (k ny + j) nx + i, brick = (bz nby + by) nbx + bx
+    nx, ny, _ = d0["grid"]["cells"]
+    nbx, nby = -(-nx // 8), -(-ny // 8)
+    cell = d0["cell"].cpu().numpy()
+    brick = (cell // (nx * ny) // 8 * nby + cell // nx % ny // 8) * nbx + cell % nx // 8
+    active = d0["active_bricks"].cpu().numpy()
+    assert bool(np.isin(brick, active).all())
+    tris = np.bincount(np.searchsorted(active, brick), minlength=a)
+    above = (d0["density"] > LEVEL).any(1).cpu().numpy()
+    want = ["ts_extract_pack", "ts_mesh_boxes", "ts_mesh_mark"]
+    groups = 0
+    for b0 in range(0, a, per):
+        want += ["ts_mesh_corners", "ts_knn", "ts_mesh_density"]
+        if above[b0:b0 + per].any():
+            want.append("ts_mesh_count")
+            if tris[b0:b0 + per].sum():
+                want.append("ts_mesh_emit")
+        groups += 1
+    assert groups >= 3 and "ts_mesh_emit" in want
+    names = _record_entries(monkeypatch)
+    mesh = extract_mesh(_model(params), MeshConfig(resolution=16, bounds=BOUNDS, max_workspace_bytes=cap))
+    monkeypatch.undo()
+    torch.cuda.synchronize()
+    got, normals = names[:len(want)], names[len(want):]
+    assert got == want
+    assert len(normals) >= 2 and normals == ["ts_knn", "ts_extract_normals"] * (len(normals) // 2)
+    _, d1 = _extract(params, resolution=16, bounds=BOUNDS, max_workspace_bytes=cap)
+    assert d1["chunks"] == groups and _same(mesh, whole)
+
+
+def test_the_observed_cell_kernel_marches_the_density_as_the_plain_one():
+    """The shared driver (``_bricks.march``) over the density mesher's own field, which holds no NaN: with
+    ``observed=True`` (the fusion's cell kernel) it emits the keys and positions it emits with ``observed=False``, the
+    ones ``extract_mesh`` returned."""
+    from types import SimpleNamespace
+    from tinysplat_amd import _bricks, _lib
+    from tinysplat_amd.ops import _stream
+    _, dbg = _extract(MO.sheet_scene(SEED), resolution=16, bounds=BOUNDS)
+    density, active = dbg["density"].contiguous(), dbg["active_bricks"]
+    a = int(active.shape[0])
+    assert a > 1 and not bool(torch.isnan(density).any())
+    grid = _bricks.BrickGrid(*BOUNDS, 16, 1 << 20)
+    assert grid.debug == dbg["grid"]
+    per = -(-a // 2)                                                        # two chunks, by a cap in bricks
+
+    def make_chunk(bricks):
+        return SimpleNamespace(counts=torch.empty((bricks,), dtype=torch.int32, device=DEV),
+                               offsets=torch.empty((bricks,), dtype=torch.int64, device=DEV))
+
+    def fill(ck, ids, b):
+        b0 = next(rows)
+        assert torch.equal(ids, active[b0:b0 + b])
+        return density[b0:b0 + b].view(-1)
+    out = {}
+    with torch.cuda.device(DEV):
+        for observed in (False, True):
+            rows = iter(range(0, a, per))
+            out[observed] = _bricks.march(_lib.load(), grid, active, lambda b: b, per, make_chunk, fill, LEVEL, observed,
+                                          True, _stream(torch.device(DEV)))
+    torch.cuda.synchronize()
+    (keys, pos, cell, chunks), (okeys, opos, ocell, ochunks) = out[False], out[True]
+    assert chunks == ochunks == 2 and keys.shape[0] > 100
+    assert torch.equal(keys, dbg["keys"]) and torch.equal(cell, dbg["cell"])
+    assert torch.equal(okeys, keys) and torch.equal(opos, pos) and torch.equal(ocell, cell)

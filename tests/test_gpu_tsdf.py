@@ -142,6 +142,51 @@ def test_invariances_bit_for_bit(name):
     assert _same(mesh, again)
 
 
+@pytest.mark.parametrize("camera_batch", [1, None])
+def test_the_launches_of_one_brick_chunks_in_order(camera_batch, monkeypatch):
+    """What ``fuse_depth_maps`` launches, entry by entry, with chunks of one brick: the marking; per brick one integration
+    per camera batch, the field and - where a corner is inside - the observed count, and the observed emit where the
+    count is not zero; never the plain cell kernel.  Which bricks count and emit follows from the field and the
+    triangles' cells of the default run."""
+    from tinysplat_amd import _lib, fuse_depth_maps
+    name = "plane2"
+    c = TC.case(name)
+    mesh, dbg = _default(name)
+    active = dbg["active_bricks"].cpu().numpy()
+    a = active.size
+    assert a > 1
+    # the triangles of each active brick, from their cells: cell = (k ny + j) nx + i, brick = (bz nby + by) nbx + bx
+    nx, ny, _ = dbg["grid"]["cells"]
+    nbx, nby = -(-nx // 8), -(-ny // 8)
+    cell = dbg["cell"].cpu().numpy()
+    brick = (cell // (nx * ny) // 8 * nby + cell // nx % ny // 8) * nbx + cell % nx // 8
+    assert bool(np.isin(brick, active).all())
+    tris = np.bincount(np.searchsorted(active, brick), minlength=a)
+    inside = (dbg["field"] > 0).any(1).cpu().numpy()
+    cams, depths = TC.torch_inputs(c, DEV)
+    launches = 1 if camera_batch is None else math.ceil(len(cams) / camera_batch)
+    want = ["ts_tsdf_mark"]
+    for i in range(a):
+        want += ["ts_tsdf_integrate"] * launches + ["ts_tsdf_field"]
+        if inside[i]:
+            want.append("ts_mesh_count_observed")
+            if tris[i]:
+                want.append("ts_mesh_emit_observed")
+    assert len(cams) == 2 and "ts_mesh_emit_observed" in want
+    cfg = _config(c, max_workspace_bytes=int(_lib.load().ts_tsdf_chunk_bytes(1)), camera_batch=camera_batch)
+    names, check = [], _lib.check
+
+    def spy(code, what):
+        names.append(what)
+        check(code, what)
+    monkeypatch.setattr(_lib, "check", spy)
+    small = fuse_depth_maps(cams, depths, cfg)
+    monkeypatch.undo()
+    torch.cuda.synchronize()
+    assert names == want and "ts_mesh_count" not in names and "ts_mesh_emit" not in names
+    assert _same(small, mesh)
+
+
 def test_sphere_is_closed():
     c = TC.case("sphere")
     m = TO.march_observed(c.F, c.positions)

@@ -218,6 +218,59 @@ def test_mesh_config_validation():
         make_grid((0, 0, 0), (1, 1, 1), 0)
 
 
+def test_the_one_weld_is_the_oracles():
+    """``_bricks.weld``, the weld of both extractors, against ``mesh_oracle.weld``: 200 triangles over 50 keys, every
+    occurrence with a position of its own (so that the first occurrence shows), and no triangle at all."""
+    from tinysplat_amd import _bricks, fusion, mesh
+    assert mesh.weld is _bricks.weld and fusion.weld is _bricks.weld
+    rng = np.random.default_rng(5)
+    pool = rng.choice(2 ** 40, 50, replace=False).astype(np.int64)
+    keys = pool[rng.integers(0, 50, (200, 3))]
+    pos = rng.standard_normal((200, 3, 3)).astype(np.float32)
+    uniq, faces, verts = MO.weld(keys, pos)
+    got_v, got_f = _bricks.weld(torch.from_numpy(keys), torch.from_numpy(pos))
+    assert got_f.dtype == torch.int32 and got_v.dtype == torch.float32
+    assert np.array_equal(got_f.numpy(), faces) and np.array_equal(got_v.numpy(), verts)
+    assert bool(np.all(np.diff(uniq) > 0)) and np.array_equal(uniq[got_f.numpy()], keys)      # ascending key order
+    first = np.array([np.flatnonzero(keys.reshape(-1) == k)[0] for k in uniq])
+    assert np.array_equal(got_v.numpy(), pos.reshape(-1, 3)[first])                          # the first occurrence's
+    none_v, none_f = _bricks.weld(torch.empty((0, 3), dtype=torch.int64), torch.empty((0, 3, 3)))
+    assert none_v.shape == (0, 3) and none_v.dtype == torch.float32
+    assert none_f.shape == (0, 3) and none_f.dtype == torch.int32
+
+
+@pytest.mark.parametrize("resolution", [21, 37])
+def test_brick_grid_is_the_arithmetic_of_its_callers(resolution):
+    """``BrickGrid`` against what ``extract_mesh`` and ``fuse_depth_maps`` each derived from ``make_grid`` themselves, on
+    cell counts that are no multiple of 8; the flags (a byte per brick) fit a cap of exactly that many bytes."""
+    from tinysplat_amd._bricks import BrickGrid
+    from tinysplat_amd.mesh import BRICK, BRICK_CORNERS, make_grid
+    bounds = ((-1.55, -1.52, 1.85), (1.53, 1.56, 4.2))
+    lo, h, cells = make_grid(*bounds, resolution)
+    assert (BRICK, BRICK_CORNERS) == (8, 729) and all(c % 8 for c in cells)
+    grid = BrickGrid(*bounds, resolution, 1 << 20)
+    assert (grid.lo, grid.h, grid.cells, grid.cap) == (lo, h, cells, 1 << 20)
+    assert grid.bricks == [math.ceil(c / 8) for c in cells]
+    total = grid.bricks[0] * grid.bricks[1] * grid.bricks[2]
+    assert grid.total_bricks == total > 1
+    assert list(grid.grid_host) == [*lo, h] and isinstance(grid.grid_host, ctypes.c_float * 4)
+    assert list(grid.cells_host) == cells and isinstance(grid.cells_host, ctypes.c_int32 * 3)
+    assert grid.debug == {"lo": tuple(lo), "h": h, "cells": tuple(cells)}
+    BrickGrid(*bounds, resolution, total).check_fits(total, "one brick")
+    with pytest.raises(ValueError, match=f"the flags of {total} bricks do not fit max_workspace_bytes = {total - 1}"):
+        BrickGrid(*bounds, resolution, total - 1).check_fits(1, "one brick")
+    with pytest.raises(ValueError, match=f"max_workspace_bytes = {total} is below the {total + 1} bytes one brick over "
+                                         "300 Gaussians needs"):
+        BrickGrid(*bounds, resolution, total).check_fits(total + 1, "one brick over 300 Gaussians")
+    dense = grid.active_bricks(False, None, "cpu")
+    assert dense.dtype == torch.int64 and dense.tolist() == list(range(total))
+
+    def mark(flags):
+        assert flags.shape == (total,) and flags.dtype == torch.uint8 and not bool(flags.any())
+        flags[[total - 1, 0, 5]] = 1
+    assert grid.active_bricks(True, mark, "cpu").tolist() == [0, 5, total - 1]
+
+
 def test_mesh_refuses_cpu_tensors_and_small_models():
     from tinysplat_amd.mesh import extract_mesh, gaussian_boxes
     from tinysplat_amd.synthetic import make_scene

@@ -2,7 +2,7 @@
 
 The second mesh extractor, for the scenes whose density is no surface (a plain ``fit``, a loaded ``.ply`` or ``.splat``:
 anything not trained through the density regulariser's window) but which render good depth.  Every corner of the mesher's
-brick grid (``mesh.make_grid``, csrc/mesh_cells.h) is projected into every camera as ``project_gaussians`` places a
+brick grid (``_bricks.BrickGrid``, csrc/mesh_cells.h) is projected into every camera as ``project_gaussians`` places a
 Gaussian's centre, reads the depth ``d`` of the pixel it rounds to and, unless it lies more than ``trunc`` behind it,
 observes ``min(1, (d - z) / trunc)``; the field is minus the mean observation (positive inside), NaN where fewer than
 ``min_observations`` cameras observed the corner, and the mesh is its zero set by the marching tetrahedra of section 6g,
@@ -13,6 +13,10 @@ has a positive field value, which takes a negative observation, ``-trunc <= d - 
 the corner lies in that pixel's frustum piece between the depths ``d`` and ``d + trunc``, and the cell in that piece's box
 widened by one cell edge.  ``ts_tsdf_mark`` flags the bricks such a box touches; ``sparse=False`` evaluates every brick
 and gives the same mesh bit for bit.
+
+The grid, the list of active bricks, the march over chunks of them, the weld and the simplify and clean tail are
+``_bricks.py``'s, the code ``mesh.extract_mesh`` runs; what is here is how the depth maps flag bricks and fill a chunk's
+field.
 
 The hot path is csrc/tsdf.hip and the observed variant of csrc/mesh.hip's cell kernel; there is no CPU fallback: tensors
 must be on the GPU.
@@ -26,11 +30,11 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
-from torch import Tensor
 
 from . import _lib
-from ._field import Workspace, cat, largest
-from .mesh import BRICK, BRICK_CORNERS, TriangleMesh, _check_bounds, make_grid
+from ._bricks import BRICK_CORNERS, BrickGrid, _check_bounds, check_config, march, mesh_tail, weld
+from ._field import Workspace, cat
+from .mesh import TriangleMesh
 from .ops import _call, _f32c, _need_hip, _ptr, _stream
 
 _MAX_BRICKS = (2 ** 31 - 1) // BRICK_CORNERS
@@ -65,10 +69,7 @@ class FusionConfig:
     clean: Optional["CleanConfig"] = None
 
     def __post_init__(self):
-        if int(self.resolution) < 1:
-            raise ValueError("resolution must be at least 1")
-        if self.bounds is not None:
-            _check_bounds(*self.bounds)
+        check_config(self)
         tv = self.trunc_voxels
         if not (isinstance(tv, (int, float)) and math.isfinite(tv) and tv > 0):
             raise ValueError("trunc_voxels must be positive and finite")
@@ -83,16 +84,8 @@ class FusionConfig:
             raise ValueError("min_alpha must be in (0, 1]")
         if int(self.min_observations) < 1:
             raise ValueError("min_observations must be at least 1")
-        if int(self.max_workspace_bytes) < 1:
-            raise ValueError("max_workspace_bytes must be positive")
         if self.camera_batch is not None and int(self.camera_batch) < 1:
             raise ValueError("camera_batch must be at least 1")
-        if self.target_faces is not None and int(self.target_faces) < 1:
-            raise ValueError("target_faces must be at least 1")
-        if self.clean is not None:
-            from .clean import CleanConfig
-            if not isinstance(self.clean, CleanConfig):
-                raise ValueError("clean must be a CleanConfig or None")
 
 
 def projview(camera) -> np.ndarray:
@@ -184,22 +177,6 @@ class _Chunk:
         ws.done()
 
 
-def weld(keys: Tensor, pos: Tensor):
-    """The vertices welded by key exactly as ``extract_mesh`` welds them: ascending key order, the first occurrence's
-    position (all occurrences are bit-identical) -> ``(vertices float32 [V,3], faces int32 [T,3])``."""
-    dev = keys.device
-    if not keys.shape[0]:
-        return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int32, device=dev))
-    uniq, inv = torch.unique(keys.view(-1), sorted=True, return_inverse=True)
-    v = int(uniq.shape[0])
-    if v >= 2 ** 31:
-        raise ValueError(f"{v} vertices do not fit int32 faces; lower the resolution")
-    occ = torch.arange(inv.shape[0], dtype=torch.int64, device=dev)
-    first = torch.full((v,), inv.shape[0], dtype=torch.int64, device=dev).scatter_reduce_(
-        0, inv, occ, reduce="amin", include_self=True)
-    return pos.view(-1, 3).index_select(0, first), inv.view(-1, 3).to(torch.int32)
-
-
 @torch.no_grad()
 def fuse_depth_maps(cameras, depths, config: Optional[FusionConfig] = None, return_debug: bool = False,
                     frustum_cull: bool = True):
@@ -211,7 +188,7 @@ def fuse_depth_maps(cameras, depths, config: Optional[FusionConfig] = None, retu
     depth sample and their ascending list; per chunk of listed bricks (sized so that one chunk's buffers fit
     ``config.max_workspace_bytes``) the double sums and the counts over the cameras in list order, ``camera_batch`` at a
     time, the field, the triangle counts and the triangles as edge keys and positions; then the vertices are welded by
-    key as ``extract_mesh`` welds them, and the mesh is simplified and cleaned when configured.  The mesh is a fixed
+    key (``_bricks.weld``, as ``extract_mesh``'s), and the mesh is simplified and cleaned when configured.  The mesh is a fixed
     function of (cameras, depths, config): the same for any chunk size, any camera batch, ``sparse`` on or off and
     ``frustum_cull`` on or off (a debug switch: off, every corner is projected into every camera).
 
@@ -229,7 +206,6 @@ def fuse_depth_maps(cameras, depths, config: Optional[FusionConfig] = None, retu
         if d.dim() != 2 or d.shape[0] < 1 or d.shape[1] < 1 or d.numel() >= 2 ** 31:
             raise ValueError("a depth map is a float32 [H, W] tensor")
     lib = _lib.load()
-    cap = int(cfg.max_workspace_bytes)
     depth_max, znear = float(cfg.depth_max), float(cfg.znear)
     pvs = [projview(c) for c in cameras]
     res, tv = int(cfg.resolution), float(cfg.trunc_voxels)
@@ -245,7 +221,8 @@ def fuse_depth_maps(cameras, depths, config: Optional[FusionConfig] = None, retu
         lo_hi = ([a - trunc_w for a in lo_t], [b + trunc_w for b in hi_t])
     else:
         lo_hi = _check_bounds(*cfg.bounds)
-    glo, h, cells = make_grid(*lo_hi, res)
+    grid = BrickGrid(*lo_hi, res, cfg.max_workspace_bytes)
+    glo, h, cells = grid.lo, grid.h, grid.cells
     trunc = ctypes.c_float(tv * h).value
     if not (trunc > 0 and math.isfinite(trunc)):
         raise ValueError("the truncation distance trunc_voxels * h is not a positive float32")
@@ -255,97 +232,49 @@ def fuse_depth_maps(cameras, depths, config: Optional[FusionConfig] = None, retu
         if float((np.abs(view[:3, :3]).sum(1) * reach + np.abs(view[:3, 3])).max()) > _MAX_COORD_CELLS * h:
             raise ValueError("the grid's coordinates in a camera's frame exceed 2^16 cell edges: float32 cannot place a "
                              "corner in a pixel to a sixteenth of a cell there; move the scene or lower the resolution")
-    nb = [-(-c // BRICK) for c in cells]
-    total_bricks = nb[0] * nb[1] * nb[2]
-    if total_bricks > cap:
-        raise ValueError(f"the flags of {total_bricks} bricks do not fit max_workspace_bytes = {cap}")
-    one = int(lib.ts_tsdf_chunk_bytes(1))
-    if one > cap:
-        raise ValueError(f"max_workspace_bytes = {cap} is below the {one} bytes one brick needs")
-    grid_host = (ctypes.c_float * 4)(*glo, h)
-    cells_host = (ctypes.c_int32 * 3)(*cells)
+    grid.check_fits(int(lib.ts_tsdf_chunk_bytes(1)), "one brick")
     n_cam = len(cameras)
     batch = n_cam if cfg.camera_batch is None else min(int(cfg.camera_batch), n_cam)
     flags_arg = 0 if frustum_cull else _lib.TSDF_NO_CULL
-    tri_keys, tri_pos, tri_cell = [], [], []
     dbg = {"field": [], "count": []} if return_debug else None
-    chunks = 0
+    tail = {}
     with torch.cuda.device(dev):
         s = _stream(dev)
         table = torch.from_numpy(camera_table(cameras, depths)).to(dev)
-        if cfg.sparse:
-            flags = torch.zeros((total_bricks,), dtype=torch.uint8, device=dev)
-            _call("ts_tsdf_mark", lib.ts_tsdf_mark, n_cam, _ptr(table), max(int(d.numel()) for d in depths), grid_host,
-                  cells_host, trunc, depth_max, _ptr(flags), s)
-            active = torch.nonzero(flags).view(-1)                      # ascending
-            del flags
-        else:
-            active = torch.arange(total_bricks, dtype=torch.int64, device=dev)
-        a = int(active.shape[0])
-        if a:
-            per = largest(lambda b: int(lib.ts_tsdf_chunk_bytes(b)) <= cap, min(a, _MAX_BRICKS))
-            ck = _Chunk(lib, per, dev)
-            for b0 in range(0, a, per):
-                b = min(per, a - b0)
-                q = b * BRICK_CORNERS
-                chunks += 1
-                ids = active[b0:b0 + b]
-                ck.sum[:q].zero_()
-                ck.count[:q].zero_()
-                for c0 in range(0, n_cam, batch):
-                    _call("ts_tsdf_integrate", lib.ts_tsdf_integrate, b, _ptr(ids), grid_host, cells_host, _ptr(table), c0,
-                          min(c0 + batch, n_cam), trunc, znear, depth_max, flags_arg, _ptr(ck.sum), _ptr(ck.count), s)
-                _call("ts_tsdf_field", lib.ts_tsdf_field, b, _ptr(ck.sum), _ptr(ck.count), int(cfg.min_observations),
-                      _ptr(ck.field), s)
-                if return_debug:
-                    dbg["field"].append(ck.field[:q].view(b, BRICK_CORNERS).clone())
-                    dbg["count"].append(ck.count[:q].view(b, BRICK_CORNERS).clone())
-                # no corner inside: no triangle, and nothing to launch
-                if not bool((ck.field[:q] > 0).any()):
-                    continue
-                _call("ts_mesh_count_observed", lib.ts_mesh_count_observed, b, _ptr(ids), grid_host, cells_host, 0.0,
-                      _ptr(ck.field), _ptr(ck.counts), s)
-                ends = torch.cumsum(ck.counts[:b], 0, dtype=torch.int64)
-                t = int(ends[-1])
-                if t == 0:
-                    continue
-                ck.offsets[:b] = ends - ck.counts[:b]
-                keys = torch.empty((t, 3), dtype=torch.int64, device=dev)
-                pos = torch.empty((t, 3, 3), dtype=torch.float32, device=dev)
-                cell = torch.empty((t,), dtype=torch.int64, device=dev) if return_debug else None
-                _call("ts_mesh_emit_observed", lib.ts_mesh_emit_observed, b, _ptr(ids), grid_host, cells_host, 0.0,
-                      _ptr(ck.field), _ptr(ck.offsets), _ptr(keys), _ptr(pos), _ptr(cell), s)
-                tri_keys.append(keys)
-                tri_pos.append(pos)
-                if return_debug:
-                    tri_cell.append(cell)
-            del ck
-        keys = cat(tri_keys, (0, 3), torch.int64, dev)
-        pos = cat(tri_pos, (0, 3, 3), torch.float32, dev)
-        del tri_keys, tri_pos
+
+        def mark(flags):
+            _call("ts_tsdf_mark", lib.ts_tsdf_mark, n_cam, _ptr(table), max(int(d.numel()) for d in depths),
+                  grid.grid_host, grid.cells_host, trunc, depth_max, _ptr(flags), s)
+
+        def fill(ck, ids, b):
+            q = b * BRICK_CORNERS
+            ck.sum[:q].zero_()
+            ck.count[:q].zero_()
+            for c0 in range(0, n_cam, batch):
+                _call("ts_tsdf_integrate", lib.ts_tsdf_integrate, b, _ptr(ids), grid.grid_host, grid.cells_host,
+                      _ptr(table), c0, min(c0 + batch, n_cam), trunc, znear, depth_max, flags_arg, _ptr(ck.sum),
+                      _ptr(ck.count), s)
+            _call("ts_tsdf_field", lib.ts_tsdf_field, b, _ptr(ck.sum), _ptr(ck.count), int(cfg.min_observations),
+                  _ptr(ck.field), s)
+            if return_debug:
+                dbg["field"].append(ck.field[:q].view(b, BRICK_CORNERS).clone())
+                dbg["count"].append(ck.count[:q].view(b, BRICK_CORNERS).clone())
+            return ck.field
+
+        active = grid.active_bricks(cfg.sparse, mark, dev)
+        # level 0, observed: a corner is inside where the field is positive, and a cell with a NaN corner emits nothing
+        keys, pos, cell, chunks = march(lib, grid, active, lib.ts_tsdf_chunk_bytes, _MAX_BRICKS,
+                                        lambda b: _Chunk(lib, b, dev), fill, 0.0, True, return_debug, s)
         vertices, faces = weld(keys, pos)
         del pos
-        if cfg.target_faces is not None:
-            from .simplify import SimplifyConfig, _simplify
-            simplified = {}
-            vertices, faces = _simplify(lib, vertices, faces, SimplifyConfig(target_faces=int(cfg.target_faces),
-                                                                             max_workspace_bytes=cap), s, simplified)
-        if cfg.clean is not None:
-            from .clean import _clean
-            cleaned = {}
-            vertices, faces, _ = _clean(lib, vertices, faces, cfg.clean, s, cleaned)
+        vertices, faces = mesh_tail(lib, vertices, faces, cfg, s, tail)
         torch.cuda.current_stream(dev).synchronize()        # the table and the maps it points to stay alive until here
     mesh = TriangleMesh(vertices, faces, None, None)
     if not return_debug:
         return mesh
     debug = {"active_bricks": active, "field": cat(dbg["field"], (0, BRICK_CORNERS), torch.float32, dev),
-             "count": cat(dbg["count"], (0, BRICK_CORNERS), torch.int32, dev), "keys": keys,
-             "cell": cat(tri_cell, (0,), torch.int64, dev), "chunks": chunks, "total_bricks": total_bricks, "trunc": trunc,
-             "grid": {"lo": tuple(glo), "h": h, "cells": tuple(cells)}}
-    if cfg.target_faces is not None:
-        debug["simplify"] = simplified
-    if cfg.clean is not None:
-        debug["clean"] = cleaned
+             "count": cat(dbg["count"], (0, BRICK_CORNERS), torch.int32, dev), "keys": keys, "cell": cell,
+             "chunks": chunks, "total_bricks": grid.total_bricks, "trunc": trunc, "grid": grid.debug, **tail}
     return mesh, debug
 
 

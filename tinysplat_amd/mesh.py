@@ -16,12 +16,15 @@ the dense grid bit for bit (``sparse=False`` evaluates every brick, to show it).
 ``MeshConfig(colors=True)`` also colours the vertices from the Gaussians' spherical harmonics, seen head-on along the
 normal (section 6h, csrc/field_color.hip); ``vertex_colors`` does the same for any points.
 
+The grid, the list of active bricks, the march over chunks of them, the weld and the simplify and clean tail are
+``_bricks.py``'s, shared with the depth-map fusion (``fusion.py``); what is here is the density's own: the boxes that flag
+bricks and the corners, neighbours and densities that fill a chunk.
+
 The hot path is csrc/mesh.hip on top of ``ts_knn``, ``ts_extract_pack`` and ``ts_extract_normals``; there is no CPU
 fallback: tensors must be on the GPU.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
@@ -30,12 +33,12 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._bricks import BRICK, make_grid  # noqa: F401  (tests and tools import them from here)
+from ._bricks import BRICK_CORNERS, BrickGrid, _check_bounds, check_config, march, mesh_tail, weld
 from ._field import (EXTRACT_K, PackedModel, Workspace, align256, cat, colors_at, knn, largest, normals_at,
                      pack_model)
 from .ops import _call, _f32c, _need_hip, _ptr, _stream
 
-BRICK = 8                       # TS_MESH_BRICK
-BRICK_CORNERS = 729             # TS_MESH_BRICK_CORNERS
 _MAX_BRICKS = (2 ** 31 - 1) // (BRICK_CORNERS * EXTRACT_K)
 MAX_COLOR_DEGREE = 3            # ts_field_colors evaluates the bands 0..3
 
@@ -79,20 +82,9 @@ class MeshConfig:
             raise ValueError(f"surface_level = {self.surface_level} is not above 16 exp(-extent_sigmas^2 / 2) = "
                              f"{level_floor(self.extent_sigmas):.4f}: the density may reach it outside every Gaussian's "
                              "box and the sparse grid would miss surface")
-        if int(self.resolution) < 1:
-            raise ValueError("resolution must be at least 1")
-        if int(self.max_workspace_bytes) < 1:
-            raise ValueError("max_workspace_bytes must be positive")
-        if self.bounds is not None:
-            _check_bounds(*self.bounds)
+        check_config(self)
         if self.color_sh_degree is not None and not 0 <= int(self.color_sh_degree) <= MAX_COLOR_DEGREE:
             raise ValueError(f"color_sh_degree must be in 0..{MAX_COLOR_DEGREE}")
-        if self.target_faces is not None and int(self.target_faces) < 1:
-            raise ValueError("target_faces must be at least 1")
-        if self.clean is not None:
-            from .clean import CleanConfig
-            if not isinstance(self.clean, CleanConfig):
-                raise ValueError("clean must be a CleanConfig or None")
 
 
 @dataclass
@@ -104,37 +96,6 @@ class TriangleMesh:
     faces: Tensor
     normals: Optional[Tensor]
     colors: Optional[Tensor] = None
-
-
-def _check_bounds(lo, hi):
-    lo, hi = [float(v) for v in lo], [float(v) for v in hi]
-    if len(lo) != 3 or len(hi) != 3:
-        raise ValueError("bounds must be (lo [3], hi [3])")
-    if not all(math.isfinite(v) for v in lo + hi):
-        raise ValueError("bounds must be finite")
-    if not all(b > a for a, b in zip(lo, hi)):
-        raise ValueError("bounds must be non-empty on every axis")
-    return lo, hi
-
-
-def make_grid(lo, hi, resolution: int):
-    """-> ``(lo float32 x 3, h float32, cells per axis)``: cubes of edge ``h = max(hi - lo) / resolution`` and
-    ``ceil((hi_a - lo_a) / h)`` cells on axis a (``resolution`` on the longest).  ``lo`` and ``hi`` are rounded to
-    float32 first; corner (i, j, k) sits at the float32 ``lo + (i, j, k) * h``."""
-    lo, hi = _check_bounds(lo, hi)
-    res = int(resolution)
-    if res < 1:
-        raise ValueError("resolution must be at least 1")
-    f32 = lambda v: ctypes.c_float(v).value
-    lo, hi = [f32(v) for v in lo], [f32(v) for v in hi]
-    ext = [b - a for a, b in zip(lo, hi)]
-    longest = max(ext)
-    h = f32(longest / res)
-    if not (longest > 0 and h > 0 and math.isfinite(h)):
-        raise ValueError("bounds must be non-empty on every axis")
-    # (hi_a - lo_a) / h with h = longest / res, taken as a ratio so that the longest axis has exactly `res` cells
-    cells = [max(1, math.ceil(e / longest * res - 1e-9)) for e in ext]
-    return lo, h, cells
 
 
 class _Chunk:
@@ -288,101 +249,43 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
             raise ValueError(f"the union of the Gaussians' boxes is no usable bound ({e}); give bounds") from None
     else:
         lo_hi = _check_bounds(*cfg.bounds)
-    glo, h, cells = make_grid(*lo_hi, cfg.resolution)
-    nb = [-(-c // BRICK) for c in cells]
-    total_bricks = nb[0] * nb[1] * nb[2]
-    if total_bricks > cap:
-        raise ValueError(f"the flags of {total_bricks} bricks do not fit max_workspace_bytes = {cap}")
-    one = int(lib.ts_mesh_chunk_bytes(n, 1))
-    if one > cap:
-        raise ValueError(f"max_workspace_bytes = {cap} is below the {one} bytes one brick over {n} Gaussians needs")
-    grid_host = (ctypes.c_float * 4)(*glo, h)
-    cells_host = (ctypes.c_int32 * 3)(*cells)
-    f32 = dict(dtype=torch.float32, device=dev)
-    tri_keys, tri_pos, tri_cell = [], [], []
+    grid = BrickGrid(*lo_hi, cfg.resolution, cap)
+    grid.check_fits(int(lib.ts_mesh_chunk_bytes(n, 1)), f"one brick over {n} Gaussians")
     dbg = {k: [] for k in ("corners", "knn", "density", "knn_fallback")} if return_debug else None
-    chunks = 0
+    tail = {}
     with torch.cuda.device(dev):
         s = _stream(dev)
-        if cfg.sparse:
-            flags = torch.zeros((total_bricks,), dtype=torch.uint8, device=dev)
-            _call("ts_mesh_mark", lib.ts_mesh_mark, n, _ptr(boxes), grid_host, cells_host, _ptr(flags), s)
-            active = torch.nonzero(flags).view(-1)                      # ascending, as the survivors of section 6f
-            del flags
-        else:
-            active = torch.arange(total_bricks, dtype=torch.int64, device=dev)
-        a = int(active.shape[0])
-        if a:
-            per = largest(lambda b: int(lib.ts_mesh_chunk_bytes(n, b)) <= cap, min(a, _MAX_BRICKS))
-            ck = _Chunk(lib, n, per, dev)
-            for b0 in range(0, a, per):
-                b = min(per, a - b0)
-                q = b * BRICK_CORNERS
-                chunks += 1
-                ids = active[b0:b0 + b]
-                _call("ts_mesh_corners", lib.ts_mesh_corners, b, _ptr(ids), grid_host, cells_host, _ptr(ck.corners), s)
-                if return_debug:
-                    # brick by brick, for the per-brick share of brute-force queries; the lists are the same
-                    for i in range(b):
-                        r = slice(i * BRICK_CORNERS, (i + 1) * BRICK_CORNERS)
-                        knn(lib, pk, ck.corners[r], BRICK_CORNERS, EXTRACT_K, ck.knn_dist[r], ck.knn_idx[r], ck.knn_ws,
-                            ck.stats[i], s)
-                else:
-                    knn(lib, pk, ck.corners, q, EXTRACT_K, ck.knn_dist, ck.knn_idx, ck.knn_ws, None, s)
-                _call("ts_mesh_density", lib.ts_mesh_density, n, b, _ptr(ids), grid_host, cells_host, _ptr(ck.corners),
-                      _ptr(ck.knn_idx), _ptr(pk.records), _ptr(ck.density), s)
-                if return_debug:
-                    dbg["corners"].append(ck.corners[:q].view(b, BRICK_CORNERS, 3).clone())
-                    dbg["knn"].append(ck.knn_idx[:q].view(b, BRICK_CORNERS, EXTRACT_K).clone())
-                    dbg["density"].append(ck.density[:q].view(b, BRICK_CORNERS).clone())
-                    dbg["knn_fallback"].append(ck.stats[:b, 0].clone())
-                # no corner above the level: no triangle, and nothing to launch
-                if not bool((ck.density[:q] > level).any()):
-                    continue
-                _call("ts_mesh_count", lib.ts_mesh_count, b, _ptr(ids), grid_host, cells_host, level, _ptr(ck.density),
-                      _ptr(ck.counts), s)
-                ends = torch.cumsum(ck.counts[:b], 0, dtype=torch.int64)
-                t = int(ends[-1])
-                if t == 0:
-                    continue
-                ck.offsets[:b] = ends - ck.counts[:b]
-                keys = torch.empty((t, 3), dtype=torch.int64, device=dev)
-                pos = torch.empty((t, 3, 3), **f32)
-                cell = torch.empty((t,), dtype=torch.int64, device=dev) if return_debug else None
-                _call("ts_mesh_emit", lib.ts_mesh_emit, b, _ptr(ids), grid_host, cells_host, level, _ptr(ck.density),
-                      _ptr(ck.offsets), _ptr(keys), _ptr(pos), _ptr(cell), s)
-                tri_keys.append(keys)
-                tri_pos.append(pos)
-                if return_debug:
-                    tri_cell.append(cell)
-            del ck
-        keys = cat(tri_keys, (0, 3), torch.int64, dev)
-        pos = cat(tri_pos, (0, 3, 3), torch.float32, dev)
-        del tri_keys, tri_pos
-        if keys.shape[0]:
-            uniq, inv = torch.unique(keys.view(-1), sorted=True, return_inverse=True)
-            v = int(uniq.shape[0])
-            if v >= 2 ** 31:
-                raise ValueError(f"{v} vertices do not fit int32 faces; lower the resolution")
-            occ = torch.arange(inv.shape[0], dtype=torch.int64, device=dev)
-            first = torch.full((v,), inv.shape[0], dtype=torch.int64, device=dev).scatter_reduce_(
-                0, inv, occ, reduce="amin", include_self=True)
-            vertices = pos.view(-1, 3).index_select(0, first)
-            faces = inv.view(-1, 3).to(torch.int32)
-            del uniq, inv, occ, first
-        else:
-            vertices = torch.empty((0, 3), **f32)
-            faces = torch.empty((0, 3), dtype=torch.int32, device=dev)
+
+        def mark(flags):
+            _call("ts_mesh_mark", lib.ts_mesh_mark, n, _ptr(boxes), grid.grid_host, grid.cells_host, _ptr(flags), s)
+
+        def fill(ck, ids, b):
+            q = b * BRICK_CORNERS
+            _call("ts_mesh_corners", lib.ts_mesh_corners, b, _ptr(ids), grid.grid_host, grid.cells_host,
+                  _ptr(ck.corners), s)
+            if return_debug:
+                # brick by brick, for the per-brick share of brute-force queries; the lists are the same
+                for i in range(b):
+                    r = slice(i * BRICK_CORNERS, (i + 1) * BRICK_CORNERS)
+                    knn(lib, pk, ck.corners[r], BRICK_CORNERS, EXTRACT_K, ck.knn_dist[r], ck.knn_idx[r], ck.knn_ws,
+                        ck.stats[i], s)
+            else:
+                knn(lib, pk, ck.corners, q, EXTRACT_K, ck.knn_dist, ck.knn_idx, ck.knn_ws, None, s)
+            _call("ts_mesh_density", lib.ts_mesh_density, n, b, _ptr(ids), grid.grid_host, grid.cells_host,
+                  _ptr(ck.corners), _ptr(ck.knn_idx), _ptr(pk.records), _ptr(ck.density), s)
+            if return_debug:
+                dbg["corners"].append(ck.corners[:q].view(b, BRICK_CORNERS, 3).clone())
+                dbg["knn"].append(ck.knn_idx[:q].view(b, BRICK_CORNERS, EXTRACT_K).clone())
+                dbg["density"].append(ck.density[:q].view(b, BRICK_CORNERS).clone())
+                dbg["knn_fallback"].append(ck.stats[:b, 0].clone())
+            return ck.density
+
+        active = grid.active_bricks(cfg.sparse, mark, dev)
+        keys, pos, cell, chunks = march(lib, grid, active, lambda b: lib.ts_mesh_chunk_bytes(n, b), _MAX_BRICKS,
+                                        lambda b: _Chunk(lib, n, b, dev), fill, level, False, return_debug, s)
+        vertices, faces = weld(keys, pos)
         del pos
-        if cfg.target_faces is not None:
-            from .simplify import SimplifyConfig, _simplify
-            simplified = {}
-            vertices, faces = _simplify(lib, vertices, faces, SimplifyConfig(target_faces=int(cfg.target_faces),
-                                                                             max_workspace_bytes=cap), s, simplified)
-        if cfg.clean is not None:
-            from .clean import _clean
-            cleaned = {}
-            vertices, faces, _ = _clean(lib, vertices, faces, cfg.clean, s, cleaned)
+        vertices, faces = mesh_tail(lib, vertices, faces, cfg, s, tail)
         normals, colors = _at_points(lib, pk, vertices, cap, s, cfg.normals, coeffs)
     mesh = TriangleMesh(vertices, faces, normals, colors)
     if not return_debug:
@@ -390,10 +293,6 @@ def extract_mesh(model, config: Optional[MeshConfig] = None, return_debug: bool 
     shapes = {"corners": ((0, BRICK_CORNERS, 3), torch.float32), "knn": ((0, BRICK_CORNERS, EXTRACT_K), torch.int32),
               "density": ((0, BRICK_CORNERS), torch.float32), "knn_fallback": ((0,), torch.int32)}
     debug = {k: cat(v, *shapes[k], dev) for k, v in dbg.items()}
-    debug.update(active_bricks=active, keys=keys, cell=cat(tri_cell, (0,), torch.int64, dev), chunks=chunks,
-                 total_bricks=total_bricks, grid={"lo": tuple(glo), "h": h, "cells": tuple(cells)})
-    if cfg.target_faces is not None:
-        debug["simplify"] = simplified
-    if cfg.clean is not None:
-        debug["clean"] = cleaned
+    debug.update(active_bricks=active, keys=keys, cell=cell, chunks=chunks, total_bricks=grid.total_bricks,
+                 grid=grid.debug, **tail)
     return mesh, debug

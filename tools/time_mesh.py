@@ -48,12 +48,9 @@ HBM_PEAK = 8.0e12               # bytes / s, the MI355X's HBM3E
 @torch.no_grad()
 def fallback_share(model, pk, cfg, active, grid, chunk_bricks=1024):
     """The share of the active bricks' corner queries that take ``ts_knn``'s brute-force pass."""
-    import ctypes
     lib = _lib.load()
     dev = torch.device(DEV)
     n = pk.means.shape[0]
-    grid_host = (ctypes.c_float * 4)(*grid["lo"], grid["h"])
-    cells_host = (ctypes.c_int32 * 3)(*grid["cells"])
     q = chunk_bricks * BRICK_CORNERS
     ws = torch.empty(int(lib.ts_knn_ws_bytes(n, q, EXTRACT_K)), dtype=torch.uint8, device=dev)
     corners = torch.empty((q, 3), device=dev)
@@ -65,7 +62,7 @@ def fallback_share(model, pk, cfg, active, grid, chunk_bricks=1024):
     for b0 in range(0, active.shape[0], chunk_bricks):
         ids = active[b0:b0 + chunk_bricks]
         b = int(ids.shape[0])
-        assert lib.ts_mesh_corners(b, _ptr(ids), grid_host, cells_host, _ptr(corners), s) == 0
+        assert lib.ts_mesh_corners(b, _ptr(ids), grid.grid_host, grid.cells_host, _ptr(corners), s) == 0
         assert lib.ts_knn(n, _ptr(pk.means), b * BRICK_CORNERS, _ptr(corners), EXTRACT_K, _ptr(dist), _ptr(idx),
                           _ptr(ws), _ptr(stats), s) == 0
         took += int(stats[0])
@@ -185,18 +182,19 @@ def main():
     peak = torch.cuda.max_memory_allocated() - base
     mesh = run()
     # the bricks, from a run of the marking stage alone
-    from tinysplat_amd.mesh import BRICK, gaussian_boxes, make_grid
-    import ctypes
+    from tinysplat_amd._bricks import BrickGrid
+    from tinysplat_amd.mesh import gaussian_boxes
     boxes = gaussian_boxes(model, cfg.extent_sigmas)
-    glo, gh, cells = make_grid(boxes[:, :3].amin(0).tolist(), boxes[:, 3:].amax(0).tolist(), cfg.resolution)
-    nb = [-(-c // BRICK) for c in cells]
-    bricks = nb[0] * nb[1] * nb[2]
-    flags = torch.zeros((bricks,), dtype=torch.uint8, device=DEV)
+    grid = BrickGrid(boxes[:, :3].amin(0).tolist(), boxes[:, 3:].amax(0).tolist(), cfg.resolution,
+                     cfg.max_workspace_bytes)
+    cells, bricks = grid.cells, grid.total_bricks
     lib = _lib.load()
-    assert lib.ts_mesh_mark(args.n, _ptr(boxes), (ctypes.c_float * 4)(*glo, gh), (ctypes.c_int32 * 3)(*cells),
-                            _ptr(flags), _stream(torch.device(DEV))) == 0
-    marked = torch.nonzero(flags).view(-1)
-    active = marked if cfg.sparse else torch.arange(bricks, dtype=torch.int64, device=DEV)
+
+    def mark(flags):
+        assert lib.ts_mesh_mark(args.n, _ptr(boxes), grid.grid_host, grid.cells_host, _ptr(flags),
+                                _stream(torch.device(DEV))) == 0
+    marked = grid.active_bricks(True, mark, DEV)
+    active = marked if cfg.sparse else grid.active_bricks(False, None, DEV)
     emit("extract_mesh", total, vertices=int(mesh.vertices.shape[0]), faces=int(mesh.faces.shape[0]), cells=cells,
          bricks=bricks, marked_bricks=int(marked.shape[0]), evaluated_bricks=int(active.shape[0]),
          active_share=round(int(marked.shape[0]) / bricks, 5), peak_mib=round(peak / 2 ** 20, 1),
@@ -245,7 +243,6 @@ def main():
         del plain, out
     if args.clean:
         clean_stage(model, pk, cfg, ccfg, args.reps, emit, shape)
-    grid = {"lo": glo, "h": gh, "cells": cells}
     emit("fallback share", 0.0, share=round(fallback_share(model, pk, cfg, active, grid), 5),
          corner_queries=int(active.shape[0]) * BRICK_CORNERS, **shape)
     if args.out:

@@ -42,14 +42,16 @@ def sphere_depth(view, proj, width, height, dev):
     return torch.where((disc > 0) & (z > 0), z, torch.zeros_like(z)).float().contiguous()
 
 
-def projected_pairs(table_host, active, glo, h, cells, znear):
-    """(pairs with the cull, pairs without): a double restatement of csrc/tsdf_math.h's sphere test per (brick, camera)."""
+def projected_pairs(table_host, active, bricks, znear):
+    """(pairs with the cull, pairs without): a double restatement of csrc/tsdf_math.h's sphere test per (brick, camera) of
+    the ``active`` bricks of the ``BrickGrid`` ``bricks``."""
     import numpy as np
     from tinysplat_amd import _lib
-    nb = [-(-c // 8) for c in cells]
+    from tinysplat_amd._bricks import BRICK
+    glo, h, cells, nb = bricks.lo, bricks.h, bricks.cells, bricks.bricks
     b = np.stack((active % nb[0], (active // nb[0]) % nb[1], active // (nb[0] * nb[1])), -1)
-    i0 = b * 8
-    i1 = np.minimum(i0 + 8, np.asarray(cells)[None, :])
+    i0 = b * BRICK
+    i1 = np.minimum(i0 + BRICK, np.asarray(cells)[None, :])
     p0, p1 = np.asarray(glo)[None, :] + i0 * h, np.asarray(glo)[None, :] + i1 * h
     centre = 0.5 * (p0 + p1)
     radius = np.linalg.norm(0.5 * (p1 - p0), axis=1) + 0.0625 * h
@@ -86,7 +88,7 @@ def main(argv=None):
     import torch
     import tsdf_cases as TC
     from tinysplat_amd import FusionConfig, _lib, fuse_depth_maps, fusion
-    from tinysplat_amd.mesh import make_grid
+    from tinysplat_amd._bricks import BRICK_CORNERS, BrickGrid, count_and_emit
     dev = args.device
     lib = _lib.load()
     cams, depths = [], []
@@ -121,12 +123,10 @@ def main(argv=None):
     s = torch.cuda.current_stream().cuda_stream
     for res in args.resolution:
         cfg = FusionConfig(resolution=res, bounds=bounds, max_workspace_bytes=4 << 30)
-        glo, h, cells = make_grid(*bounds, res)
-        trunc = ctypes.c_float(cfg.trunc_voxels * h).value
-        grid = (ctypes.c_float * 4)(*glo, h)
-        cells_c = (ctypes.c_int32 * 3)(*cells)
-        nb = [-(-c // 8) for c in cells]
-        total = nb[0] * nb[1] * nb[2]
+        bricks = BrickGrid(*bounds, res, cfg.max_workspace_bytes)
+        cells, total = bricks.cells, bricks.total_bricks
+        trunc = ctypes.c_float(cfg.trunc_voxels * bricks.h).value
+        grid, cells_c = bricks.grid_host, bricks.cells_host
         flags = torch.zeros((total,), dtype=torch.uint8, device=dev)
 
         def mark():
@@ -136,7 +136,7 @@ def main(argv=None):
         t_mark, _ = timed(mark)
         active = torch.nonzero(flags).view(-1)
         a = int(active.shape[0])
-        q = a * 729
+        q = a * BRICK_CORNERS
         acc = torch.zeros((q,), dtype=torch.float64, device=dev)
         cnt = torch.zeros((q,), dtype=torch.int32, device=dev)
         field = torch.empty((q,), dtype=torch.float32, device=dev)
@@ -150,23 +150,15 @@ def main(argv=None):
         t_cull, _ = timed(lambda: integrate(0))
         t_all, _ = timed(lambda: integrate(_lib.TSDF_NO_CULL))
         t_cull, t_all = t_cull - t_zero, t_all - t_zero
-        pairs_cull, pairs_all = projected_pairs(table_host, active.cpu().numpy(), glo, h, cells, cfg.znear)
+        pairs_cull, pairs_all = projected_pairs(table_host, active.cpu().numpy(), bricks, cfg.znear)
         t_field, _ = timed(lambda: _lib.check(lib.ts_tsdf_field(a, acc.data_ptr(), cnt.data_ptr(), 1, field.data_ptr(), s),
                                               "ts_tsdf_field"))
         counts = torch.empty((a,), dtype=torch.int32, device=dev)
         offsets = torch.empty((a,), dtype=torch.int64, device=dev)
 
         def mesh():
-            _lib.check(lib.ts_mesh_count_observed(a, active.data_ptr(), grid, cells_c, 0.0, field.data_ptr(),
-                                                  counts.data_ptr(), s), "ts_mesh_count_observed")
-            ends = torch.cumsum(counts, 0, dtype=torch.int64)
-            t = int(ends[-1])
-            offsets.copy_(ends - counts)
-            keys = torch.empty((t, 3), dtype=torch.int64, device=dev)
-            pos = torch.empty((t, 3, 3), dtype=torch.float32, device=dev)
-            _lib.check(lib.ts_mesh_emit_observed(a, active.data_ptr(), grid, cells_c, 0.0, field.data_ptr(), offsets.data_ptr(),
-                                                 keys.data_ptr(), pos.data_ptr(), None, s), "ts_mesh_emit_observed")
-            return t
+            emitted = count_and_emit(lib, bricks, active, a, field, counts, offsets, 0.0, True, False, s)
+            return emitted[0].shape[0] if emitted is not None else 0
         t_mesh, tris = timed(mesh)
         t_whole, fused = timed(lambda: fuse_depth_maps(cams, depths, cfg))
         say(f"resolution {res}: cells {tuple(cells)}, {a} of {total} bricks active, {tris} triangles, "
