@@ -167,6 +167,18 @@ int ts_colors_pack_fwd(int32_t n, int32_t degrees_to_use, int32_t num_bases, con
                        const float* xys, const int32_t* radii, const float* conics, const float* opacity,
                        const int32_t* cum_tiles_hit, const ts_camera* cam_host, const float* depths,
                        float* splats, void* stream);
+/* The same launch, which also leaves one 16-byte SPAN RECORD per Gaussian in row_spans (4 n int32 words, 16-byte
+ * aligned; layout in csrc/row_spans.h): the 16x16 tile columns [lo, hi) of every tile row of its box in this camera's
+ * stripe, as ts::TightTest::row_range leaves them (tight != 0) or the bounding box's (tight = 0) - what the list build
+ * would compute from xys, radii and the record.  Every Gaussian gets one: the empty record where nothing is listed
+ * (culled, outside the stripe, live[i] == 0), a "not representable" mark beyond six rows or 256 columns.  The records
+ * are computed while the coefficient loads are in flight.  row_spans = NULL: ts_colors_pack_fwd. */
+int ts_colors_pack_spans_fwd(int32_t n, int32_t degrees_to_use, int32_t num_bases, const float* means3d,
+                             const float* origin, const float* colors_dc, const float* colors_rest,
+                             uint8_t* clamp_mask, const int32_t* live, int32_t channels, int32_t flags,
+                             const float* xys, const int32_t* radii, const float* conics, const float* opacity,
+                             const int32_t* cum_tiles_hit, const ts_camera* cam_host, const float* depths,
+                             float* splats, int32_t tight, int32_t* row_spans, void* stream);
 
 /* ========================= rasterize_gaussians (rasterize.py:44,50) =========================== */
 /* Stage order: ts_scan_tiles -> (read total) -> ts_bin_count -> ts_tile_offsets -> ts_bin_scatter
@@ -280,6 +292,13 @@ int32_t ts_bin_stage_capacity(void);
 int ts_bin_emit_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
                        const ts_camera* cam_host, const int32_t* cum_tiles_hit, int64_t capacity, int32_t* bin_ws,
                        int32_t* scratch, void* stream);
+/* ts_bin_emit_groups with the SPAN RECORDS the colour stage left (ts_colors_pack_spans_fwd; 4 n int32 words, 16-byte
+ * aligned): the walk reads one record per Gaussian instead of xys, radii and splats, which it touches only for a
+ * Gaussian whose record says "not representable".  Same lists.  row_spans = NULL: ts_bin_emit_groups.  The records must
+ * come from the same camera, and from tight != 0 exactly where splats != NULL here. */
+int ts_bin_emit_groups_spans(int32_t n, const float* xys, const int32_t* radii, const float* splats,
+                             const int32_t* row_spans, const ts_camera* cam_host, const int32_t* cum_tiles_hit,
+                             int64_t capacity, int32_t* bin_ws, int32_t* scratch, void* stream);
 int ts_emit_offsets(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins,
                     const int32_t* cum_tiles_hit, int64_t capacity, int32_t* longest_list, void* stream);
 int ts_bin_gather_groups(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t* tile_bins, int32_t* bucket_ids,
@@ -421,6 +440,10 @@ int ts_reduce_partials(int32_t n, int32_t channels, int32_t flags, const int32_t
                                           TS_HINT_BALANCED_WALK; ignored otherwise.  ts_frame_fwd_prepare then enqueues
                                           the colour stage only; ts_frame_fwd_composite emit, offsets, fine hop, sort,
                                           raster.  Same lists, same frame */
+#define TS_FRAME_ROW_SPANS (4096)       /* SPAN RECORDS (csrc/row_spans.h) in a ONE WALK frame with `row_spans` set: the colour
+                                          stage writes every Gaussian's tile columns per row, the emit launch walks those
+                                          instead of computing them (ts_colors_pack_spans_fwd, ts_bin_emit_groups_spans).
+                                          Ignored in every other form: no record is computed there.  Same lists */
 #define TS_FRAME_SURVIVORS 512         /* SURVIVOR LISTS (csrc/raster.hip): the forward compositing pass hands the entries
                                           it staged to the backward pass, which replays those instead of re-culling the
                                           lists (same rows, same gradients).  Only with the in-kernel sort on 16x16 lists
@@ -460,6 +483,9 @@ typedef struct ts_frame {
     /* TS_FRAME_SURVIVORS: int32 workspace, 8 * num_tiles rounded up to 64, plus one word per list entry (the buffers'
      * capacity) - written by ts_frame_fwd_composite, read by ts_frame_bwd_composite */
     int32_t* survivors;
+    /* TS_FRAME_ROW_SPANS: 4 n int32 words (one 16-byte record per Gaussian, 16-byte aligned), or NULL - written by
+     * ts_frame_fwd_prepare, read by ts_frame_fwd_composite */
+    int32_t* row_spans;
 } ts_frame;
 int32_t ts_frame_struct_bytes(void);       /* sizeof(ts_frame): bindings check their mirror against it */
 int ts_frame_fwd_project(const ts_frame* f, void* stream);

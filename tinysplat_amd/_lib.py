@@ -33,6 +33,7 @@ FRAME_LIST_STATS = 256
 FRAME_SURVIVORS = 512
 FRAME_GROUP_COUNTS = 1024
 FRAME_ONE_WALK = 2048
+FRAME_ROW_SPANS = 4096
 PARTIAL_ROW_FLOATS = 12          # TS_PARTIAL_ROW_FLOATS: floats per (tile, Gaussian) gradient row slot
 
 
@@ -75,7 +76,7 @@ class TsFrame(ctypes.Structure):
                     "v_out_img", "partials", "row_flags",
                     "v_xy", "v_conic", "v_colors", "v_depth", "v_opacity",
                     "v_means", "v_scales", "v_quats", "v_colors_dc", "v_colors_rest",
-                    "out_depth", "v_out_depth", "survivors")])
+                    "out_depth", "v_out_depth", "survivors", "row_spans")])
 
 
 _FRAME = POINTER(TsFrame)
@@ -146,6 +147,7 @@ SIGNATURES = {
     "ts_bin_one_walk_form": (c_int32, [c_int32, c_int32]),
     "ts_bin_stage_capacity": (c_int32, []),
     "ts_bin_emit_groups": (c_int32, [c_int32, _P, _P, _P, _CAM, _P, c_int64, _P, _P, _P]),
+    "ts_bin_emit_groups_spans": (c_int32, [c_int32, _P, _P, _P, _P, _CAM, _P, c_int64, _P, _P, _P]),
     "ts_emit_offsets": (c_int32, [c_int32, c_int32, _P, _P, _P, c_int64, _P, _P]),
     "ts_bin_gather_groups": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P]),
     "ts_sort_tiles_stats": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, c_int32, _P, _P, _P]),
@@ -155,6 +157,8 @@ SIGNATURES = {
     "ts_cut_tiles": (c_int32, [_CAM, _P, _P]),
     "ts_colors_pack_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_int32, c_int32,
                                      _P, _P, _P, _P, _P, _CAM, _P, _P, _P]),
+    "ts_colors_pack_spans_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_int32, c_int32,
+                                           _P, _P, _P, _P, _P, _CAM, _P, _P, c_int32, _P, _P]),
     "ts_pack_splats": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _CAM, _P, _P, _P]),
     "ts_raster_fwd": (c_int32, [c_int32, c_int32, _CAM, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ts_raster_bwd": (c_int32, [c_int32, c_int32, c_int64, _CAM, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

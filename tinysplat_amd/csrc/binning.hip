@@ -29,6 +29,7 @@
 #include "../../include/tinysplat_hip.h"
 #include "host_util.h"
 #include "pack.h"
+#include "row_spans.h"
 #include "splat_math.h"
 
 namespace {
@@ -969,6 +970,78 @@ inline bool one_walk_form(int n, int num_tiles) {
     return g.groups <= kEmitMaxGroups && g.rows_end <= g.tile_start;
 }
 
+// SPAN WALK of the emit launch (row_spans.h).  The colour stage has left one 16-byte record per Gaussian with the tile
+// columns of every row of its box - computed there by the very code walk_chunk runs, in the shadow of that launch's
+// coefficient stream - so the walk here is one load per Gaussian, all kSpanPre of a thread up front, and two loops.  It
+// reads neither xys nor radii nor the records, except for a Gaussian whose record says it is not representable (more
+// than six rows, a column from 256 on): that lane computes the Gaussian as walk_chunk does.  The same lists as walk_chunk,
+// emitted a run at a time.
+constexpr int kSpanPre = 4;                              // a chunk of <= 4096 Gaussians in one round
+template <typename Emit>
+__device__ __forceinline__ void walk_gaussian(int i, const float* __restrict__ xys, const int* __restrict__ radii,
+                                              const float4* __restrict__ splats, const ts_camera& cam, Emit emit) {
+    const int ws = cam.wide_tiles ? 1 : 0;
+    const int tbx = (cam.tile_bounds_x + ws) >> ws;
+    const int r = radii[i];
+    if (r <= 0) return;
+    const float2 xy = reinterpret_cast<const float2*>(xys)[i];
+    float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
+    if (splats) { q0 = splats[3 * (size_t)i]; q1 = splats[3 * (size_t)i + 1]; }
+    const ts::TileBox b = ts::tile_bbox(xy.x, xy.y, (float)r, cam.tile_bounds_x, cam.tile_bounds_y, cam.tile_row0,
+                                        cam.tile_rows);
+    if (b.maxy <= b.miny || b.maxx <= b.minx) return;
+    const TightTest tight(splats != nullptr, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, (float)r);
+    if (tight.cull_all) return;
+    for (int ty = b.miny; ty < b.maxy; ++ty) {
+        int lo, hi;
+        tight.row_range(ty, b.minx, b.maxx, lo, hi);
+        if (hi <= lo) continue;
+        for (int tx = lo >> ws; tx <= (hi - 1) >> ws; ++tx) emit((ty - cam.tile_row0) * tbx + tx, i);
+    }
+}
+// emit(t, len, i): the Gaussian enters the len <= 32 consecutive lists from t on, all of one group of kCoarseTiles lists -
+// a row of a record is a run of consecutive lists already, cut here where it crosses into the next group.
+template <typename Emit>
+__device__ __forceinline__ void walk_spans(int g0, int g1, const int4* __restrict__ spans,
+                                           const float* __restrict__ xys, const int* __restrict__ radii,
+                                           const float4* __restrict__ splats, const ts_camera& cam, Emit emit) {
+    const int ws = cam.wide_tiles ? 1 : 0;
+    const int tbx = (cam.tile_bounds_x + ws) >> ws;
+    for (int base = g0 + threadIdx.x; base < g1; base += kSpanPre * kBinThreads) {
+        int4 rec[kSpanPre];
+#pragma unroll
+        for (int u = 0; u < kSpanPre; ++u) {
+            const int i = base + u * kBinThreads;
+            rec[u] = i < g1 ? spans[i] : make_int4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < kSpanPre; ++u) {
+            ts::RowSpans s;
+            s.w[0] = (unsigned int)rec[u].x; s.w[1] = (unsigned int)rec[u].y;
+            s.w[2] = (unsigned int)rec[u].z; s.w[3] = (unsigned int)rec[u].w;
+            const int rows = ts::spans_rows(s);
+            if (rows == 0) continue;
+            const int i = base + u * kBinThreads;
+            if (rows == ts::kSpanFallback) {
+                walk_gaussian(i, xys, radii, splats, cam, [&](int t, int id) { emit(t, 1, id); });
+                continue;
+            }
+            int t0 = ts::spans_first_row(s) * tbx;       // first list of the row
+            for (int k = 0; k < rows; ++k, t0 += tbx) {
+                int lo, hi;
+                ts::spans_pop_row(s, lo, hi);
+                if (hi <= lo) continue;
+                const int last = t0 + ((hi - 1) >> ws);
+                for (int t = t0 + (lo >> ws); t <= last;) {
+                    const int len = min(last - t + 1, kCoarseTiles - (t & (kCoarseTiles - 1)));
+                    emit(t, len, i);
+                    t += len;
+                }
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(kBinThreads) void bin_scatter_emit_kernel(
     int n, int chunk, const float* __restrict__ xys, const int* __restrict__ radii,
     const float4* __restrict__ splats, const ts_camera cam, int groups, const int* __restrict__ cum,
@@ -1061,6 +1134,118 @@ __global__ __launch_bounds__(kBinThreads) void bin_scatter_emit_kernel(
     } else {
         walk_chunk(g0, g1, xys, radii, splats, cam, [&](int t, int i) {
             dst[atomicAdd(&cursor[t >> kCoarseShift], 1)] = i | ((t & (kCoarseTiles - 1)) << kCoarseIdBits);
+        });
+    }
+}
+
+// The emit launch over SPAN RECORDS: bin_scatter_emit_kernel with walk_spans in both of its walks and ONE STAGED ITEM PER
+// RUN.  (A kernel of its own beside the one above, not a template of it: run staging in the shared body cost the
+// launch without records 2.4 us, profiles/r26_row_spans.txt, and that launch is to stay what it was.)
+__global__ __launch_bounds__(kBinThreads) void bin_scatter_spans_kernel(
+    int n, int chunk, const float* __restrict__ xys, const int* __restrict__ radii,
+    const float4* __restrict__ splats, const int4* __restrict__ spans, const ts_camera cam, int groups,
+    const int* __restrict__ cum, long long capacity, int* __restrict__ counts, int* __restrict__ starts,
+    int* __restrict__ scratch) {
+    extern __shared__ int lds[];
+    __shared__ int staged;
+    // capacity guard, read here because the offsets launch runs behind this one; a wrapped total places nothing either.
+    // (The three words of cum_tiles_hit are in flight together, while the histogram is cleared)
+    const int g0 = min(n, (int)blockIdx.x * chunk), g1 = min(n, g0 + chunk);
+    const int total = cum[n - 1];
+    const int chunk_base = g0 > 0 ? cum[g0 - 1] : 0;
+    const int chunk_end = g1 > g0 ? cum[g1 - 1] : chunk_base;
+    int* hist = lds;
+    int* cursor = lds + groups;
+    unsigned int* words = reinterpret_cast<unsigned int*>(lds + 2 * groups);
+    unsigned short* grp = reinterpret_cast<unsigned short*>(words + kStageCap);
+    const int tid = threadIdx.x;
+    for (int j = tid; j < groups; j += kBinThreads) hist[j] = 0;
+    if (tid == 0) staged = 0;
+    __syncthreads();
+    if (total < 0 || (capacity >= 0 && (long long)total > capacity)) return;
+    const int room = chunk_end - chunk_base;                         // the chunk's bounding-box slots
+    auto walk = [&](auto emit) { walk_spans(g0, g1, spans, xys, radii, splats, cam, emit); };     // emit(t, len, i)
+    // ONE STAGED ITEM PER RUN: the word carries the id and the first tile-in-group, the 5 spare bits of the 16-bit group
+    // index carry len - 1; the histogram takes the whole run in one atomic, the append happens once per run
+    static_assert(kEmitMaxGroups <= (1 << 11) && kCoarseTiles <= 32, "group index in 11 bits, len - 1 in 5");
+    walk([&](int t, int len, int i) {
+        const int g = t >> kCoarseShift;
+        atomicAdd(&hist[g], len);
+        const unsigned long long m = __ballot(1);                     // the lanes that emit in this step
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32),
+                                                        __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
+        int base = 0;
+        if (rank == 0) base = atomicAdd(&staged, (int)__popcll(m));
+        base = __builtin_amdgcn_readfirstlane(base);                  // (the first active lane is the one of rank 0)
+        const int slot = base + rank;
+        if (slot < kStageCap) {
+            words[slot] = (unsigned int)i | ((unsigned int)(t & (kCoarseTiles - 1)) << kCoarseIdBits);
+            grp[slot] = (unsigned short)(g | ((len - 1) << 11));
+        }
+    });
+    __syncthreads();
+    const int items = staged;                                         // runs the chunk lists
+    int pairs;                                                        // everything it lists: the histogram's total
+    bool sound;
+    {   // exclusive scan of the histogram: two groups per thread; the chunk's two rows
+        const int a = 2 * tid;
+        const int h0 = a < groups ? hist[a] : 0, h1 = a + 1 < groups ? hist[a + 1] : 0;
+        const int ex = block_inclusive_scan<kBinThreads / 64>(h0 + h1, &pairs) - h0 - h1;
+        // a chunk cannot list more than its bounding-box slots; were it ever to, it lists nothing rather than write
+        // beyond its region
+        sound = pairs <= room;
+        int* crow = counts + (size_t)blockIdx.x * groups;
+        int* srow = starts + (size_t)blockIdx.x * groups;
+        if (a < groups) {
+            cursor[a] = ex;
+            crow[a] = sound ? h0 : 0;
+            srow[a] = chunk_base + ex;
+        }
+        if (a + 1 < groups) {
+            cursor[a + 1] = ex + h0;
+            crow[a + 1] = sound ? h1 : 0;
+            srow[a + 1] = chunk_base + ex + h0;
+        }
+    }
+    __syncthreads();
+    if (!sound) return;
+    int* dst = scratch + chunk_base;
+    if (items <= kStageCap && pairs <= kStageCap) {
+        // ordered by group inside LDS first (every thread keeps its entries and their places in registers while the
+        // buffer changes hands), then copied out: consecutive lanes store consecutive words of the chunk's region.
+        // Straight from the staging order a wave's store touched up to 64 lines, 16 k such words in one burst
+        constexpr int kPer = kStageCap / kBinThreads;
+        static_assert(kStageCap % kBinThreads == 0, "whole staging rounds");
+        unsigned int w[kPer];
+        int at[kPer];                                                 // place of the run's first word | (len - 1) << 16
+        static_assert(kStageCap <= 65536, "a place in 16 bits");
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            const int j = u * kBinThreads + tid;
+            if (j < items) {
+                w[u] = words[j];
+                const int gl = grp[j], len1 = gl >> 11;
+                at[u] = atomicAdd(&cursor[gl & 2047], len1 + 1) | (len1 << 16);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kPer; ++u)
+            if (u * kBinThreads + tid < items) {
+                // the run expanded into its words: tile-in-group first, first + 1, ... (<= 31: a run ends with its group)
+                const int first = at[u] & 0xffff, len1 = at[u] >> 16;
+                for (int q = 0; q <= len1; ++q) words[first + q] = w[u] + ((unsigned int)q << kCoarseIdBits);
+            }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            const int j = u * kBinThreads + tid;
+            if (j < pairs) dst[j] = (int)words[j];
+        }
+    } else {
+        walk([&](int t, int len, int i) {
+            const int at = atomicAdd(&cursor[t >> kCoarseShift], len);
+            for (int q = 0; q < len; ++q) dst[at + q] = i | (((t + q) & (kCoarseTiles - 1)) << kCoarseIdBits);
         });
     }
 }
@@ -1610,11 +1795,28 @@ int32_t ts_bin_stage_capacity(void) { return kStageCap; }
 int ts_bin_emit_groups(int32_t n, const float* xys, const int32_t* radii, const float* splats,
                        const ts_camera* cam, const int32_t* cum_tiles_hit, int64_t capacity, int32_t* bin_ws,
                        int32_t* scratch, void* stream) {
+    return ts_bin_emit_groups_spans(n, xys, radii, splats, nullptr, cam, cum_tiles_hit, capacity, bin_ws, scratch,
+                                    stream);
+}
+
+int ts_bin_emit_groups_spans(int32_t n, const float* xys, const int32_t* radii, const float* splats,
+                             const int32_t* row_spans, const ts_camera* cam, const int32_t* cum_tiles_hit,
+                             int64_t capacity, int32_t* bin_ws, int32_t* scratch, void* stream) {
     if (!cam || !xys || !radii || !cum_tiles_hit || !bin_ws || !scratch) return TS_E_BADARG;
+    if (row_spans && ((uintptr_t)row_spans & 15)) return TS_E_BADARG;
     const int nt = ts_num_tiles(cam);
     if (!one_walk_form(n, nt) || (cam->hints & TS_HINT_BALANCED_WALK)) return TS_E_BADARG;
     const BinGeometry g = bin_geometry(n, nt);
     const size_t lds = (size_t)g.groups * 8 + (size_t)kStageCap * 6;
+    if (row_spans) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_spans_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(bin_scatter_spans_kernel, dim3(g.chunks), dim3(kBinThreads), lds, (hipStream_t)stream, n,
+                           g.chunk, xys, radii, reinterpret_cast<const float4*>(splats),
+                           reinterpret_cast<const int4*>(row_spans), *cam, g.groups, cum_tiles_hit, (long long)capacity,
+                           bin_ws + g.counts, bin_ws + g.starts, scratch);
+        return launch_status();
+    }
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_emit_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(bin_scatter_emit_kernel, dim3(g.chunks), dim3(kBinThreads), lds, (hipStream_t)stream, n, g.chunk,

@@ -133,6 +133,11 @@ inline ListForm list_form(const ts_frame* f) {
         return ListForm::one_walk;
     return ListForm::group;
 }
+// SPAN RECORDS (TS_FRAME_ROW_SPANS): written by the colour stage and walked by the emit launch of a one-walk frame; no
+// other form reads them, so no other form computes them
+inline int32_t* row_spans(const ts_frame* f) {
+    return ((f->flags & TS_FRAME_ROW_SPANS) && list_form(f) == ListForm::one_walk) ? f->row_spans : nullptr;
+}
 // the records the lists are tightened with (TS_FRAME_TIGHT), or null: bounding-box lists
 inline const float* tight_records(const ts_frame* f) { return (f->flags & TS_FRAME_TIGHT) ? f->splats : nullptr; }
 // TS_FRAME_LIST_STATS: the word behind the count word, or null
@@ -186,14 +191,14 @@ int ts_frame_fwd_prepare(const ts_frame* f, void* stream) {
     if (bad(f)) return TS_E_BADARG;
     // colour stage and record packing in one launch; channel 3 of an RGB + depth frame is the depth itself
     // (rasterize.py:48-50), taken from `depths`
-    TS_TRY(TS_ENTRY("ts_colors_pack_fwd",
-                    ts_colors_pack_fwd(f->n, f->sh_degree, f->num_bases, f->means, f->origin, f->colors_dc,
-                                       f->num_bases > 1 ? f->colors_rest : nullptr, f->sh_mask,
-                                       (f->flags & TS_FRAME_STRIPE) ? f->num_tiles_hit : nullptr, f->channels,
-                                       TS_RASTER_LOGIT_OPACITY, f->xys, f->radii, f->conics, f->opacities,
-                                       f->cum_tiles_hit, &f->cam, f->channels == 4 ? f->depths : nullptr, f->splats,
-                                       stream)));
     const float* tight = tight_records(f);
+    TS_TRY(TS_ENTRY("ts_colors_pack_fwd",
+                    ts_colors_pack_spans_fwd(f->n, f->sh_degree, f->num_bases, f->means, f->origin, f->colors_dc,
+                                             f->num_bases > 1 ? f->colors_rest : nullptr, f->sh_mask,
+                                             (f->flags & TS_FRAME_STRIPE) ? f->num_tiles_hit : nullptr, f->channels,
+                                             TS_RASTER_LOGIT_OPACITY, f->xys, f->radii, f->conics, f->opacities,
+                                             f->cum_tiles_hit, &f->cam, f->channels == 4 ? f->depths : nullptr,
+                                             f->splats, tight ? 1 : 0, row_spans(f), stream)));
     // (TS_FRAME_LIST_STATS: the longest list goes to the word behind the count word - read a frame later by the caller's
     // launch policy, never waited for)
     switch (list_form(f)) {
@@ -235,8 +240,8 @@ int ts_frame_fwd_composite(const ts_frame* f, void* stream) {
     case ListForm::one_walk:
         // (emit and offsets also for a frame without intersections: the offsets launch is what empties its lists)
         TS_TRY(TS_ENTRY("ts_bin_scatter",
-                        ts_bin_emit_groups(f->n, f->xys, f->radii, tight, &f->cam, f->cum_tiles_hit, f->capacity,
-                                           f->bin_ws, scratch, stream)));
+                        ts_bin_emit_groups_spans(f->n, f->xys, f->radii, tight, row_spans(f), &f->cam,
+                                                 f->cum_tiles_hit, f->capacity, f->bin_ws, scratch, stream)));
         TS_TRY(TS_ENTRY("ts_tile_offsets",
                         ts_emit_offsets(f->n, num_tiles(f), f->bin_ws, f->tile_bins, f->cum_tiles_hit, f->capacity,
                                         longest_word(f), stream)));

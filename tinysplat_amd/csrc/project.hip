@@ -273,7 +273,11 @@ __global__ __launch_bounds__(kThreads) void sh_bwd_kernel(
 // colors_dc[N,3] / colors_rest[N,K-1,3] (no 192 N-byte torch.cat), then clamp(rgb + 0.5, min=0).
 // mask[n] bit c is set where the clamp passes gradient (pre-clamp value >= 0, torch's rule).
 // ------------------------------------------------------------------------------------------------
-template <int DEG>
+// SPANS: the launch also writes every Gaussian's SPAN RECORD (row_spans.h).  The operands of the record go out in front
+// of the coefficient stream (vector-memory loads return in order), and the record is computed and stored while that
+// stream is in flight: vector work in the shadow of a launch that is bound by HBM.  The same registers feed pack_store
+// behind the barrier.  (A lane beyond the last Gaussian loads the last one's operands and stores nothing.)
+template <int DEG, bool SPANS>
 __global__ __launch_bounds__(kShThreadsFwd) void sh_colors_fwd_kernel(
     int n, int num_bases, const float* __restrict__ means, const float* __restrict__ origin,
     const float* __restrict__ dc, const float* __restrict__ rest, float* __restrict__ colors,
@@ -285,6 +289,17 @@ __global__ __launch_bounds__(kShThreadsFwd) void sh_colors_fwd_kernel(
     const int g0 = blockIdx.x * kShThreadsFwd;
     const int cnt = min(kShThreadsFwd, n - g0);
     const int tid = threadIdx.x;
+    // (the workgroup is kShThreadsFwd threads: with that known, the coefficient loads below are straight-line code and
+    // the wait in front of the span arithmetic counts them exactly)
+    if (SPANS) __builtin_assume(tid < kShThreadsFwd);
+    ts::PackIn in{};
+    if (SPANS) in = ts::pack_load(pk, min(g0 + tid, n - 1));
+    auto write_spans = [&]() {
+        if (!SPANS) return;
+        in.op = ts::pack_opacity(pk, in.op);
+        if (tid < cnt) ts::store_row_spans(pk, g0 + tid, in);
+    };
+    if (RS == 0) write_spans();
     if (RS > 0) {
         const size_t row = 3 * (size_t)(num_bases - 1);
         const float* src = rest + (size_t)g0 * row;
@@ -300,6 +315,7 @@ __global__ __launch_bounds__(kShThreadsFwd) void sh_colors_fwd_kernel(
                 const int f4 = tid + u * kShThreadsFwd;
                 v[u] = f4 < total4 ? load4_stream(src4 + f4) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
+            write_spans();
 #pragma unroll
             for (int u = 0; u < per; ++u) {
                 const int f4 = tid + u * kShThreadsFwd;
@@ -313,6 +329,7 @@ __global__ __launch_bounds__(kShThreadsFwd) void sh_colors_fwd_kernel(
                 }
             }
         } else {
+            write_spans();
             const int total = cnt * RS;
             for (int f = tid; f < total; f += kShThreadsFwd) {
                 const int g = f / RS, j = f % RS;
@@ -338,7 +355,11 @@ __global__ __launch_bounds__(kShThreadsFwd) void sh_colors_fwd_kernel(
     if (mask) mask[i] = (unsigned char)((c0 >= 0.0f ? 1 : 0) | (c1 >= 0.0f ? 2 : 0) | (c2 >= 0.0f ? 4 : 0));
     c0 = fmaxf(c0, 0.0f); c1 = fmaxf(c1, 0.0f); c2 = fmaxf(c2, 0.0f);
     if (colors) { colors[3 * i] = c0; colors[3 * i + 1] = c1; colors[3 * i + 2] = c2; }
-    if (pk.splats) ts::pack_one(pk, i, c0, c1, c2, pk.channels == 4 ? pk.depths[i] : 0.0f);
+    if (pk.splats) {
+        const float c3 = pk.channels == 4 ? pk.depths[i] : 0.0f;
+        if (SPANS) ts::pack_store(pk, i, in, c0, c1, c2, c3);
+        else ts::pack_one(pk, i, c0, c1, c2, c3);
+    }
 }
 
 // The same colour stage for a tile-row STRIPE of a multi-GPU frame: only the Gaussians that are listed in
@@ -354,7 +375,16 @@ __global__ __launch_bounds__(kThreads) void sh_colors_fwd_sparse_kernel(
     float* __restrict__ colors, unsigned char* __restrict__ mask, const ts::PackArgs pk) {
     constexpr int KA = (DEG + 1) * (DEG + 1);
     const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n || live[i] == 0) return;
+    if (i >= n) return;
+    if (live[i] == 0) {                  // not listed in the stripe: the empty span record, nothing else
+        if (pk.row_spans) pk.row_spans[i] = make_int4(0, 0, 0, 0);
+        return;
+    }
+    if (pk.row_spans) {
+        ts::PackIn in = ts::pack_load(pk, i);
+        in.op = ts::pack_opacity(pk, in.op);
+        ts::store_row_spans(pk, i, in);
+    }
     float Y[KA];
     ts::sh_basis(DEG, means[3 * i] - origin[0], means[3 * i + 1] - origin[1],
                  means[3 * i + 2] - origin[2], Y);
@@ -667,11 +697,12 @@ static int launch_colors_fwd(int32_t n, int32_t degrees_to_use, int32_t num_base
     const int grid_d = (n + kShThreadsFwd - 1) / kShThreadsFwd;
 #define TS_SHC_FWD(D)                                                                             \
     do {                                                                                          \
+        const auto kernel = pk.row_spans ? sh_colors_fwd_kernel<D, true> : sh_colors_fwd_kernel<D, false>; \
         if (lds > 48 * 1024)                                                                      \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sh_colors_fwd_kernel<D>),    \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),                      \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
-        hipLaunchKernelGGL(sh_colors_fwd_kernel<D>, dim3(grid_d), dim3(kShThreadsFwd), lds, s, n,  \
-                           num_bases, means3d, origin, colors_dc, colors_rest, colors, clamp_mask, pk); \
+        hipLaunchKernelGGL(kernel, dim3(grid_d), dim3(kShThreadsFwd), lds, s, n, num_bases, means3d, origin, \
+                           colors_dc, colors_rest, colors, clamp_mask, pk);                       \
     } while (0)
     switch (degrees_to_use) {
         case 0: TS_SHC_FWD(0); break;
@@ -700,14 +731,27 @@ int ts_colors_pack_fwd(int32_t n, int32_t degrees_to_use, int32_t num_bases, con
                        const float* xys, const int32_t* radii, const float* conics, const float* opacity,
                        const int32_t* cum_tiles_hit, const ts_camera* cam, const float* depths,
                        float* splats, void* stream) {
+    return ts_colors_pack_spans_fwd(n, degrees_to_use, num_bases, means3d, origin, colors_dc, colors_rest, clamp_mask,
+                                    live, channels, flags, xys, radii, conics, opacity, cum_tiles_hit, cam, depths,
+                                    splats, 0, nullptr, stream);
+}
+
+int ts_colors_pack_spans_fwd(int32_t n, int32_t degrees_to_use, int32_t num_bases, const float* means3d,
+                             const float* origin, const float* colors_dc, const float* colors_rest,
+                             uint8_t* clamp_mask, const int32_t* live, int32_t channels, int32_t flags,
+                             const float* xys, const int32_t* radii, const float* conics, const float* opacity,
+                             const int32_t* cum_tiles_hit, const ts_camera* cam, const float* depths,
+                             float* splats, int32_t tight, int32_t* row_spans, void* stream) {
     if (n < 0 || !cam || (channels != 3 && channels != 4)) return TS_E_BADARG;
     if (n > 0 && (!xys || !radii || !conics || !opacity || !cum_tiles_hit || !splats ||
                   (channels == 4 && !depths)))
         return TS_E_BADARG;
+    if (row_spans && ((uintptr_t)row_spans & 15)) return TS_E_BADARG;         // one aligned 16-byte store per record
     ts::PackArgs pk;
     pk.channels = channels; pk.flags = (int)flags; pk.xys = xys; pk.radii = radii; pk.conics = conics;
     pk.opacity = opacity; pk.cum_tiles_hit = cum_tiles_hit; pk.depths = depths;
     pk.splats = reinterpret_cast<float4*>(splats); pk.cam = *cam;
+    pk.row_spans = reinterpret_cast<int4*>(row_spans); pk.tight = tight ? 1 : 0;
     return launch_colors_fwd(n, degrees_to_use, num_bases, means3d, origin, colors_dc, colors_rest, nullptr,
                              clamp_mask, live, pk, stream);
 }

@@ -306,6 +306,12 @@ GROUP_COUNTS = os.environ.get("TS_GROUP_COUNTS", "1") != "0"
 # TS_ONE_WALK=0: the group form.
 ONE_WALK = os.environ.get("TS_ONE_WALK", "1") != "0"
 
+# ROW SPANS (TS_FRAME_ROW_SPANS, csrc/row_spans.h): in a one-walk frame the colour stage - bound by HBM, its vector pipe
+# idle - leaves every Gaussian's tile columns per row in a 16-byte record, and the emit launch walks those records instead
+# of computing them from the centre, the radius and the packed record.  Same lists, same frame, bit for bit.
+# TS_ROW_SPANS=0: the emit launch computes them itself.
+ROW_SPANS = os.environ.get("TS_ROW_SPANS", "1") != "0"
+
 # CAPACITY ALLOCATION (option, off by default): the per-intersection buffers (bucket_ids | gaussian_ids_sorted;
 # partials in backward) are sized by the bounding-box pair count I, which only the GPU knows (gsplat synchronises
 # for it at the same place, rasterize.py:44).  With TS_CAPACITY_ALLOC=1, from the second frame of a (scene size,
@@ -421,17 +427,18 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
         i32 = dict(dtype=torch.int32, device=dev)
         # ONE allocation for every fixed-size intermediate (a torch.empty costs ~3 us of host time, and a
         # frame used to make a dozen); 256-byte aligned sections:
-        #   splats[12n] f32 | xys[2n] | conics[3n] | (unused) | depths[n] | radii[n] i32 | nth[n] | cum[n] |
+        #   splats[12n] f32 | xys[2n] | conics[3n] | row_spans[4n] i32 (ROW_SPANS) | depths[n] | radii[n] i32 | nth[n] | cum[n] |
         #   scan_ws | bin_ws | tile_bins[2T] | sh_mask[n] u8 | final_Ts[P] f32 | final_index[P] i32 | clamp_mask[P] u8
         px = rows * w
-        lkey = (n, num_tiles, w, rows, ch, keep, cam.hints & 0xFFFF00, cam.wide_tiles, cam.tile_rows, cam.tile_row0, cam.tile_bounds_x, cam.img_height)
+        lkey = (n, num_tiles, w, rows, ch, keep, cam.hints & 0xFFFF00, cam.wide_tiles, cam.tile_rows, cam.tile_row0, cam.tile_bounds_x, cam.img_height,
+                ROW_SPANS)
         lay = _layouts.get(lkey)
         if lay is None:                                  # (the same few shapes come back every frame: ~10 us of host time)
             nscan = int(lib.ts_scan_ws_ints(n))
             nbin = int(lib.ts_bin_ws_ints(n, num_tiles))
             fin_floats = int(lib.ts_final_floats(ctypes.byref(cam), ch)) if keep else px      # T_fin + the cut tiles' checkpoints
             # (the colour stage keeps the colours in registers - ts_colors_pack_fwd - so no colors[n,3] section exists)
-            sizes = [48 * m, 8 * m, 12 * m, 0, 4 * m, 4 * m, 4 * m, 4 * m, 4 * nscan, 4 * nbin,
+            sizes = [48 * m, 8 * m, 12 * m, 16 * m if ROW_SPANS else 0, 4 * m, 4 * m, 4 * m, 4 * m, 4 * nscan, 4 * nbin,
                      8 * max(num_tiles, 1)] + ([m, 4 * fin_floats, 4 * px, px] if keep else [])
             offs, off = [], 0
             for sz in sizes:
@@ -476,6 +483,9 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
             fr.flags |= _lib.FRAME_GROUP_COUNTS                           # (the executor decides where it applies)
         if ONE_WALK:
             fr.flags |= _lib.FRAME_ONE_WALK                               # (the executor decides where it applies)
+        if ROW_SPANS:
+            fr.flags |= _lib.FRAME_ROW_SPANS                              # (one-walk frames only: the executor decides)
+            fr.row_spans = ptr[3]
         if full:
             _stats_mode[dev.index] = mode
         fr.cam = cam
