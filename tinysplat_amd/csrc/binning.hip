@@ -22,6 +22,8 @@
 // ONE WALK form of the same frames (bin_scatter_emit / group_tile_offsets<false> / bin_scatter_fine_runs): the Gaussians are
 // walked once - a chunk stages its pairs in LDS, orders them by group and writes them into its own bounding-box slots of
 // the scratch buffer; the fine hop gathers its group's run from every chunk.
+// Every form lists a Gaussian through ONE piece of code, walk_one (box, TightTest, row_range per tile row, emit_row); the
+// fine hops share place_pass, the two emit kernels the EmitChunk pieces, the offsets launches arm_guard / empty_every_list.
 // Traffic: 4 I written + 4 I read (+ gathers) + 4 I written (+ 8 B T for the count matrix; 8 B G + 4 I read once more in the
 // group form) against the 36 I a 3-pass 64-bit LSD radix sort of key+payload would move at minimum.
 #include <hip/hip_runtime.h>
@@ -184,6 +186,32 @@ inline int bin_window_tiles(int n, int num_tiles) {
 // too, and tests/test_hostmath_cull.py checks every rejection against a float64 per-pixel evaluation.
 using ts::TightTest;
 
+// THE PER-GAUSSIAN WALK, stated once for the walks of this file (walk_chunk, the span walk's fallback, and - its row
+// mapping - the balanced walk): the list forms are held to each other bit for bit, and they are because they decide here.
+// emit_row: 16x16 tiles lo..hi-1 of tile row ty -> emit(list, i) for the list columns: those tiles, or the wide tiles
+// that contain them (ws: list column = 16x16 column >> ws; tbx: list columns per row)
+template <typename Emit>
+__device__ __forceinline__ void emit_row(int ty, int lo, int hi, int i, const ts_camera& cam, int ws, int tbx, Emit emit) {
+    for (int tx = lo >> ws; tx <= (hi - 1) >> ws; ++tx) emit((ty - cam.tile_row0) * tbx + tx, i);
+}
+// walk_one: Gaussian i of radius r > 0 with its loaded operands (q0, q1: the two record words of the tight test, unused
+// for bounding-box lists) -> emit(list, i) for every list it is entered in
+template <typename Emit>
+__device__ __forceinline__ void walk_one(bool tight_lists, int i, int r, float2 xy, float4 q0, float4 q1,
+                                         const ts_camera& cam, int ws, int tbx, Emit emit) {
+    const ts::TileBox b = ts::tile_bbox(xy.x, xy.y, (float)r, cam.tile_bounds_x, cam.tile_bounds_y, cam.tile_row0,
+                                        cam.tile_rows);
+    if (b.maxy <= b.miny || b.maxx <= b.minx) return;            // not in this stripe (its record was never written)
+    const TightTest tight(tight_lists, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, (float)r);
+    if (tight.cull_all) return;
+    for (int ty = b.miny; ty < b.maxy; ++ty) {
+        int lo, hi;
+        tight.row_range(ty, b.minx, b.maxx, lo, hi);
+        if (hi <= lo) continue;
+        emit_row(ty, lo, hi, i, cam, ws, tbx, emit);
+    }
+}
+
 // Walks the Gaussians of a chunk and calls emit(t) for every list (tile of the lists' shape, index t
 // inside the launch) a Gaussian is entered in.  Count and scatter replay the same walk, so they agree.
 // A thread handles kBinThreads-strided Gaussians; the operands of kBinPre of them (radius, centre, the
@@ -226,19 +254,7 @@ __device__ __forceinline__ void walk_chunk(int g0, int g1, const float* __restri
 #pragma unroll
         for (int u = 0; u < kBinPre; ++u) {
             if (r[u] <= 0) continue;
-            const ts::TileBox b = ts::tile_bbox(xy[u].x, xy[u].y, (float)r[u], cam.tile_bounds_x,
-                                                cam.tile_bounds_y, cam.tile_row0, cam.tile_rows);
-            if (b.maxy <= b.miny || b.maxx <= b.minx) continue;  // not in this stripe (its record was never written)
-            const TightTest tight(tight_lists, q0[u].x, q0[u].y, q0[u].z, q0[u].w, q1[u].x, q1[u].y, (float)r[u]);
-            if (tight.cull_all) continue;
-            const int i = base + u * kBinThreads;
-            for (int ty = b.miny; ty < b.maxy; ++ty) {
-                int lo, hi;
-                tight.row_range(ty, b.minx, b.maxx, lo, hi);
-                if (hi <= lo) continue;
-                // list columns: 16x16 tiles lo..hi-1, or the wide tiles that contain them
-                for (int tx = lo >> ws; tx <= (hi - 1) >> ws; ++tx) emit((ty - cam.tile_row0) * tbx + tx, i);
-            }
+            walk_one(tight_lists, base + u * kBinThreads, r[u], xy[u], q0[u], q1[u], cam, ws, tbx, emit);
         }
     }
 }
@@ -249,7 +265,9 @@ __device__ __forceinline__ void walk_chunk(int g0, int g1, const float* __restri
 // a batch of 1024 Gaussians (one per thread) is expanded into ITEMS = (Gaussian, tile row): phase 1 computes the box
 // and the TightTest once per Gaussian and stashes what a row needs in LDS; a workgroup scan of the row counts gives
 // every Gaussian its item range; the items are written out in windows of kItemCap and phase 2 hands consecutive
-// items to consecutive lanes.  Same decisions as walk_chunk (same TightTest members, same row_range), different
+// items to consecutive lanes.  Same decisions as walk_one (phase 1 restates its first four lines around the stash - taken
+// from a shared helper, by callback or by struct, they compile to other instructions in the two balanced kernels,
+// profiles/r27_binning_shared.txt; phase 2 has the stashed TightTest members, the same row_range and emit_row), different
 // ORDER of the emits - which no caller depends on (LDS histogram / cursors; the per-tile sort follows).
 constexpr int kItemCap = 4096;                    // items per window
 constexpr int kStashWords = 11;                   // per Gaussian: 10 TightTest floats + (minx | maxx << 16)
@@ -263,6 +281,7 @@ __device__ __forceinline__ void walk_chunk_balanced(int g0, int g1, const float*
     __shared__ float stash[kStashWords][kBinThreads];
     __shared__ int items[kItemCap];
     __shared__ int wave_sum[kBinThreads / 64 + 1];
+    static_assert(sizeof(stash) + sizeof(items) + sizeof(wave_sum) <= kBalancedLds, "kBalancedLds states this walk's LDS");
     const int ws = cam.wide_tiles ? 1 : 0;
     const int tbx = (cam.tile_bounds_x + ws) >> ws;
     const bool tight_lists = splats != nullptr;
@@ -270,7 +289,7 @@ __device__ __forceinline__ void walk_chunk_balanced(int g0, int g1, const float*
     for (int base = g0; base < g1; base += kBinThreads) {
         // ---- phase 1: one Gaussian per thread
         const int i = base + tid;
-        int rows = 0, miny = 0;
+        int rows = 0;
         if (i < g1) {
             const int r = radii[i];
             if (r > 0) {
@@ -283,7 +302,6 @@ __device__ __forceinline__ void walk_chunk_balanced(int g0, int g1, const float*
                     const TightTest t(tight_lists, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, (float)r);
                     if (!t.cull_all) {
                         rows = b.maxy - b.miny;
-                        miny = b.miny;
                         stash[0][tid] = t.geometric ? t.dymax : -1.0f;          // dymax >= 0 when geometric
                         stash[1][tid] = t.gx; stash[2][tid] = t.gy; stash[3][tid] = t.B; stash[4][tid] = t.D4;
                         stash[5][tid] = t.inv2A; stash[6][tid] = t.tau4A; stash[7][tid] = t.dxext;
@@ -333,8 +351,7 @@ __device__ __forceinline__ void walk_chunk_balanced(int g0, int g1, const float*
                 int lo, hi;
                 t.row_range(ty, xx & 0xffff, xx >> 16, lo, hi);
                 if (hi <= lo) continue;
-                const int id = base + lt;
-                for (int tx = lo >> ws; tx <= (hi - 1) >> ws; ++tx) emit((ty - cam.tile_row0) * tbx + tx, id);
+                emit_row(ty, lo, hi, base + lt, cam, ws, tbx, emit);
             }
             __syncthreads();
         }
@@ -420,6 +437,23 @@ constexpr int kOffsetsThreads = 1024;
 // (spare[-1]) is set, every list is left empty (tile_bins = 0, tile_start = 0), ts_bin_scatter returns at once, and
 // the compositing kernels find nothing to do; the host sees the same total when it reads the count and runs the
 // frame again with exact sizes.
+// One thread of an offsets launch (tile_offsets_kernel, group_tile_offsets_kernel) arms the guard: over (the workgroup's
+// LDS word) = whether it tripped.  refuse_negative: a negative total trips it whatever the capacity
+__device__ __forceinline__ void arm_guard(int& over, int* __restrict__ spare, const int* __restrict__ total_ptr,
+                                          long long capacity, bool refuse_negative) {
+    *spare = 0;                                           // the workspace's last word: ts_sort_tiles' tile counter
+    over = (total_ptr && capacity >= 0 && ((long long)*total_ptr > capacity || *total_ptr < 0)) ? 1 : 0;
+    if (refuse_negative && total_ptr && *total_ptr < 0) over = 1;
+    spare[-1] = over;
+}
+// ... and where it tripped (or nothing is listed) the whole workgroup leaves every list empty
+template <int THREADS>
+__device__ __forceinline__ void empty_every_list(int num_tiles, int* __restrict__ tile_start, int* __restrict__ tile_bins) {
+    for (int t = threadIdx.x; t <= num_tiles; t += THREADS) {
+        tile_start[t] = 0;
+        if (t < num_tiles) reinterpret_cast<int2*>(tile_bins)[t] = make_int2(0, 0);
+    }
+}
 __global__ __launch_bounds__(kOffsetsThreads) void tile_offsets_kernel(int num_tiles,
                                                                        int* __restrict__ tile_total,
                                                                        int* __restrict__ tile_bins,
@@ -432,16 +466,11 @@ __global__ __launch_bounds__(kOffsetsThreads) void tile_offsets_kernel(int num_t
     if (threadIdx.x == 0) {
         carry = 0;
         longest = 0;
-        *spare = 0;                                       // the workspace's last word: ts_sort_tiles' tile counter
-        over = (total_ptr && capacity >= 0 && ((long long)*total_ptr > capacity || *total_ptr < 0)) ? 1 : 0;
-        spare[-1] = over;
+        arm_guard(over, spare, total_ptr, capacity, /*refuse_negative=*/false);
     }
     __syncthreads();
     if (over) {
-        for (int t = threadIdx.x; t <= num_tiles; t += kOffsetsThreads) {
-            tile_total[t] = 0;
-            if (t < num_tiles) reinterpret_cast<int2*>(tile_bins)[t] = make_int2(0, 0);
-        }
+        empty_every_list<kOffsetsThreads>(num_tiles, tile_total, tile_bins);
         return;
     }
     for (int base = 0; base < num_tiles; base += kOffsetsThreads * kPer) {
@@ -511,6 +540,10 @@ __global__ __launch_bounds__(kBinThreads) void bin_scatter_kernel(
 //   group     group_bin_count -> group_tile_offsets -> coarse<.., true> + fine_groups: B x G counts, two walks
 //   one walk  emit -> group_tile_offsets<false> -> fine_runs: B x G counts and run starts, ONE walk; the coarse hop's
 //             scattered 4-byte stores into ~G open runs become a linear copy of the chunk's region out of LDS
+// Shared by the forms: the per-Gaussian walk (walk_one, through walk_chunk or the span walk's fallback; the balanced walk
+// takes its row mapping), the guard and the emptying of every list in the offsets launches (arm_guard, empty_every_list),
+// the fine hop (place_pass), and in the two emit kernels everything but what is staged and how it is placed (EmitChunk:
+// emit_chunk_begin, stage_slot, emit_chunk_rows, emit_copy_out).
 #ifndef TS_COARSE_SHIFT
 #define TS_COARSE_SHIFT 5
 #endif
@@ -575,10 +608,7 @@ __global__ __launch_bounds__(kGoThreads) void group_tile_offsets_kernel(
     const int tid = threadIdx.x;
     if (tid == 0) {
         carry = 0;
-        *spare = 0;                                       // the workspace's last word: ts_sort_tiles' tile counter
-        over = (total_ptr && capacity >= 0 && ((long long)*total_ptr > capacity || *total_ptr < 0)) ? 1 : 0;
-        if (!BASES && total_ptr && *total_ptr < 0) over = 1;
-        spare[-1] = over;
+        arm_guard(over, spare, total_ptr, capacity, /*refuse_negative=*/!BASES);
     }
     __syncthreads();
     if (!over) {
@@ -663,10 +693,7 @@ __global__ __launch_bounds__(kGoThreads) void group_tile_offsets_kernel(
         if (carry != 0) return;
         if (tid == 0 && longest_out) *longest_out = 0;       // nothing listed: no later launch may come to say so
     }
-    for (int t = tid; t <= num_tiles; t += kGoThreads) {     // overflow, or nothing listed: every list empty
-        tile_start[t] = 0;
-        if (t < num_tiles) reinterpret_cast<int2*>(tile_bins)[t] = make_int2(0, 0);
-    }
+    empty_every_list<kGoThreads>(num_tiles, tile_start, tile_bins);     // overflow, or nothing listed
 }
 
 template <bool BAL, bool GROUPS = false>
@@ -918,7 +945,9 @@ __global__ __launch_bounds__(kFineThreads) void bin_scatter_fine_groups_kernel(i
 #endif
 constexpr int kStageCap = TS_STAGE_CAP;                  // staged pairs per chunk: 6 bytes each (word + group index)
 constexpr int kEmitMaxGroups = 2048;                     // histogram + cursors: 8 bytes per group; 136 KiB in all
-static_assert((size_t)kStageCap * 6 + (size_t)kEmitMaxGroups * 8 <= 144 * 1024, "LDS budget of a binning workgroup");
+// dynamic LDS of an emit workgroup, as EmitChunk carves it: hist[groups], cursor[groups], words[kStageCap], grp[kStageCap]
+constexpr size_t emit_lds_bytes(int groups) { return (size_t)groups * 8 + (size_t)kStageCap * 6; }
+static_assert(emit_lds_bytes(kEmitMaxGroups) <= 144 * 1024, "LDS budget of a binning workgroup");
 static_assert(kEmitMaxGroups <= 2 * kBinThreads && kEmitMaxGroups <= 65536, "two groups per thread, 16-bit group index");
 static_assert(kEmitMaxGroups <= kGoLdsGroups, "the offsets launch keeps the column totals in LDS");
 
@@ -987,17 +1016,7 @@ __device__ __forceinline__ void walk_gaussian(int i, const float* __restrict__ x
     const float2 xy = reinterpret_cast<const float2*>(xys)[i];
     float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
     if (splats) { q0 = splats[3 * (size_t)i]; q1 = splats[3 * (size_t)i + 1]; }
-    const ts::TileBox b = ts::tile_bbox(xy.x, xy.y, (float)r, cam.tile_bounds_x, cam.tile_bounds_y, cam.tile_row0,
-                                        cam.tile_rows);
-    if (b.maxy <= b.miny || b.maxx <= b.minx) return;
-    const TightTest tight(splats != nullptr, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, (float)r);
-    if (tight.cull_all) return;
-    for (int ty = b.miny; ty < b.maxy; ++ty) {
-        int lo, hi;
-        tight.row_range(ty, b.minx, b.maxx, lo, hi);
-        if (hi <= lo) continue;
-        for (int tx = lo >> ws; tx <= (hi - 1) >> ws; ++tx) emit((ty - cam.tile_row0) * tbx + tx, i);
-    }
+    walk_one(splats != nullptr, i, r, xy, q0, q1, cam, ws, tbx, emit);
 }
 // emit(t, len, i): the Gaussian enters the len <= 32 consecutive lists from t on, all of one group of kCoarseTiles lists -
 // a row of a record is a run of consecutive lists already, cut here where it crosses into the next group.
@@ -1042,105 +1061,142 @@ __device__ __forceinline__ void walk_spans(int g0, int g1, const int4* __restric
     }
 }
 
+// THE CHUNK EPILOGUE (and prologue) of the two emit kernels below, which differ in what they walk, in what a staged item
+// is (a pair, a run) and therefore in how staged items are placed, and in nothing else.
+struct EmitChunk {
+    int g0, g1;                                          // the chunk's Gaussians
+    int chunk_base, room;                                // its bounding-box slots in the scratch buffer: first, how many
+    int* hist;                                           // [groups] what the chunk lists per group
+    int* cursor;                                         // [groups] next free word of a group's run, from chunk_base
+    unsigned int* words;                                 // [kStageCap] the staged words; then the region ordered by group
+    unsigned short* grp;                                 // [kStageCap] a staged word's group (+ the kernel's own bits)
+};
+constexpr int kStagePer = kStageCap / kBinThreads;       // staged words per thread
+static_assert(kStageCap % kBinThreads == 0, "whole staging rounds");
+
+// Chunk bounds, the LDS carve-up (emit_lds_bytes), histogram and append counter cleared.  False: the frame trips the
+// capacity guard and the launch places nothing
+__device__ __forceinline__ bool emit_chunk_begin(EmitChunk& c, int* lds, int* staged, int n, int chunk, int groups,
+                                                 const int* __restrict__ cum, long long capacity) {
+    // capacity guard, read here because the offsets launch runs behind this one; a wrapped total places nothing either.
+    // (The three words of cum_tiles_hit are in flight together, while the histogram is cleared)
+    c.g0 = min(n, (int)blockIdx.x * chunk);
+    c.g1 = min(n, c.g0 + chunk);
+    const int total = cum[n - 1];
+    c.chunk_base = c.g0 > 0 ? cum[c.g0 - 1] : 0;
+    const int chunk_end = c.g1 > c.g0 ? cum[c.g1 - 1] : c.chunk_base;
+    c.hist = lds;
+    c.cursor = lds + groups;
+    c.words = reinterpret_cast<unsigned int*>(lds + 2 * groups);
+    c.grp = reinterpret_cast<unsigned short*>(c.words + kStageCap);
+    for (int j = threadIdx.x; j < groups; j += kBinThreads) c.hist[j] = 0;
+    if (threadIdx.x == 0) *staged = 0;
+    __syncthreads();
+    c.room = chunk_end - c.chunk_base;
+    return total < 0 || (capacity >= 0 && (long long)total > capacity);
+}
+
+// The append of one staged item: one LDS atomic per wave and emit step, the active lanes take consecutive slots (a slot
+// from kStageCap on is not stored: the chunk will walk a second time)
+__device__ __forceinline__ int stage_slot(int* staged) {
+    const unsigned long long m = __ballot(1);                         // the lanes that emit in this step
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32),
+                                                    __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
+    int base = 0;
+    if (rank == 0) base = atomicAdd(staged, (int)__popcll(m));
+    base = __builtin_amdgcn_readfirstlane(base);                      // (the first active lane is the one of rank 0)
+    return base + rank;
+}
+
+// Behind the walk: exclusive scan of the histogram, two groups per thread -> the cursors and the chunk's two rows.
+// Returns everything the chunk lists (the histogram's total).  sound: a chunk cannot list more than its bounding-box
+// slots; were it ever to, it lists nothing (zero counts) rather than write beyond its region
+__device__ __forceinline__ int emit_chunk_rows(const EmitChunk& c, int groups, int* __restrict__ counts,
+                                               int* __restrict__ starts, bool& sound) {
+    __syncthreads();
+    const int a = 2 * threadIdx.x;
+    const int h0 = a < groups ? c.hist[a] : 0, h1 = a + 1 < groups ? c.hist[a + 1] : 0;
+    int pairs;
+    const int ex = block_inclusive_scan<kBinThreads / 64>(h0 + h1, &pairs) - h0 - h1;
+    sound = pairs <= c.room;
+    int* crow = counts + (size_t)blockIdx.x * groups;
+    int* srow = starts + (size_t)blockIdx.x * groups;
+    if (a < groups) {
+        c.cursor[a] = ex;
+        crow[a] = sound ? h0 : 0;
+        srow[a] = c.chunk_base + ex;
+    }
+    if (a + 1 < groups) {
+        c.cursor[a + 1] = ex + h0;
+        crow[a + 1] = sound ? h1 : 0;
+        srow[a + 1] = c.chunk_base + ex + h0;
+    }
+    __syncthreads();
+    return pairs;
+}
+
+// The chunk's region, ordered by group in c.words, goes out: consecutive lanes store consecutive words
+__device__ __forceinline__ void emit_copy_out(const EmitChunk& c, int pairs, int* __restrict__ dst) {
+#pragma unroll
+    for (int u = 0; u < kStagePer; ++u) {
+        const int j = u * kBinThreads + (int)threadIdx.x;
+        if (j < pairs) dst[j] = (int)c.words[j];
+    }
+}
+
 __global__ __launch_bounds__(kBinThreads) void bin_scatter_emit_kernel(
     int n, int chunk, const float* __restrict__ xys, const int* __restrict__ radii,
     const float4* __restrict__ splats, const ts_camera cam, int groups, const int* __restrict__ cum,
     long long capacity, int* __restrict__ counts, int* __restrict__ starts, int* __restrict__ scratch) {
     extern __shared__ int lds[];
     __shared__ int staged;
-    // capacity guard, read here because the offsets launch runs behind this one; a wrapped total places nothing either.
-    // (The three words of cum_tiles_hit are in flight together, while the histogram is cleared)
-    const int g0 = min(n, (int)blockIdx.x * chunk), g1 = min(n, g0 + chunk);
-    const int total = cum[n - 1];
-    const int chunk_base = g0 > 0 ? cum[g0 - 1] : 0;
-    const int chunk_end = g1 > g0 ? cum[g1 - 1] : chunk_base;
-    int* hist = lds;
-    int* cursor = lds + groups;
-    unsigned int* words = reinterpret_cast<unsigned int*>(lds + 2 * groups);
-    unsigned short* grp = reinterpret_cast<unsigned short*>(words + kStageCap);
-    const int tid = threadIdx.x;
-    for (int j = tid; j < groups; j += kBinThreads) hist[j] = 0;
-    if (tid == 0) staged = 0;
-    __syncthreads();
-    if (total < 0 || (capacity >= 0 && (long long)total > capacity)) return;
-    const int room = chunk_end - chunk_base;                         // the chunk's bounding-box slots
-    walk_chunk(g0, g1, xys, radii, splats, cam, [&](int t, int i) {
+    EmitChunk c;
+    if (emit_chunk_begin(c, lds, &staged, n, chunk, groups, cum, capacity)) return;      // over capacity
+    walk_chunk(c.g0, c.g1, xys, radii, splats, cam, [&](int t, int i) {
         const int g = t >> kCoarseShift;
-        atomicAdd(&hist[g], 1);
-        const unsigned long long m = __ballot(1);                     // the lanes that emit in this step
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32),
-                                                        __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
-        int base = 0;
-        if (rank == 0) base = atomicAdd(&staged, (int)__popcll(m));
-        base = __builtin_amdgcn_readfirstlane(base);                  // (the first active lane is the one of rank 0)
-        const int slot = base + rank;
+        atomicAdd(&c.hist[g], 1);
+        const int slot = stage_slot(&staged);
         if (slot < kStageCap) {
-            words[slot] = (unsigned int)i | ((unsigned int)(t & (kCoarseTiles - 1)) << kCoarseIdBits);
-            grp[slot] = (unsigned short)g;
+            c.words[slot] = (unsigned int)i | ((unsigned int)(t & (kCoarseTiles - 1)) << kCoarseIdBits);
+            c.grp[slot] = (unsigned short)g;
         }
     });
-    __syncthreads();
-    const int pairs = staged;                                         // everything the chunk lists
-    // a chunk cannot list more than its bounding-box slots; were it ever to, it lists nothing rather than write
-    // beyond its region
-    const bool sound = pairs <= room;
-    {   // exclusive scan of the histogram: two groups per thread; the chunk's two rows
-        const int a = 2 * tid;
-        const int h0 = a < groups ? hist[a] : 0, h1 = a + 1 < groups ? hist[a + 1] : 0;
-        int all;
-        const int ex = block_inclusive_scan<kBinThreads / 64>(h0 + h1, &all) - h0 - h1;
-        int* crow = counts + (size_t)blockIdx.x * groups;
-        int* srow = starts + (size_t)blockIdx.x * groups;
-        if (a < groups) {
-            cursor[a] = ex;
-            crow[a] = sound ? h0 : 0;
-            srow[a] = chunk_base + ex;
-        }
-        if (a + 1 < groups) {
-            cursor[a + 1] = ex + h0;
-            crow[a + 1] = sound ? h1 : 0;
-            srow[a + 1] = chunk_base + ex + h0;
-        }
-    }
-    __syncthreads();
+    bool sound;
+    const int pairs = emit_chunk_rows(c, groups, counts, starts, sound);      // (= staged: one pair per append)
     if (!sound) return;
-    int* dst = scratch + chunk_base;
+    int* dst = scratch + c.chunk_base;
     if (pairs <= kStageCap) {
         // ordered by group inside LDS first (every thread keeps its entries and their places in registers while the
         // buffer changes hands), then copied out: consecutive lanes store consecutive words of the chunk's region.
         // Straight from the staging order a wave's store touched up to 64 lines, 16 k such words in one burst
-        constexpr int kPer = kStageCap / kBinThreads;
-        static_assert(kStageCap % kBinThreads == 0, "whole staging rounds");
-        unsigned int w[kPer];
-        int at[kPer];
+        const int tid = threadIdx.x;
+        unsigned int w[kStagePer];
+        int at[kStagePer];
 #pragma unroll
-        for (int u = 0; u < kPer; ++u) {
+        for (int u = 0; u < kStagePer; ++u) {
             const int j = u * kBinThreads + tid;
             if (j < pairs) {
-                w[u] = words[j];
-                at[u] = atomicAdd(&cursor[grp[j]], 1);
+                w[u] = c.words[j];
+                at[u] = atomicAdd(&c.cursor[c.grp[j]], 1);
             }
         }
         __syncthreads();
 #pragma unroll
-        for (int u = 0; u < kPer; ++u)
-            if (u * kBinThreads + tid < pairs) words[at[u]] = w[u];
+        for (int u = 0; u < kStagePer; ++u)
+            if (u * kBinThreads + tid < pairs) c.words[at[u]] = w[u];
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            const int j = u * kBinThreads + tid;
-            if (j < pairs) dst[j] = (int)words[j];
-        }
+        emit_copy_out(c, pairs, dst);
     } else {
-        walk_chunk(g0, g1, xys, radii, splats, cam, [&](int t, int i) {
-            dst[atomicAdd(&cursor[t >> kCoarseShift], 1)] = i | ((t & (kCoarseTiles - 1)) << kCoarseIdBits);
+        walk_chunk(c.g0, c.g1, xys, radii, splats, cam, [&](int t, int i) {
+            dst[atomicAdd(&c.cursor[t >> kCoarseShift], 1)] = i | ((t & (kCoarseTiles - 1)) << kCoarseIdBits);
         });
     }
 }
 
 // The emit launch over SPAN RECORDS: bin_scatter_emit_kernel with walk_spans in both of its walks and ONE STAGED ITEM PER
 // RUN.  (A kernel of its own beside the one above, not a template of it: run staging in the shared body cost the
-// launch without records 2.4 us, profiles/r26_row_spans.txt, and that launch is to stay what it was.)
+// launch without records 2.4 us, profiles/r26_row_spans.txt.  That covers what is staged and how it is placed, and those
+// are what the two kernels spell out; the rest is the EmitChunk pieces, profiles/r27_binning_shared.txt.)
 __global__ __launch_bounds__(kBinThreads) void bin_scatter_spans_kernel(
     int n, int chunk, const float* __restrict__ xys, const int* __restrict__ radii,
     const float4* __restrict__ splats, const int4* __restrict__ spans, const ts_camera cam, int groups,
@@ -1148,103 +1204,54 @@ __global__ __launch_bounds__(kBinThreads) void bin_scatter_spans_kernel(
     int* __restrict__ scratch) {
     extern __shared__ int lds[];
     __shared__ int staged;
-    // capacity guard, read here because the offsets launch runs behind this one; a wrapped total places nothing either.
-    // (The three words of cum_tiles_hit are in flight together, while the histogram is cleared)
-    const int g0 = min(n, (int)blockIdx.x * chunk), g1 = min(n, g0 + chunk);
-    const int total = cum[n - 1];
-    const int chunk_base = g0 > 0 ? cum[g0 - 1] : 0;
-    const int chunk_end = g1 > g0 ? cum[g1 - 1] : chunk_base;
-    int* hist = lds;
-    int* cursor = lds + groups;
-    unsigned int* words = reinterpret_cast<unsigned int*>(lds + 2 * groups);
-    unsigned short* grp = reinterpret_cast<unsigned short*>(words + kStageCap);
-    const int tid = threadIdx.x;
-    for (int j = tid; j < groups; j += kBinThreads) hist[j] = 0;
-    if (tid == 0) staged = 0;
-    __syncthreads();
-    if (total < 0 || (capacity >= 0 && (long long)total > capacity)) return;
-    const int room = chunk_end - chunk_base;                         // the chunk's bounding-box slots
-    auto walk = [&](auto emit) { walk_spans(g0, g1, spans, xys, radii, splats, cam, emit); };     // emit(t, len, i)
+    EmitChunk c;
+    if (emit_chunk_begin(c, lds, &staged, n, chunk, groups, cum, capacity)) return;      // over capacity
+    auto walk = [&](auto emit) { walk_spans(c.g0, c.g1, spans, xys, radii, splats, cam, emit); };     // emit(t, len, i)
     // ONE STAGED ITEM PER RUN: the word carries the id and the first tile-in-group, the 5 spare bits of the 16-bit group
     // index carry len - 1; the histogram takes the whole run in one atomic, the append happens once per run
     static_assert(kEmitMaxGroups <= (1 << 11) && kCoarseTiles <= 32, "group index in 11 bits, len - 1 in 5");
     walk([&](int t, int len, int i) {
         const int g = t >> kCoarseShift;
-        atomicAdd(&hist[g], len);
-        const unsigned long long m = __ballot(1);                     // the lanes that emit in this step
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32),
-                                                        __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
-        int base = 0;
-        if (rank == 0) base = atomicAdd(&staged, (int)__popcll(m));
-        base = __builtin_amdgcn_readfirstlane(base);                  // (the first active lane is the one of rank 0)
-        const int slot = base + rank;
+        atomicAdd(&c.hist[g], len);
+        const int slot = stage_slot(&staged);
         if (slot < kStageCap) {
-            words[slot] = (unsigned int)i | ((unsigned int)(t & (kCoarseTiles - 1)) << kCoarseIdBits);
-            grp[slot] = (unsigned short)(g | ((len - 1) << 11));
+            c.words[slot] = (unsigned int)i | ((unsigned int)(t & (kCoarseTiles - 1)) << kCoarseIdBits);
+            c.grp[slot] = (unsigned short)(g | ((len - 1) << 11));
         }
     });
-    __syncthreads();
-    const int items = staged;                                         // runs the chunk lists
-    int pairs;                                                        // everything it lists: the histogram's total
     bool sound;
-    {   // exclusive scan of the histogram: two groups per thread; the chunk's two rows
-        const int a = 2 * tid;
-        const int h0 = a < groups ? hist[a] : 0, h1 = a + 1 < groups ? hist[a + 1] : 0;
-        const int ex = block_inclusive_scan<kBinThreads / 64>(h0 + h1, &pairs) - h0 - h1;
-        // a chunk cannot list more than its bounding-box slots; were it ever to, it lists nothing rather than write
-        // beyond its region
-        sound = pairs <= room;
-        int* crow = counts + (size_t)blockIdx.x * groups;
-        int* srow = starts + (size_t)blockIdx.x * groups;
-        if (a < groups) {
-            cursor[a] = ex;
-            crow[a] = sound ? h0 : 0;
-            srow[a] = chunk_base + ex;
-        }
-        if (a + 1 < groups) {
-            cursor[a + 1] = ex + h0;
-            crow[a + 1] = sound ? h1 : 0;
-            srow[a + 1] = chunk_base + ex + h0;
-        }
-    }
-    __syncthreads();
+    const int pairs = emit_chunk_rows(c, groups, counts, starts, sound);
+    const int items = staged;                                         // runs the chunk lists
     if (!sound) return;
-    int* dst = scratch + chunk_base;
+    int* dst = scratch + c.chunk_base;
     if (items <= kStageCap && pairs <= kStageCap) {
-        // ordered by group inside LDS first (every thread keeps its entries and their places in registers while the
-        // buffer changes hands), then copied out: consecutive lanes store consecutive words of the chunk's region.
-        // Straight from the staging order a wave's store touched up to 64 lines, 16 k such words in one burst
-        constexpr int kPer = kStageCap / kBinThreads;
-        static_assert(kStageCap % kBinThreads == 0, "whole staging rounds");
-        unsigned int w[kPer];
-        int at[kPer];                                                 // place of the run's first word | (len - 1) << 16
+        // bin_scatter_emit_kernel's placement, a run at a time
+        const int tid = threadIdx.x;
+        unsigned int w[kStagePer];
+        int at[kStagePer];                                            // place of the run's first word | (len - 1) << 16
         static_assert(kStageCap <= 65536, "a place in 16 bits");
 #pragma unroll
-        for (int u = 0; u < kPer; ++u) {
+        for (int u = 0; u < kStagePer; ++u) {
             const int j = u * kBinThreads + tid;
             if (j < items) {
-                w[u] = words[j];
-                const int gl = grp[j], len1 = gl >> 11;
-                at[u] = atomicAdd(&cursor[gl & 2047], len1 + 1) | (len1 << 16);
+                w[u] = c.words[j];
+                const int gl = c.grp[j], len1 = gl >> 11;
+                at[u] = atomicAdd(&c.cursor[gl & 2047], len1 + 1) | (len1 << 16);
             }
         }
         __syncthreads();
 #pragma unroll
-        for (int u = 0; u < kPer; ++u)
+        for (int u = 0; u < kStagePer; ++u)
             if (u * kBinThreads + tid < items) {
                 // the run expanded into its words: tile-in-group first, first + 1, ... (<= 31: a run ends with its group)
                 const int first = at[u] & 0xffff, len1 = at[u] >> 16;
-                for (int q = 0; q <= len1; ++q) words[first + q] = w[u] + ((unsigned int)q << kCoarseIdBits);
+                for (int q = 0; q <= len1; ++q) c.words[first + q] = w[u] + ((unsigned int)q << kCoarseIdBits);
             }
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            const int j = u * kBinThreads + tid;
-            if (j < pairs) dst[j] = (int)words[j];
-        }
+        emit_copy_out(c, pairs, dst);
     } else {
         walk([&](int t, int len, int i) {
-            const int at = atomicAdd(&cursor[t >> kCoarseShift], len);
+            const int at = atomicAdd(&c.cursor[t >> kCoarseShift], len);
             for (int q = 0; q < len; ++q) dst[at + q] = i | (((t + q) & (kCoarseTiles - 1)) << kCoarseIdBits);
         });
     }
@@ -1643,6 +1650,16 @@ __global__ __launch_bounds__(kThreads) void pack_splats_kernel(int n, const ts::
     ts::pack_one(a, i, c0, c1, c2, c3);
 }
 
+// A launch with `lds` bytes of dynamic LDS: beyond 64 KiB the kernel has to be told so first (the emit launches and the
+// one-walk fine hop are beyond it at the default kStageCap and kRunItems; the window launches on large frames)
+template <typename... Params, typename... Args>
+void launch_with_lds(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1683,13 +1700,9 @@ int ts_bin_count(int32_t n, const float* xys, const int32_t* radii, const float*
     const BinGeometry g = bin_geometry(n, nt);
     const int window = bin_window_tiles(n, nt);
     const int windows = (nt + window - 1) / window;
-    const size_t lds = (size_t)window * sizeof(int);
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_count_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(bin_count_kernel, dim3(g.chunks, windows), dim3(kBinThreads), lds,
-                       (hipStream_t)stream, n, g.chunk, xys, radii,
-                       reinterpret_cast<const float4*>(splats), *cam, nt, window, bin_ws);
+    launch_with_lds(bin_count_kernel, dim3(g.chunks, windows), dim3(kBinThreads), (size_t)window * sizeof(int),
+                    (hipStream_t)stream, n, g.chunk, xys, radii, reinterpret_cast<const float4*>(splats), *cam, nt,
+                    window, bin_ws);
     return launch_status();
 }
 
@@ -1807,21 +1820,14 @@ int ts_bin_emit_groups_spans(int32_t n, const float* xys, const int32_t* radii, 
     const int nt = ts_num_tiles(cam);
     if (!one_walk_form(n, nt) || (cam->hints & TS_HINT_BALANCED_WALK)) return TS_E_BADARG;
     const BinGeometry g = bin_geometry(n, nt);
-    const size_t lds = (size_t)g.groups * 8 + (size_t)kStageCap * 6;
-    if (row_spans) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_spans_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(bin_scatter_spans_kernel, dim3(g.chunks), dim3(kBinThreads), lds, (hipStream_t)stream, n,
-                           g.chunk, xys, radii, reinterpret_cast<const float4*>(splats),
-                           reinterpret_cast<const int4*>(row_spans), *cam, g.groups, cum_tiles_hit, (long long)capacity,
-                           bin_ws + g.counts, bin_ws + g.starts, scratch);
-        return launch_status();
-    }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_emit_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(bin_scatter_emit_kernel, dim3(g.chunks), dim3(kBinThreads), lds, (hipStream_t)stream, n, g.chunk,
-                       xys, radii, reinterpret_cast<const float4*>(splats), *cam, g.groups, cum_tiles_hit,
-                       (long long)capacity, bin_ws + g.counts, bin_ws + g.starts, scratch);
+    // one launch, with or without records: the two kernels take the same arguments behind (kernel, records)
+    auto emit = [&](auto kernel, auto... records) {
+        launch_with_lds(kernel, dim3(g.chunks), dim3(kBinThreads), emit_lds_bytes(g.groups), (hipStream_t)stream, n,
+                        g.chunk, xys, radii, reinterpret_cast<const float4*>(splats), records..., *cam, g.groups,
+                        cum_tiles_hit, (long long)capacity, bin_ws + g.counts, bin_ws + g.starts, scratch);
+    };
+    if (row_spans) emit(bin_scatter_spans_kernel, reinterpret_cast<const int4*>(row_spans));
+    else emit(bin_scatter_emit_kernel);
     return launch_status();
 }
 
@@ -1836,12 +1842,10 @@ int ts_bin_gather_groups(int32_t n, int32_t num_tiles, int32_t* bin_ws, int32_t*
                          const int32_t* scratch, void* stream) {
     if (!one_walk_form(n, num_tiles) || !bin_ws || !tile_bins || !bucket_ids || !scratch) return TS_E_BADARG;
     const BinGeometry g = bin_geometry(n, num_tiles);
-    const size_t lds = (size_t)kRunPass * sizeof(int);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_fine_runs_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(bin_scatter_fine_runs_kernel, dim3(g.groups), dim3(kFineThreads), lds, (hipStream_t)stream,
-                       num_tiles, g.groups, g.chunks, (const int*)(bin_ws + g.counts), (const int*)(bin_ws + g.starts),
-                       bin_ws + g.tile_start, tile_bins, bin_ws + g.group_max, scratch, bucket_ids);
+    launch_with_lds(bin_scatter_fine_runs_kernel, dim3(g.groups), dim3(kFineThreads), (size_t)kRunPass * sizeof(int),
+                    (hipStream_t)stream, num_tiles, g.groups, g.chunks, (const int*)(bin_ws + g.counts),
+                    (const int*)(bin_ws + g.starts), bin_ws + g.tile_start, tile_bins, bin_ws + g.group_max, scratch,
+                    bucket_ids);
     return launch_status();
 }
 
@@ -1872,12 +1876,9 @@ int ts_bin_scatter(int32_t n, const float* xys, const int32_t* radii, const floa
     }
     const int window = bin_window_tiles(n, nt);
     const int windows = (nt + window - 1) / window;
-    const size_t lds = (size_t)window * sizeof(int);
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_scatter_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(bin_scatter_kernel, dim3(g.chunks, windows), dim3(kBinThreads), lds, s, n, g.chunk, xys, radii,
-                       reinterpret_cast<const float4*>(splats), *cam, nt, window, bin_ws, tile_start, bucket_ids);
+    launch_with_lds(bin_scatter_kernel, dim3(g.chunks, windows), dim3(kBinThreads), (size_t)window * sizeof(int), s, n,
+                    g.chunk, xys, radii, reinterpret_cast<const float4*>(splats), *cam, nt, window, bin_ws, tile_start,
+                    bucket_ids);
     return launch_status();
 }
 
