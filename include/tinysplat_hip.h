@@ -1207,6 +1207,56 @@ int ts_label_votes(int32_t flags, const ts_camera* cam_host, const int32_t* tile
 int ts_votes_labels(int32_t n, int32_t num_classes, const int64_t* votes, double min_share, uint8_t* labels_out,
                     float* confidence_out, void* stream);
 
+/* Budgeted (MCMC) densification: relocation of dead Gaussians, growth to a cap, position noise and the two mean
+ * regularisers (csrc/mcmc_math.h).  Additive entries: the ABI version is unchanged.  None allocates
+ * or synchronises; every result is the same bits on every run.  All return TS_E_BADARG, before any launch, for a count
+ * below 1 or a NULL pointer that is not said to be optional.
+ * ts_mcmc_noise: means float32 [n,3] += scale * g(1 - o) * (Sigma z) with o = sigmoid(opacities), g(x) = 1 / (1 + exp(-100
+ * (x - 0.995))) and Sigma = R diag(exp(2 scales)) R^T of the normalised quats (w, x, y, z), all float32; a row whose g is
+ * 0 (the exponent overflowed) or NaN keeps its bits.  z: float32 [n,3] unit normals, or NULL: row i then draws its own
+ * from Philox4x32-10 with key = seed and counter (i, step, 0, 0), the words mapped to u = ((x >> 8) + 0.5) 2^-24 and
+ * Box-Muller applied to (u0, u1) and (u2, u3), of which the first three normals are used.  quats must be 16-byte aligned.
+ * ts_mcmc_normals: out float32 [n,3] <- exactly the normals ts_mcmc_noise draws for (seed, step).
+ * ts_mcmc_mean: value (device float) <- mean f(x) over count float32 elements, and grad float32 [count] (may be NULL) <-
+ * f'(x) / count; kind TS_MCMC_MEAN_SIGMOID: f = sigmoid, TS_MCMC_MEAN_EXP: f = exp.  The sum is taken in double in a fixed
+ * order.  ws: >= ts_mcmc_mean_ws_bytes(count) bytes, 8-byte aligned.
+ * ts_mcmc_weights: weights double [n] <- o_i, the float32 nearest to sigmoid(opacities_i) (evaluated in double), or 0
+ * where o_i is 0 or NaN and, with zero_dead != 0, where row i is dead (not o_i > min_opacity).  flags uint8 [n] (may be
+ * NULL) <- 0 for a dead row and TS_DENSIFY_PRUNE for a live one: ts_densify_plan then lists the dead rows in ascending
+ * order as its kept rows, with their number in counts[0].  TS_E_BADARG also for a negative or NaN min_opacity.
+ * ts_mcmc_sample_rows: m draws over n rows.  P = the inclusive prefix of weights in double, in the fixed order
+ * ts_density_sample uses; draw j picks the first row with P_i > (double)uniforms[j] * P_{n-1} (uniforms float32 [m] in
+ * [0,1)) by bisection, and from a row of weight 0 moves to the nearest earlier row of positive weight, else the nearest
+ * later one; -1 when every weight is 0.  picks int32 [m] <- the rows; counts int32 [n] <- how many draws picked each row
+ * (zeroed here, integer atomics).  ws: >= ts_mcmc_sample_ws_bytes(n) bytes, 256-byte aligned.
+ * ts_mcmc_rewrite: every row with counts[i] > 0 is rewritten in place from its old values: M = min(counts[i] + 1,
+ * TS_MCMC_N_MAX), o' = 1 - (1 - o)^(1/M), D = sum_{a=1..M} sum_{k<a} C(a-1,k) (-1)^k o'^(k+1) / sqrt(k+1) (both in
+ * double, each rounded to float32 once), opacities[i] <- logit(clamp(o', min_opacity, 1 - 2^-23)), scales[i, :] += log(o /
+ * D); and row i of the num_tensors (0..TS_GATHER_MAX_TENSORS) moment pairs exp_avg / exp_avg_sq (HOST tables of device
+ * pointers, row_floats_host[k] floats per row) is set to zero.  Other rows are not touched.
+ * ts_mcmc_copy_rows: for j < m and every tensor k: params[k][dst_rows[j], :] <- params[k][src_rows[j], :] and, where the
+ * tables are given (both or neither), both moments of row dst_rows[j] <- 0.  Rows are in [0, n); a pair with a row
+ * outside is skipped.  No row may be both a destination and a source. */
+#define TS_MCMC_N_MAX 51
+#define TS_MCMC_MEAN_SIGMOID 0
+#define TS_MCMC_MEAN_EXP 1
+int ts_mcmc_noise(int32_t n, float* means, const float* scales, const float* quats, const float* opacities, float scale,
+                  const float* z, uint64_t seed, uint32_t step, void* stream);
+int ts_mcmc_normals(int32_t n, uint64_t seed, uint32_t step, float* out, void* stream);
+int64_t ts_mcmc_mean_ws_bytes(int64_t count);
+int ts_mcmc_mean(int32_t kind, int64_t count, const float* x, float* value, float* grad, void* ws, void* stream);
+int ts_mcmc_weights(int32_t n, const float* opacities, float min_opacity, int32_t zero_dead, double* weights,
+                    uint8_t* flags, void* stream);
+int64_t ts_mcmc_sample_ws_bytes(int32_t n);
+int ts_mcmc_sample_rows(int32_t n, int32_t m, const double* weights, const float* uniforms, int32_t* picks,
+                        int32_t* counts, void* ws, void* stream);
+int ts_mcmc_rewrite(int32_t n, const int32_t* counts, float min_opacity, float* opacities, float* scales,
+                    int32_t num_tensors, float* const* exp_avg_host, float* const* exp_avg_sq_host,
+                    const int32_t* row_floats_host, void* stream);
+int ts_mcmc_copy_rows(int32_t n, int32_t m, const int32_t* dst_rows, const int32_t* src_rows, int32_t num_tensors,
+                      float* const* params_host, float* const* exp_avg_host, float* const* exp_avg_sq_host,
+                      const int32_t* row_floats_host, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

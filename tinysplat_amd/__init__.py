@@ -12,6 +12,8 @@ from .clean import CleanConfig, clean_mesh, mesh_components
 from .dataset import Dataset
 from .depth import DepthPriors, SparseDepth, match_scale, sparse_depth
 from .jpeg import JpegEncoder, encode_jpeg
+from .mcmc import (ExponentialLr, McmcConfig, McmcDensifier, inject_noise, mcmc_normals, mean_opacity, mean_scale,
+                   relocation, sample_rows)
 from .metrics import EvalResult, Evaluator, evaluate, holdout_split, image_metrics
 from .fusion import FusionConfig, extract_mesh_tsdf, fuse_depth_maps, render_depth_alpha
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
@@ -33,4 +35,5 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "image_metrics", "evaluate", "holdout_split", "Evaluator", "EvalResult", "DepthPriors", "SparseDepth", "match_scale",
            "sparse_depth", "FusionConfig", "fuse_depth_maps", "render_depth_alpha", "extract_mesh_tsdf", "SemanticMaps",
            "LiftResult", "lift_labels", "labels_from_votes", "gaussian_contributions", "select_gaussians", "render_labels",
-           "label_iou"]
+           "label_iou", "McmcConfig", "McmcDensifier", "ExponentialLr", "sample_rows", "relocation", "inject_noise",
+           "mcmc_normals", "mean_opacity", "mean_scale"]

@@ -68,6 +68,10 @@ SOURCES = [
     # votes.hip: its staging culls are raster.hip's and are compiled as raster.hip compiles them (no file-wide contraction
     # switch); the per-pixel body that must give the forward's bits turns contraction off itself, as fwd_chunk does
     ("votes.hip", []),
+    # mcmc.hip: the noise's Sigma z and the normals' Box-Muller are compared with the host build of mcmc_math.h, which
+    # rounds every product and sum on its own, and the double series of the relocation is compared with a float64
+    # restatement term by term; an fma in either would make the device and the host build two different functions
+    ("mcmc.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_double, c_float, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_double, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 from pathlib import Path
 
 # TS_LIB_PATH: another build of the library (tests/test_gpu_variants.py loads builds with the other settings of the
@@ -283,6 +283,15 @@ SIGNATURES = {
     "ts_depth_prior_apply": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, _P]),
     "ts_label_votes": (c_int32, [c_int32, _CAM, _P, _P, _P, _P, _P, c_int32, _P, _P]),
     "ts_votes_labels": (c_int32, [c_int32, c_int32, _P, c_double, _P, _P, _P]),
+    "ts_mcmc_noise": (c_int32, [c_int32, _P, _P, _P, _P, c_float, _P, c_uint64, c_uint32, _P]),
+    "ts_mcmc_normals": (c_int32, [c_int32, c_uint64, c_uint32, _P, _P]),
+    "ts_mcmc_mean_ws_bytes": (c_int64, [c_int64]),
+    "ts_mcmc_mean": (c_int32, [c_int32, c_int64, _P, _P, _P, _P, _P]),
+    "ts_mcmc_weights": (c_int32, [c_int32, _P, c_float, c_int32, _P, _P, _P]),
+    "ts_mcmc_sample_ws_bytes": (c_int64, [c_int32]),
+    "ts_mcmc_sample_rows": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
+    "ts_mcmc_rewrite": (c_int32, [c_int32, _P, c_float, _P, _P, c_int32, _P, _P, _P, _P]),
+    "ts_mcmc_copy_rows": (c_int32, [c_int32, c_int32, _P, _P, c_int32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

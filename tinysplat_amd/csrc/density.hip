@@ -2,8 +2,8 @@
 // model_gaussian.py:244-326), DESIGN.md section 6e.
 //
 //   sample (update steps)   weights a_i = prod(exp(s_i)) (or their prefix sums, the reference's quirk), an
-//                           inclusive prefix in double by a fixed tree, rows by binary search of caller-supplied
-//                           uniforms, p = mu + R(q/|q|) (exp(s) * xi) from caller-supplied normals xi; the values
+//                           inclusive prefix in double by a fixed tree (prefix_scan.h, shared with mcmc.hip),
+//                           rows by binary search of caller-supplied uniforms, p = mu + R(q/|q|) (exp(s) * xi) from caller-supplied normals xi; the values
 //                           the frozen backward needs (xi, exp(s), q) are kept per sample
 //   pairs (active steps)    one thread per point, two passes over its K = 16 neighbours: the density
 //                           d = sum sigmoid(o_j) exp(-q_j / 2), beta, the depth fetch, |d - approx| and, per
@@ -21,6 +21,7 @@
 
 #include "../../include/tinysplat_hip.h"
 #include "host_util.h"
+#include "prefix_scan.h"
 
 #ifndef TS_PIX_OFF
 #define TS_PIX_OFF 0.0f
@@ -29,7 +30,6 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kScanItems = 8;                       // per thread: one scan workgroup covers 2048 weights
 constexpr int kK = TS_DENSITY_K;
 constexpr int kRow = TS_DENSITY_ROW;                // gradient row: mu xyz | s xyz | q wxyz | opacity
 constexpr int kFrozen = TS_DENSITY_FROZEN;          // per sample: xi xyz | exp(s) xyz | q wxyz
@@ -84,64 +84,6 @@ __global__ __launch_bounds__(kThreads) void weights_kernel(int n, const float* _
     if (i >= n) return;
     const float e0 = expf(scales[i * 3]), e1 = expf(scales[i * 3 + 1]), e2 = expf(scales[i * 3 + 2]);
     a[i] = (double)fabsf((e0 * e1) * e2);          // torch.prod(exp(scales), -1).abs() in float32
-}
-
-// inclusive scan, pass 1: each workgroup scans kThreads * kScanItems consecutive items (per-thread serial sums,
-// then a fixed Hillis-Steele tree over the thread totals) and writes its total
-__global__ __launch_bounds__(kThreads) void scan_local_kernel(int64_t n, const double* __restrict__ in,
-                                                              double* __restrict__ out, double* __restrict__ totals) {
-    __shared__ double sh[kThreads];
-    const int64_t base = (int64_t)blockIdx.x * (kThreads * kScanItems) + (int64_t)threadIdx.x * kScanItems;
-    double loc[kScanItems];
-    double acc = 0.0;
-#pragma unroll
-    for (int t = 0; t < kScanItems; ++t) {
-        acc += (base + t < n) ? in[base + t] : 0.0;
-        loc[t] = acc;
-    }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {
-        const double v = (int)threadIdx.x >= off ? sh[threadIdx.x - off] : 0.0;
-        __syncthreads();
-        sh[threadIdx.x] += v;
-        __syncthreads();
-    }
-    const double before = threadIdx.x > 0 ? sh[threadIdx.x - 1] : 0.0;
-#pragma unroll
-    for (int t = 0; t < kScanItems; ++t)
-        if (base + t < n) out[base + t] = before + loc[t];
-    if (threadIdx.x == kThreads - 1) totals[blockIdx.x] = sh[kThreads - 1];
-}
-
-// pass 2: one workgroup turns the workgroup totals into exclusive offsets (serial runs per thread + the same tree)
-__global__ __launch_bounds__(kThreads) void scan_totals_kernel(int64_t nb, double* __restrict__ totals) {
-    __shared__ double sh[kThreads];
-    const int64_t per = (nb + kThreads - 1) / kThreads;
-    const int64_t b0 = (int64_t)threadIdx.x * per;
-    double acc = 0.0;
-    for (int64_t b = b0; b < b0 + per && b < nb; ++b) acc += totals[b];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {
-        const double v = (int)threadIdx.x >= off ? sh[threadIdx.x - off] : 0.0;
-        __syncthreads();
-        sh[threadIdx.x] += v;
-        __syncthreads();
-    }
-    double run = threadIdx.x > 0 ? sh[threadIdx.x - 1] : 0.0;
-    for (int64_t b = b0; b < b0 + per && b < nb; ++b) {
-        const double t = totals[b];
-        totals[b] = run;
-        run += t;
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void scan_add_kernel(int64_t n, const double* __restrict__ offsets,
-                                                            double* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    out[i] += offsets[i / (kThreads * kScanItems)];
 }
 
 __global__ __launch_bounds__(kThreads) void sample_kernel(int n, int m, const double* __restrict__ cdf,
@@ -516,16 +458,7 @@ __global__ __launch_bounds__(kThreads) void segment_join_kernel(int64_t T, const
     for (int d = 0; d < D; ++d) out[(int64_t)key * D + d] = (float)(acc[d] * (double)sc);
 }
 
-inline int64_t scan_blocks(int64_t n) { return (n + kThreads * kScanItems - 1) / (kThreads * kScanItems); }
 inline int loss_blocks(int32_t m) { return (int)nblocks(m < 1 ? 1 : m, kThreads); }
-
-void scan(int64_t n, const double* in, double* out, double* totals, hipStream_t s) {
-    const int64_t nb = scan_blocks(n);
-    hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, n, in, out, totals);
-    hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(kThreads), 0, s, nb, totals);
-    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nblocks(n, kThreads)), dim3(kThreads), 0, s, n,
-                       (const double*)totals, out);
-}
 
 }  // namespace
 

@@ -284,7 +284,8 @@ class TrainStep:
     def __call__(self, camera, target_rgb: Tensor, target_depth: Optional[Tensor] = None,
                  densifier=None, step: Optional[int] = None, surface=None):
         """``densifier`` (densify.Densifier) + ``step`` add train.py:99-102 after the Adam update:
-        gradient accumulation and, on the policy's steps, clone / split / prune.
+        gradient accumulation and, on the policy's steps, clone / split / prune.  A densifier with a ``loss_terms(model,
+        step)`` method (mcmc.McmcDensifier) adds its terms to the loss as ``surface`` does.
         ``surface`` (surface.SurfaceRegularizer) + ``step`` add the regularisers of train.py:71-91 that its schedule
         makes active at ``step`` (the density term on the rendered depth): ``loss += lambda * term``, one backward for
         the whole loss, then the two-launch Adam (the fused in-backward update only sees the frame's own gradients);
@@ -295,6 +296,10 @@ class TrainStep:
             if step is None:
                 raise ValueError("the surface regularisers need the 1-based step number")
             terms = surface.terms(self.model, step)
+        if densifier is not None and hasattr(densifier, "loss_terms"):   # mcmc.McmcDensifier: its two mean regularisers
+            if step is None:
+                raise ValueError("densification needs the 1-based step number")
+            terms.update(densifier.loss_terms(self.model, step))
         rgb, extras = self.scene.render(camera)
         if surface is not None:                                # train.py:77-91: the density term reads the render
             terms.update(surface.frame_terms(self.model, step, camera, extras))
@@ -389,14 +394,16 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
         sh_increment_interval: int = 500, max_sh_degree: int = 3, lambda_dssim: float = 0.2,
         lambda_depth: float = 0.2, depth_schedule: Optional[Scheduler] = None, densifier=None,
         lrs: Optional[Dict[str, float]] = None, rng=None, generator: Optional[torch.Generator] = None,
-        on_step=None, surface=None):
+        on_step=None, surface=None, lr_schedule=None):
     """The training loop of scripts/train.py:45-106 (steps 1-7) on in-memory cameras / targets:
     SH degree schedule (:49-50, model_gaussian.py:126-128), random background (:51), camera pick
     (:54), render + loss (:55-69), the opacity-entropy (:71-75) and SuGaR density (:77-91)
     regularisers when ``surface`` (surface.SurfaceConfig) enables them, backward + Adam (:93-97),
     gradient accumulation and densification (:99-102), the density window's opening prune
     (:103-105).  ``generator`` also draws the density samples.  Dataset loading, metrics and
-    checkpoints stay with the caller (``on_step(step, out)``)."""
+    checkpoints stay with the caller (``on_step(step, out)``).  ``lr_schedule``: a callable ``step -> {name: lr}`` whose
+    rates are written into ``Adam.lrs`` before the step (``mcmc.ExponentialLr``: the reference's ``update_learning_rate``
+    TODO, model_gaussian.py:122-124); None, the default: the rates stay constant."""
     dev = torch.device(device)
     scene = Scene(cameras, model, device=dev, rng=rng)
     step_fn = TrainStep(model, dev, lambda_dssim, lambda_depth, lrs, scene=scene)
@@ -412,6 +419,8 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
             else torch.rand(3, device=dev)
         i = pick(step)
         use_depth = depth_targets is not None and (depth_schedule is None or depth_schedule(step))
+        if lr_schedule is not None:
+            step_fn.optimizer.lrs.update(lr_schedule(step))
         out = step_fn(cameras[i], targets[i], depth_targets[i] if use_depth else None,
                       densifier=densifier, step=step, surface=surface)
         if on_step is not None:

@@ -16,8 +16,10 @@ appends the rows to a file.  ``--regularize-depth`` adds the reference's depth t
 maps ``<dataset-dir>/<depths-path>/<image name>.npy``, made with any model, are scale-matched to the SfM points on the GPU
 (``tinysplat_amd.DepthPriors``) and weigh in with ``--lambda-depth`` from step ``--regularize-depth-start`` to
 ``--regularize-depth-end``; a camera without a usable map trains without the term, held-out views get none, and
-``--depth-fits-csv`` writes the table of fits.  Without the flag the run is what it was.  Flags the reference's parser has
-keep its names and defaults.  Needs a GPU: there is no CPU path.
+``--depth-fits-csv`` writes the table of fits.  Without the flag the run is what it was.  ``--strategy mcmc`` replaces the
+reference's clone / split / prune with budgeted densification (``tinysplat_amd.McmcDensifier``): dead Gaussians are moved
+onto live ones and the set grows to exactly ``--max-gaussians``; ``--means-lr-final`` decays the means' learning rate
+log-linearly over the run (off unless given).  Flags the reference's parser has keep its names and defaults.  Needs a GPU: there is no CPU path.
 """
 import argparse
 import sys
@@ -54,12 +56,35 @@ def parse_depth(argv=None):
     return args
 
 
+def _strategy_parser():
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    g = ap.add_argument_group("densification strategy")
+    g.add_argument("--strategy", choices=("reference", "mcmc"), default="reference",
+                   help="reference: the reference's clone / split / prune; mcmc: relocation and growth to --max-gaussians")
+    g.add_argument("--max-gaussians", type=int, default=1_000_000, help="the cap of --strategy mcmc (cap_max)")
+    g.add_argument("--means-lr-final", type=float, default=None,
+                   help="decay the means' learning rate log-linearly to this value over --max-iter steps")
+    return ap
+
+
+def parse_strategy(argv=None):
+    """The densification strategy's options, a namespace of their own like the depth prior's."""
+    ap = _strategy_parser()
+    args, _rest = ap.parse_known_args(argv)
+    if args.max_gaussians < 1 or (args.means_lr_final is not None and not args.means_lr_final > 0):
+        ap.error("--max-gaussians must be at least 1 and --means-lr-final positive")
+    return args
+
+
 def parse(argv=None):
-    depth_ap = _depth_parser()
+    depth_ap, strategy_ap = _depth_parser(), _strategy_parser()
     parse_depth(argv)                                          # checks the depth prior's options
+    parse_strategy(argv)
     _depth, argv = depth_ap.parse_known_args(argv)
+    _strategy, argv = strategy_ap.parse_known_args(argv)
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter,
-                                 epilog=depth_ap.format_help().split("\n\n", 1)[-1])
+                                 epilog=depth_ap.format_help().split("\n\n", 1)[-1] + "\n" +
+                                 strategy_ap.format_help().split("\n\n", 1)[-1])
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--max-iter", type=int, default=10_000)
@@ -92,7 +117,7 @@ def parse(argv=None):
 
 
 def main(argv=None):
-    args, depth = parse(argv), parse_depth(argv)
+    args, depth, strategy = parse(argv), parse_depth(argv), parse_strategy(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: tinysplat_amd has no CPU path")
@@ -129,7 +154,16 @@ def main(argv=None):
                               on_result=lambda row, _result: print(Evaluator.format(row), flush=True),
                               csv_path=args.metrics_csv)
         print(f"{len(cameras)} training cameras, {len(test)} held out")
-    densifier = Densifier(model, DensifyConfig(interval_densify=len(cameras)))      # train.py:277
+    if strategy.strategy == "mcmc":
+        from tinysplat_amd.mcmc import McmcConfig, McmcDensifier
+        densifier = McmcDensifier(model, McmcConfig(cap_max=strategy.max_gaussians))
+    else:
+        densifier = Densifier(model, DensifyConfig(interval_densify=len(cameras)))      # train.py:277
+    lr_schedule = None
+    if strategy.means_lr_final is not None:
+        from tinysplat_amd.mcmc import ExponentialLr
+        from tinysplat_amd.training import DEFAULT_LRS
+        lr_schedule = ExponentialLr(DEFAULT_LRS["means"], strategy.means_lr_final, max(args.max_iter, 1))
     viewer = None
     if args.viewer:
         from tinysplat_amd import Viewer
@@ -145,7 +179,7 @@ def main(argv=None):
         extra = {} if depth_targets is None else dict(depth_targets=depth_targets, lambda_depth=depth.lambda_depth,
                                                       depth_schedule=depth_schedule)
         out = fit(model, cameras, targets, args.device, args.max_iter, max_sh_degree=args.sh_degree,
-                  densifier=densifier, on_step=on_step if callbacks else None, **extra)
+                  densifier=densifier, on_step=on_step if callbacks else None, lr_schedule=lr_schedule, **extra)
     finally:
         if viewer:
             viewer.stop()
