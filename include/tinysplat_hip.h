@@ -1257,6 +1257,30 @@ int ts_mcmc_copy_rows(int32_t n, int32_t m, const int32_t* dst_rows, const int32
                       float* const* params_host, float* const* exp_avg_host, float* const* exp_avg_sq_host,
                       const int32_t* row_floats_host, void* stream);
 
+/* ======================================= per-view appearance ================================== */
+/* DESIGN.md section 6s; the arithmetic is csrc/appearance_math.h's.  image, out, v_out, v_image: float32 [height, width, 3],
+ * contiguous; grid, v_grid: float32 [levels, grid_h, grid_w, 12] of one view, the grid 16-byte aligned; every size >= 1.
+ * All results are the same bits on every run (no float atomics).  TS_E_BADARG for a NULL pointer or a non-positive size.
+ * ts_appearance_fwd: out <- the sliced affine map of every pixel (not clamped); out may not alias image.
+ * ts_appearance_bwd: v_image <- d loss / d image from v_out = d loss / d out, v_grid <- d loss / d grid (overwritten; the
+ * sums in double, rounded to float32 once).  Two launches.  ws: >= ts_appearance_ws_bytes bytes, 8-byte aligned.
+ * ts_grid_tv: value[0] (double) <- tv(grid), the sum over the axes of size > 1 of the mean squared difference of
+ * neighbouring vertices; v_out[e] <- (v_in ? v_in[e] : 0) + weight * (float) d tv / d grid[e].  One workgroup; v_out may
+ * alias v_in, not grid.
+ * ts_affine_fit_sums: out22 (double) <- over all pixels, phi = (r, g, b, 1) of image and t of target (float32 or uint8
+ * [height, width, 3], a byte standing for b / 255 as in ts_image_metrics): the sums rr rg rb r gg gb g bb b 1, then
+ * phi_k t_c at 10 + 3 k + c.  Two launches.  ws: >= ts_affine_fit_ws_bytes bytes, 8-byte aligned like out22. */
+int64_t ts_appearance_ws_bytes(int32_t height, int32_t width, int32_t levels, int32_t grid_h, int32_t grid_w);
+int ts_appearance_fwd(int32_t height, int32_t width, int32_t levels, int32_t grid_h, int32_t grid_w, const float* image,
+                      const float* grid, float* out, void* stream);
+int ts_appearance_bwd(int32_t height, int32_t width, int32_t levels, int32_t grid_h, int32_t grid_w, const float* image,
+                      const float* grid, const float* v_out, float* v_image, void* ws, float* v_grid, void* stream);
+int ts_grid_tv(int32_t levels, int32_t grid_h, int32_t grid_w, const float* grid, float weight, const float* v_in,
+               double* value, float* v_out, void* stream);
+int64_t ts_affine_fit_ws_bytes(int32_t height, int32_t width);
+int ts_affine_fit_sums(int32_t height, int32_t width, const float* image, const void* target, int32_t target_is_u8,
+                       void* ws, double* out22, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

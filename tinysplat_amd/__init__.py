@@ -14,7 +14,8 @@ from .depth import DepthPriors, SparseDepth, match_scale, sparse_depth
 from .jpeg import JpegEncoder, encode_jpeg
 from .mcmc import (ExponentialLr, McmcConfig, McmcDensifier, inject_noise, mcmc_normals, mean_opacity, mean_scale,
                    relocation, sample_rows)
-from .metrics import EvalResult, Evaluator, evaluate, holdout_split, image_metrics
+from .metrics import EvalResult, Evaluator, affine_color_fit, evaluate, holdout_split, image_metrics
+from .appearance import AppearanceConfig, AppearanceModel
 from .fusion import FusionConfig, extract_mesh_tsdf, fuse_depth_maps, render_depth_alpha
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
 from .rasterizer import GaussianRasterizer
@@ -36,4 +37,4 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "sparse_depth", "FusionConfig", "fuse_depth_maps", "render_depth_alpha", "extract_mesh_tsdf", "SemanticMaps",
            "LiftResult", "lift_labels", "labels_from_votes", "gaussian_contributions", "select_gaussians", "render_labels",
            "label_iou", "McmcConfig", "McmcDensifier", "ExponentialLr", "sample_rows", "relocation", "inject_noise",
-           "mcmc_normals", "mean_opacity", "mean_scale"]
+           "mcmc_normals", "mean_opacity", "mean_scale", "AppearanceConfig", "AppearanceModel", "affine_color_fit"]

@@ -72,6 +72,10 @@ SOURCES = [
     # rounds every product and sum on its own, and the double series of the relocation is compared with a float64
     # restatement term by term; an fma in either would make the device and the host build two different functions
     ("mcmc.hip", ["-ffp-contract=off"]),
+    # appearance.hip: the forward and the image gradient must be the bits of the host build of appearance_math.h, which
+    # rounds every product and sum of the nested lerps on its own (an fma would also break "a constant grid returns its
+    # constant"), and the double sums of the total variation and the fit are compared with the host build bit for bit
+    ("appearance.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

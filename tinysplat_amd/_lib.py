@@ -292,6 +292,12 @@ SIGNATURES = {
     "ts_mcmc_sample_rows": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
     "ts_mcmc_rewrite": (c_int32, [c_int32, _P, c_float, _P, _P, c_int32, _P, _P, _P, _P]),
     "ts_mcmc_copy_rows": (c_int32, [c_int32, c_int32, _P, _P, c_int32, _P, _P, _P, _P, _P]),
+    "ts_appearance_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "ts_appearance_fwd": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    "ts_appearance_bwd": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_grid_tv": (c_int32, [c_int32, c_int32, c_int32, _P, c_float, _P, _P, _P, _P]),
+    "ts_affine_fit_ws_bytes": (c_int64, [c_int32, c_int32]),
+    "ts_affine_fit_sums": (c_int32, [c_int32, c_int32, _P, _P, c_int32, _P, _P, _P]),
 }
 
 _lib = None

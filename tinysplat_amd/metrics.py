@@ -56,6 +56,56 @@ def image_metrics(image: Tensor, target: Tensor, out: Optional[Tensor] = None) -
     return out
 
 
+def affine_fit_sums(image: Tensor, target: Tensor) -> Tensor:
+    """``ts_affine_fit_sums``: the 22 sums of the least-squares affine colour fit of ``image`` (float32 [H, W, 3]) to
+    ``target`` ([H, W, 3], float32 or uint8 whose bytes stand for b / 255) -> a float64 [22] device tensor: with
+    phi = (r, g, b, 1), the ten distinct sums of phi phi^T (rr rg rb r gg gb g bb b 1), then phi_k t_c at 10 + 3 k + c.
+    Accumulated in double in a fixed order: the same bits on every run."""
+    dev = _need_hip(image, target)
+    if image.dim() != 3 or image.shape[2] != 3 or image.dtype != torch.float32:
+        raise ValueError("image must be float32 [H, W, 3]")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    if tuple(target.shape) != (h, w, 3) or target.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"target must be float32 or uint8 [{h}, {w}, 3], got {target.dtype} {tuple(target.shape)}")
+    image, target = image.contiguous(), target.contiguous()
+    lib = _lib.load()
+    ws = torch.empty((int(lib.ts_affine_fit_ws_bytes(h, w)),), dtype=torch.uint8, device=dev)
+    out = torch.empty((22,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _call("ts_affine_fit_sums", lib.ts_affine_fit_sums, h, w, _ptr(image), _ptr(target),
+              int(target.dtype == torch.uint8), _ptr(ws), _ptr(out), _stream(dev))
+    return out
+
+
+FIT_RCOND = 1e-12                # singular values of S below this share of the largest count as zero (a one-colour image)
+
+
+def affine_fit_solve(sums) -> np.ndarray:
+    """The 22 sums -> M = (pinv(S) B)^T, float64 [3, 4]: the affine colour map that takes the image closest to the target
+    in the least-squares sense; the minimum-norm one where the image's colours do not span all of (r, g, b, 1)."""
+    sums = np.asarray(sums, dtype=np.float64).reshape(22)
+    S = np.zeros((4, 4), np.float64)
+    S[np.triu_indices(4)] = sums[:10]
+    S = S + np.triu(S, 1).T
+    B = sums[10:].reshape(4, 3)
+    return (np.linalg.pinv(S, rcond=FIT_RCOND, hermitian=True) @ B).T
+
+
+def affine_color_fit(image: Tensor, target: Tensor) -> np.ndarray:
+    """float64 [3, 4]: the least-squares affine colour map from ``image`` to ``target``.  The sums
+    are taken on the device, the 4x4 solve on the host: one device-to-host copy of 22 doubles."""
+    return affine_fit_solve(affine_fit_sums(image, target).cpu().numpy())
+
+
+def color_corrected(image: Tensor, target: Tensor) -> Tensor:
+    """``image`` (float32 [H, W, 3 or 4]; a fourth channel is dropped) mapped by its own affine fit to ``target``: the fit
+    as a 1x1x1 grid through ``ts_appearance_fwd`` -> a new [H, W, 3] tensor."""
+    from .appearance import apply_grid
+    rgb = image[..., :3].contiguous()
+    M = torch.from_numpy(affine_color_fit(rgb, target)).to(torch.float32).reshape(1, 1, 1, 12)
+    return apply_grid(rgb, M.to(rgb.device))
+
+
 @dataclass
 class EvalResult:
     """``table``: float64 [V, 4], a row of {mse, l1, ssim, psnr} per view; ``names``: the views' names.  The properties
@@ -90,13 +140,15 @@ def _target(targets, i: int) -> Tensor:
 
 
 @torch.no_grad()
-def evaluate(model, cameras: Sequence, targets, device, background=None) -> EvalResult:
+def evaluate(model, cameras: Sequence, targets, device, background=None, color_correct: bool = False) -> EvalResult:
     """Renders every camera forward-only (``frame.render_view``, the viewer's path: its image is the training forward's
     bit for bit) on a fixed background - black unless given, the reference model's ``torch.zeros(3)``; the training loop
     draws a random one per step - and measures it against ``targets[i]`` (a ``dataset.Targets``, whose uint8 images are
     read directly, or a sequence of float32 / uint8 [H, W, 3] tensors).  View i fills row i of one [V, 4] device table;
     the only device-to-host copy comes after the last view has been enqueued.  The model is left as found: background,
-    SH degree, requires_grad flags, no .grad; no random number is drawn."""
+    SH degree, requires_grad flags, no .grad; no random number is drawn.  ``color_correct``: held-out views have no
+    colour grid (appearance.py), so each render is first mapped by its own least-squares affine fit to its target
+    (``color_corrected``) and then measured; False, the default: the render is measured as it is."""
     from .rasterizer import GaussianRasterizer
     dev = torch.device(device)
     cameras = list(cameras)
@@ -110,6 +162,8 @@ def evaluate(model, cameras: Sequence, targets, device, background=None) -> Eval
     try:
         for i, camera in enumerate(cameras):
             image, _extras = render(camera, None, model.active_sh_degree)
+            if color_correct:
+                image = color_corrected(image, _target(targets, i))
             image_metrics(image, _target(targets, i), out=table[i])
     finally:
         model.background = found
@@ -139,11 +193,12 @@ class Evaluator:
     HEADER = ("step", "n", "psnr", "ssim", "l1")
 
     def __init__(self, model, cameras, targets, device, every: int, on_result: Optional[Callable] = None,
-                 csv_path=None, background=None):
+                 csv_path=None, background=None, color_correct: bool = False):
         if int(every) < 0:
             raise ValueError("Evaluator: every must not be negative (0: only final())")
         self.model, self.cameras, self.targets, self.device = model, list(cameras), targets, device
         self.every, self.on_result, self.background = int(every), on_result, background
+        self.color_correct = bool(color_correct)
         self.csv_path = None if csv_path is None else Path(csv_path)
         self.rows: List[tuple] = []
         self.results: List[EvalResult] = []
@@ -156,7 +211,8 @@ class Evaluator:
                 f"N: {n:<10}")
 
     def _evaluate(self, step: int):
-        result = evaluate(self.model, self.cameras, self.targets, self.device, self.background)
+        result = evaluate(self.model, self.cameras, self.targets, self.device, self.background,
+                          **({"color_correct": True} if self.color_correct else {}))
         row = (int(step), int(self.model.means.shape[0]), result.psnr, result.ssim, result.l1)
         self.rows.append(row)
         self.results.append(result)

@@ -282,7 +282,7 @@ class TrainStep:
         _hold(model, "TrainStep")        # per-row state now exists outside the model: see SplatModel.spatial_sort_
 
     def __call__(self, camera, target_rgb: Tensor, target_depth: Optional[Tensor] = None,
-                 densifier=None, step: Optional[int] = None, surface=None):
+                 densifier=None, step: Optional[int] = None, surface=None, appearance=None, view: Optional[int] = None):
         """``densifier`` (densify.Densifier) + ``step`` add train.py:99-102 after the Adam update:
         gradient accumulation and, on the policy's steps, clone / split / prune.  A densifier with a ``loss_terms(model,
         step)`` method (mcmc.McmcDensifier) adds its terms to the loss as ``surface`` does.
@@ -290,7 +290,13 @@ class TrainStep:
         makes active at ``step`` (the density term on the rendered depth): ``loss += lambda * term``, one backward for
         the whole loss, then the two-launch Adam (the fused in-backward update only sees the frame's own gradients);
         after densification, the prune of train.py:103-105 on its step.  On a step where nothing is active the step
-        is exactly the one without ``surface``."""
+        is exactly the one without ``surface``.
+        ``appearance`` (appearance.AppearanceModel) + ``view`` (the camera's index among the training views) put the
+        view's colour grid between the render and the loss: the loss reads ``appearance.apply(rgb, view)``, the backward
+        pass goes through it into the frame, and ``appearance.step(view)`` updates the view's grid after it; ``out`` gains
+        ``appearance_tv``.  The fused in-backward Adam of the Gaussians stays on.  None: the step is exactly today's."""
+        if appearance is not None and view is None:
+            raise ValueError("appearance needs the index of the rendered view")
         terms = {}
         if surface is not None:
             if step is None:
@@ -306,22 +312,28 @@ class TrainStep:
         frame = getattr(rgb, "_base", None)
         depth = extras["depth"]
         direct = None
+        # the image the loss reads; which of the three paths runs is decided on the render, as without appearance
+        shown = rgb if appearance is None else appearance.apply(rgb, view)
         if (rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.is_contiguous() and rgb.is_cuda and depth.is_contiguous()
                 and depth.shape == rgb.shape[:2] and frame is None):
             # the adapter's one-node path hands out two contiguous images: the whole loss (train.py:58-69) on
             # them in one pair of launches, gradients back as two planes
-            values, v_rgb, v_depth = planes_loss_and_gradient(rgb, depth, target_rgb, target_depth, self.lambda_dssim,
+            values, v_rgb, v_depth = planes_loss_and_gradient(shown, depth, target_rgb, target_depth, self.lambda_dssim,
                                                               self.lambda_depth)
             loss, l1, ssim, depth_l1 = values.unbind(0)
-            direct = ([rgb] + ([depth] if v_depth is not None else []), [v_rgb] + ([v_depth] if v_depth is not None else []))
+            direct = ([shown] + ([depth] if v_depth is not None else []), [v_rgb] + ([v_depth] if v_depth is not None else []))
         elif (frame is not None and frame.dim() == 3 and frame.shape[2] == 4 and frame.is_contiguous()
                 and extras["depth"]._base is frame):
             # the adapter's one-node path hands out views of ONE [H, W, 4] tensor: evaluate the
             # whole loss (train.py:58-69) on it in place, no slicing / re-packing of image or gradient
-            loss, l1, ssim, depth_l1 = frame_loss(frame, target_rgb, target_depth, self.lambda_dssim,
-                                                  self.lambda_depth)
+            if appearance is None:
+                loss, l1, ssim, depth_l1 = frame_loss(frame, target_rgb, target_depth, self.lambda_dssim,
+                                                      self.lambda_depth)
+            else:                                              # the applied image is a tensor of its own: the two-plane loss
+                loss, l1, ssim, depth_l1 = planes_loss(shown, extras["depth"].contiguous(), target_rgb, target_depth,
+                                                       self.lambda_dssim, self.lambda_depth)
         else:
-            loss, l1, ssim = photometric_loss(rgb, target_rgb, self.lambda_dssim)
+            loss, l1, ssim = photometric_loss(shown, target_rgb, self.lambda_dssim)
             if target_depth is not None:                          # train.py:65-69
                 depth_l1 = (extras["depth"] - target_depth).abs().mean()
                 loss = loss + self.lambda_depth * depth_l1
@@ -343,6 +355,7 @@ class TrainStep:
         else:
             run_backward()
             self.optimizer.step()
+        appearance_tv = None if appearance is None else appearance.step(view)
         xys_grad = extras["xys"].grad                          # consumed by densification (F2)
         if densifier is not None:
             if step is None:
@@ -357,6 +370,8 @@ class TrainStep:
             out["depth_l1"] = depth_l1.detach()
         for name, (_, term) in terms.items():
             out[name] = term.detach()
+        if appearance_tv is not None:
+            out["appearance_tv"] = appearance_tv
         return out
 
 
@@ -394,7 +409,7 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
         sh_increment_interval: int = 500, max_sh_degree: int = 3, lambda_dssim: float = 0.2,
         lambda_depth: float = 0.2, depth_schedule: Optional[Scheduler] = None, densifier=None,
         lrs: Optional[Dict[str, float]] = None, rng=None, generator: Optional[torch.Generator] = None,
-        on_step=None, surface=None, lr_schedule=None):
+        on_step=None, surface=None, lr_schedule=None, appearance=None):
     """The training loop of scripts/train.py:45-106 (steps 1-7) on in-memory cameras / targets:
     SH degree schedule (:49-50, model_gaussian.py:126-128), random background (:51), camera pick
     (:54), render + loss (:55-69), the opacity-entropy (:71-75) and SuGaR density (:77-91)
@@ -403,13 +418,21 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
     (:103-105).  ``generator`` also draws the density samples.  Dataset loading, metrics and
     checkpoints stay with the caller (``on_step(step, out)``).  ``lr_schedule``: a callable ``step -> {name: lr}`` whose
     rates are written into ``Adam.lrs`` before the step (``mcmc.ExponentialLr``: the reference's ``update_learning_rate``
-    TODO, model_gaussian.py:122-124); None, the default: the rates stay constant."""
+    TODO, model_gaussian.py:122-124); None, the default: the rates stay constant.  ``appearance``: an
+    ``appearance.AppearanceConfig`` (a model with one grid per camera is made from it) or an ``AppearanceModel``: every
+    step goes through the picked camera's colour grid; None, the default: no colour model."""
     dev = torch.device(device)
     scene = Scene(cameras, model, device=dev, rng=rng)
     step_fn = TrainStep(model, dev, lambda_dssim, lambda_depth, lrs, scene=scene)
     if surface is not None:
         from .surface import SurfaceRegularizer
         surface = SurfaceRegularizer(surface, generator)
+    if appearance is not None:
+        from .appearance import AppearanceConfig, AppearanceModel
+        if isinstance(appearance, AppearanceConfig):
+            appearance = AppearanceModel(len(cameras), appearance, dev)
+        if appearance.num_views != len(cameras):
+            raise ValueError(f"the appearance model has {appearance.num_views} views, the run {len(cameras)} cameras")
     pick = scene._sampler
     out = None
     for step in range(1, int(max_iter) + 1):
@@ -422,7 +445,8 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
         if lr_schedule is not None:
             step_fn.optimizer.lrs.update(lr_schedule(step))
         out = step_fn(cameras[i], targets[i], depth_targets[i] if use_depth else None,
-                      densifier=densifier, step=step, surface=surface)
+                      densifier=densifier, step=step, surface=surface,
+                      **({} if appearance is None else dict(appearance=appearance, view=i)))
         if on_step is not None:
             on_step(step, out)
     return out

@@ -10,7 +10,9 @@ training; ``--holdout 0`` evaluates all views.  Every view is rendered on a blac
 is the training loss's (pytorch_msssim: valid filtering), not the zero-padded SSIM of the 3DGS papers' tables.
 ``--semantic-dir D`` additionally lifts the label maps ``D/<image name>.npy`` of the TRAINING views onto the Gaussians
 (``semantic.lift_labels``), renders the labels at the evaluated views and prints their mean IoU against those views'
-maps.  Needs a GPU: there is no CPU path.
+maps.  ``--color-correct`` first maps every render to its target by a least-squares affine colour fit (3x4, per view) and
+measures the result: the numbers to quote for a scene trained with ``tools/train.py --appearance``, whose held-out views
+have no colour transform of their own.  Needs a GPU: there is no CPU path.
 """
 import argparse
 import csv
@@ -36,6 +38,8 @@ def parse(argv=None):
     ap.add_argument("--principal-point", choices=("reference", "center"), default="reference")
     ap.add_argument("--holdout", type=int, default=8, help="evaluate every N-th camera by image name; 0: all of them")
     ap.add_argument("--csv", type=str, default=None, help="write the per-view table and the means to this CSV file")
+    ap.add_argument("--color-correct", action="store_true",
+                    help="measure every render after its least-squares affine colour fit to the target")
     ap.add_argument("--semantic-dir", type=str, default=None,
                     help="label maps <image name>.npy: also print the mIoU of the rendered labels on the evaluated views")
     ap.add_argument("--semantic-classes", type=int, default=150, help="labels of the maps: 0 .. this - 1, 255 ignored")
@@ -90,13 +94,13 @@ def main(argv=None):
     if not views:
         raise SystemExit(f"--holdout {args.holdout} selects none of the {len(dataset.cameras)} cameras")
     result = evaluate(model, [dataset.cameras[i] for i in views], Targets([dataset.targets.images_u8[i] for i in views]),
-                      args.device)
+                      args.device, **({"color_correct": True} if args.color_correct else {}))
     rows = table_rows(result)
     width = max(len(r[0]) for r in rows)
     print(f"{'view':<{width}}  {'PSNR':>9}  {'SSIM':>8}  {'L1':>8}")
     for name, psnr, ssim, l1, _mse in rows:
         print(f"{name:<{width}}  {psnr:9.4f}  {ssim:8.5f}  {l1:8.5f}")
-    print(f"{len(views)} views, {model.num_points} Gaussians")
+    print(f"{len(views)} views, {model.num_points} Gaussians" + (", colour-corrected" if args.color_correct else ""))
     if args.semantic_dir:
         print(semantic_line(model, dataset.cameras, train, views, args))
     if args.csv:

@@ -19,7 +19,12 @@ maps ``<dataset-dir>/<depths-path>/<image name>.npy``, made with any model, are 
 ``--depth-fits-csv`` writes the table of fits.  Without the flag the run is what it was.  ``--strategy mcmc`` replaces the
 reference's clone / split / prune with budgeted densification (``tinysplat_amd.McmcDensifier``): dead Gaussians are moved
 onto live ones and the set grows to exactly ``--max-gaussians``; ``--means-lr-final`` decays the means' learning rate
-log-linearly over the run (off unless given).  Flags the reference's parser has keep its names and defaults.  Needs a GPU: there is no CPU path.
+log-linearly over the run (off unless given).  ``--appearance affine|grid`` trains a colour transform per training image
+between the render and the loss (``tinysplat_amd.AppearanceModel``: a 3x4 exposure matrix, or a bilateral grid of
+``--appearance-grid L H W`` of them) so that exposure and white balance that change from photo to photo do not end up in the
+scene; ``--appearance-out`` saves the transforms, and with ``--eval-holdout`` the table is also printed (and written to
+``<metrics-csv stem>_cc.csv``) for renders mapped to their targets by a least-squares affine colour fit, since held-out
+views have no transform.  Flags the reference's parser has keep its names and defaults.  Needs a GPU: there is no CPU path.
 """
 import argparse
 import sys
@@ -76,15 +81,55 @@ def parse_strategy(argv=None):
     return args
 
 
+def _appearance_parser():
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    g = ap.add_argument_group("per-view appearance")
+    g.add_argument("--appearance", choices=("none", "affine", "grid"), default="none",
+                   help="a colour transform per training image: affine, one 3x4 matrix; grid, a bilateral grid of them")
+    g.add_argument("--appearance-grid", type=int, nargs=3, default=None, metavar=("L", "H", "W"),
+                   help="luminance levels, rows and columns of --appearance grid (default 8 16 16)")
+    g.add_argument("--appearance-lr", type=float, default=2e-3)
+    g.add_argument("--appearance-tv", type=float, default=10.0, help="weight of the grids' total variation")
+    g.add_argument("--appearance-out", type=str, default=None, help="save the trained transforms to this file")
+    return ap
+
+
+def parse_appearance(argv=None):
+    """The appearance model's options, a namespace of their own like the depth prior's."""
+    ap = _appearance_parser()
+    args, _rest = ap.parse_known_args(argv)
+    if args.appearance_grid is not None and args.appearance != "grid":
+        ap.error("--appearance-grid needs --appearance grid")
+    if args.appearance_grid is None:
+        args.appearance_grid = [8, 16, 16]
+    if min(args.appearance_grid) < 1 or args.appearance_lr < 0 or args.appearance_tv < 0:
+        ap.error("--appearance-grid needs sizes of at least 1; --appearance-lr and --appearance-tv must not be negative")
+    if args.appearance_out is not None and args.appearance == "none":
+        ap.error("--appearance-out needs --appearance affine or grid")
+    return args
+
+
+def appearance_config(args):
+    """The ``AppearanceConfig`` of the parsed options; None for ``--appearance none``."""
+    if args.appearance == "none":
+        return None
+    from tinysplat_amd.appearance import AppearanceConfig
+    grid = (1, 1, 1) if args.appearance == "affine" else tuple(args.appearance_grid)
+    return AppearanceConfig(grid=grid, lr=args.appearance_lr, tv_weight=args.appearance_tv)
+
+
 def parse(argv=None):
-    depth_ap, strategy_ap = _depth_parser(), _strategy_parser()
+    depth_ap, strategy_ap, appearance_ap = _depth_parser(), _strategy_parser(), _appearance_parser()
     parse_depth(argv)                                          # checks the depth prior's options
     parse_strategy(argv)
+    parse_appearance(argv)
     _depth, argv = depth_ap.parse_known_args(argv)
     _strategy, argv = strategy_ap.parse_known_args(argv)
+    _appearance, argv = appearance_ap.parse_known_args(argv)
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter,
                                  epilog=depth_ap.format_help().split("\n\n", 1)[-1] + "\n" +
-                                 strategy_ap.format_help().split("\n\n", 1)[-1])
+                                 strategy_ap.format_help().split("\n\n", 1)[-1] + "\n" +
+                                 appearance_ap.format_help().split("\n\n", 1)[-1])
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--max-iter", type=int, default=10_000)
@@ -117,7 +162,7 @@ def parse(argv=None):
 
 
 def main(argv=None):
-    args, depth, strategy = parse(argv), parse_depth(argv), parse_strategy(argv)
+    args, depth, strategy, look = parse(argv), parse_depth(argv), parse_strategy(argv), parse_appearance(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: tinysplat_amd has no CPU path")
@@ -130,7 +175,7 @@ def main(argv=None):
     print(f"{len(dataset.cameras)} cameras ({sum(dataset.resampled)} resampled), {dataset.pcd.xyz.shape[0]} points, "
           f"extent {dataset.spatial_extent:.3f}")
     model = from_pcd(dataset.pcd, sh_degree=args.sh_degree, device=args.device)
-    cameras, targets, evaluator = dataset.cameras, dataset.targets, None
+    cameras, targets, evaluator, corrected = dataset.cameras, dataset.targets, None, None
     depth_targets = depth_schedule = None
     if depth.regularize_depth:
         from tinysplat_amd import DepthPriors
@@ -153,6 +198,12 @@ def main(argv=None):
         evaluator = Evaluator(model, *held, args.device, args.eval_interval or len(cameras),
                               on_result=lambda row, _result: print(Evaluator.format(row), flush=True),
                               csv_path=args.metrics_csv)
+        if look.appearance != "none":                         # held-out views have no transform: also measure them colour-corrected
+            cc_csv = None if args.metrics_csv is None else \
+                str(Path(args.metrics_csv).with_name(Path(args.metrics_csv).stem + "_cc" + Path(args.metrics_csv).suffix))
+            corrected = Evaluator(model, *held, args.device, args.eval_interval or len(cameras), csv_path=cc_csv,
+                                  on_result=lambda row, _result: print("colour-corrected | " + Evaluator.format(row), flush=True),
+                                  color_correct=True)
         print(f"{len(cameras)} training cameras, {len(test)} held out")
     if strategy.strategy == "mcmc":
         from tinysplat_amd.mcmc import McmcConfig, McmcDensifier
@@ -170,7 +221,12 @@ def main(argv=None):
         from tinysplat_amd.viewer import ViewRenderer
         viewer = Viewer(ViewRenderer(model, dataset.cameras[0], args.device), args.viewer_ip, args.viewer_port)
         print(f"viewer on ws://{args.viewer_ip}:{viewer.port}")
-    callbacks = [f for f in (evaluator, viewer.service if viewer else None) if f is not None]
+    callbacks = [f for f in (evaluator, corrected, viewer.service if viewer else None) if f is not None]
+    appearance = None
+    if look.appearance != "none":
+        from tinysplat_amd.appearance import AppearanceModel
+        appearance = AppearanceModel(len(cameras), appearance_config(look), args.device)
+        print(f"appearance: {len(cameras)} grids of {'x'.join(map(str, appearance.config.grid))} colour matrices")
 
     def on_step(step, out):
         for f in callbacks:
@@ -178,6 +234,8 @@ def main(argv=None):
     try:
         extra = {} if depth_targets is None else dict(depth_targets=depth_targets, lambda_depth=depth.lambda_depth,
                                                       depth_schedule=depth_schedule)
+        if appearance is not None:
+            extra["appearance"] = appearance
         out = fit(model, cameras, targets, args.device, args.max_iter, max_sh_degree=args.sh_degree,
                   densifier=densifier, on_step=on_step if callbacks else None, lr_schedule=lr_schedule, **extra)
     finally:
@@ -185,6 +243,11 @@ def main(argv=None):
             viewer.stop()
     if evaluator is not None:
         evaluator.final(args.max_iter)
+    if corrected is not None:
+        corrected.final(args.max_iter)
+    if appearance is not None and look.appearance_out:
+        appearance.save(look.appearance_out)
+        print(f"wrote {look.appearance_out}: {appearance.num_views} appearance grids")
     if out is not None:
         print(f"step {args.max_iter}: loss {float(out['loss']):.6f}")
         if depth_targets is not None and "depth_l1" in out:
