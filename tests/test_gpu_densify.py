@@ -271,3 +271,58 @@ def test_spatial_order_is_a_permutation_that_leaves_the_frame_unchanged():
     d = (mb.means.detach()[1:] - mb.means.detach()[:-1]).norm(dim=1).mean()
     d0 = (ma.means.detach()[1:] - ma.means.detach()[:-1]).norm(dim=1).mean()
     assert d < 0.5 * d0                                     # neighbours in memory are neighbours in space
+
+
+@pytest.mark.parametrize("n,k_rest", [(1, 2), (3, 0), (1025, 8)])
+def test_reorder_is_a_gather(n, k_rest):
+    """Densifier.reorder copies rows with ts_gather_rows: every parameter, both moments and the accumulator are
+    ``old.index_select(0, perm)`` bit for bit.  1025 rows cross the plan's 1024-row block; 3 rows at SH degree 0 have a
+    zero-width colors_rest and 9 / 12 / 3 floats per tensor, which the gather's scalar tail copies."""
+    p, m, v, accum, g = _random_state(n, k_rest, 20 + n)
+    model, optim = _on_device(p, m, v)
+    model.quats = optim.params["quats"] = model.quats.detach()          # requires_grad False must survive, too
+    dens = Densifier(model)
+    dens.means_grad_accum = accum.to(DEV)
+    perm = torch.randperm(n, generator=g).to(DEV)
+    old = {k: (getattr(model, k).detach().clone(), optim.exp_avg[k].clone(), optim.exp_avg_sq[k].clone()) for k in D.FIELDS}
+    assert dens.reorder(optim, perm) is perm
+    for k in D.FIELDS:
+        now = getattr(model, k)
+        assert optim.params[k] is now and now.requires_grad == (k != "quats"), k
+        for got, was in zip((now.detach(), optim.exp_avg[k], optim.exp_avg_sq[k]), old[k]):
+            assert got.shape == was.shape and torch.equal(got, was.index_select(0, perm)), k
+    assert torch.equal(dens.means_grad_accum, accum.to(DEV).index_select(0, perm))
+
+
+def _launches(fn):
+    """-> {C-ABI entry: launches} of one call, recorded by ops.kernel_timer as tests/test_gpu_timer.py does"""
+    from tinysplat_amd.ops import kernel_timer
+    kernel_timer.start()
+    try:
+        fn()
+    finally:
+        table = kernel_timer.stop()
+    return {name: count for name, (count, _ms) in table.items()}
+
+
+def test_launch_inventory_of_the_rebuilds():
+    """What one rebuild issues: the plan, one gather each for the parameters, the two moments and the accumulator,
+    and nothing from PyTorch's indexing in their place."""
+    n = 1025
+    p, m, v, _, g = _random_state(n, 8, 3)
+    model, optim = _on_device(p, m, v)
+    dens = Densifier(model)
+    dens.means_grad_accum = torch.full((n,), 1.0, device=DEV)           # every row over the gradient threshold
+    got = _launches(lambda: dens.densify_and_prune(700, optim, {"camera": {"width": 640, "height": 480}}))
+    K, C, S, n2 = dens.last_counts
+    assert C > 0 and S > 0 and n2 == K + C + 2 * S
+    assert got == {"ts_densify_classify": 1, "ts_densify_plan": 1, "ts_gather_rows": 4, "ts_split_fixup": 1}
+    rows = model.means.shape[0]
+    mask = torch.rand(rows, generator=g) < 0.3
+    got = _launches(lambda: dens.update_state(optim, mask.to(DEV)))
+    assert dens.last_counts[0] == rows - int(mask.sum()) < rows
+    assert got == {"ts_densify_plan": 1, "ts_gather_rows": 4}
+    rows = model.means.shape[0]
+    assert dens.means_grad_accum.shape[0] == rows
+    got = _launches(lambda: dens.reorder(optim, torch.randperm(rows, generator=g).to(DEV)))
+    assert got == {"ts_gather_rows": 4}

@@ -308,6 +308,33 @@ def test_start_prune(enabled, ungated, pruned):
         assert n2 == n1
 
 
+def test_start_prune_without_a_densifier_is_update_state_on_a_copy():
+    """after_step with no densifier on the prune step: parameters and moments are what ``Densifier(model).update_state(
+    optim, sigmoid(opacities) < 0.5)`` leaves on a copy of the state, bit for bit, and no Densifier is registered."""
+    from tinysplat_amd.densify import Densifier
+    from tinysplat_amd.training import Adam
+    start, cam, tgt, tgt_d = _scene()
+    model = _fresh(start)
+    step = TrainStep(model, DEV)
+    surface = SurfaceRegularizer(_cfg(regularize_density_start=2), torch.Generator(device=DEV).manual_seed(1))
+    step(cam, tgt, tgt_d, step=1, surface=surface)              # Adam moments of a real step
+    optim = step.optimizer
+    copy = _fresh(model).requires_grad_(True)
+    ref = Adam({k: getattr(copy, k) for k in ALL})
+    for k in ALL:
+        ref.exp_avg[k], ref.exp_avg_sq[k] = optim.exp_avg[k].clone(), optim.exp_avg_sq[k].clone()
+    Densifier(copy).update_state(ref, (torch.sigmoid(copy.opacities) < 0.5).reshape(-1))
+    assert surface.prune_due(2) and not surface.prune_due(1)
+    n1 = model.means.shape[0]
+    surface.after_step(model, 2, optim)
+    assert 0 < model.means.shape[0] < n1 and "Densifier" not in model.held_by and "TrainStep" in model.held_by
+    for k in ALL:
+        assert optim.params[k] is getattr(model, k) and getattr(model, k).requires_grad, k
+        assert torch.equal(getattr(model, k), getattr(copy, k)), k
+        assert torch.equal(optim.exp_avg[k], ref.exp_avg[k]) and torch.equal(optim.exp_avg_sq[k], ref.exp_avg_sq[k]), k
+    assert bool(optim.exp_avg["means"].any()) and bool(optim.exp_avg_sq["opacities"].any())
+
+
 def test_both_regularisers_and_fit_in_screen_mode():
     from tinysplat_amd.densify import Densifier, DensifyConfig
     from tinysplat_amd.training import fit

@@ -413,3 +413,57 @@ def test_fit_grows_to_the_cap_and_stays_there():
     assert all(sizes[s - 1] == sizes[s - 2] for s in range(2, 301) if not cfg.fires(s))          # N moves on refinements only
     assert all(bool(torch.isfinite(p).all()) for p in model.parameters())
     assert losses[-1] < losses[0]
+
+
+# ------------------------------------------------------------------------------------------------ 9. the shared rebuild
+def _launches(fn):
+    """-> {C-ABI entry: launches} of one call, recorded by ops.kernel_timer as tests/test_gpu_timer.py does"""
+    from tinysplat_amd.ops import kernel_timer
+    kernel_timer.start()
+    try:
+        fn()
+    finally:
+        table = kernel_timer.stop()
+    return {name: count for name, (count, _ms) in table.items()}
+
+
+@pytest.mark.parametrize("appended", [0, 7])
+def test_update_state_is_the_densifiers_without_an_accumulator(appended):
+    """601 rows, a third of them dropped, with and without 7 caller-made rows: parameters and both moments are what
+    ``Densifier.update_state`` leaves on an identical copy, bit for bit; no Densifier is built or registered, and the
+    gather of the gradient accumulator nobody reads is not launched."""
+    from tinysplat_amd.densify import Densifier
+    n = 601
+    g = torch.Generator().manual_seed(51)
+    mask = (torch.rand(n, generator=g) < 1.0 / 3.0).to(DEV)
+    assert 150 < int(mask.sum()) < 250
+    states = []
+    for kind in ("densifier", "mcmc"):
+        model = _model(n, 13)
+        optim = _optim(model, 14)
+        g2 = torch.Generator().manual_seed(52)
+        rows = {nm: torch.randn((appended,) + tuple(getattr(model, nm).shape[1:]), generator=g2).to(DEV)
+                for nm in PARAMS} if appended else None
+        steps0 = dict(optim.steps)
+        d = Densifier(model) if kind == "densifier" else McmcDensifier(model, McmcConfig())
+        got = _launches(lambda: d.update_state(optim, mask, rows))
+        assert got == {"ts_densify_plan": 1, "ts_gather_rows": 4 if kind == "densifier" else 3}
+        assert optim.steps == steps0 and ("Densifier" in model.held_by) == (kind == "densifier")
+        assert all(optim.params[nm] is getattr(model, nm) for nm in PARAMS)
+        states.append((model, optim))
+    (ma, oa), (mb, ob) = states
+    assert mb.means.shape[0] == n - int(mask.sum()) + appended
+    for nm in PARAMS:
+        assert torch.equal(getattr(ma, nm), getattr(mb, nm)), nm
+        assert torch.equal(oa.exp_avg[nm], ob.exp_avg[nm]) and torch.equal(oa.exp_avg_sq[nm], ob.exp_avg_sq[nm]), nm
+
+
+def test_launch_inventory_of_a_relocation():
+    logits, _heavy = _relocation_case()
+    model = _model(len(logits), 3, logits)
+    optim = _optim(model, 4)
+    d = McmcDensifier(model, McmcConfig())
+    got = _launches(lambda: d.relocate(optim))
+    assert d.last_dead == len(logits) // 4
+    assert got == {"ts_mcmc_weights": 1, "ts_densify_plan": 1, "ts_mcmc_sample_rows": 1, "ts_mcmc_rewrite": 1,
+                   "ts_mcmc_copy_rows": 1}

@@ -136,6 +136,27 @@ def test_adam_matches_torch_optim():
         assert torch.allclose(mine[n], ref[n], rtol=2e-6, atol=2e-7), n
 
 
+def test_adam_step_on_an_sh0_model_with_a_non_contiguous_gradient():
+    """64 Gaussians at SH degree 0: colors_rest is [64, 0, 3], so nothing of it is launched, but its step count advances
+    as torch.optim.Adam's does; the means' gradient is a transposed view, copied once into row order.  One step against
+    torch.optim.Adam on CPU copies, at the tolerance of test_adam_matches_torch_optim."""
+    g = torch.Generator().manual_seed(5)
+    shapes = {"means": (64, 3), "colors_dc": (64, 3), "colors_rest": (64, 0, 3), "scales": (64, 3), "quats": (64, 4),
+              "opacities": (64, 1)}
+    ref = {n: torch.randn(s, generator=g).requires_grad_(True) for n, s in shapes.items()}
+    mine = {n: p.detach().clone().to(DEV).requires_grad_(True) for n, p in ref.items()}
+    for n, s in shapes.items():
+        gr = torch.randn(3, 64, generator=g).to(DEV).t() if n == "means" else torch.randn(s, generator=g).to(DEV)
+        mine[n].grad, ref[n].grad = gr, gr.cpu().contiguous()
+    assert not mine["means"].grad.is_contiguous() and mine["colors_rest"].grad is not None
+    opt = Adam(mine)
+    topt = torch.optim.Adam([{"params": [ref[n]], "lr": opt.lrs[n]} for n in shapes])
+    opt.step()
+    topt.step()
+    assert opt.steps == {n: 1 for n in shapes}
+    for n in shapes:
+        assert mine[n].shape == shapes[n] and torch.allclose(mine[n].detach().cpu(), ref[n].detach(), rtol=2e-6, atol=2e-7), n
+
 def test_train_step_reduces_the_loss():
     w, h, n = 160, 112, 4000
     target_model, cam = make_scene(n, 1, w, h, seed=5, scale_mult=4.0)

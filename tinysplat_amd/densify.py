@@ -11,22 +11,22 @@ names, argument meaning and gating - over the C-ABI entries of csrc/densify.hip:
 The model is any holder of the six parameter tensors (synthetic.SplatModel); ``optim`` is
 training.Adam (exp_avg / exp_avg_sq dictionaries keyed by parameter name, per-tensor step counts
 that densification leaves untouched, as the reference does by carrying the state dict over).
-Nothing here falls back to PyTorch indexing: the rebuilt tensors come from ts_gather_rows.
+Nothing here falls back to PyTorch indexing: the rebuilt tensors come from ts_gather_rows, through _rows.py.
 """
 from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 from torch import Tensor
 
 from . import _lib
 from ._lib import TsDensifyPolicy
+from ._rows import FIELDS, compact, fields_of, gather, hold, install, plan, rebuild   # noqa: F401 (FIELDS: importable)
 from .ops import _call, _f32c, _need_hip, _ptr, _stream
 
-FIELDS = ("means", "colors_dc", "colors_rest", "scales", "quats", "opacities")
 MAX_GAUSSIANS = 1000000          # model_gaussian.py:146
 
 
@@ -50,23 +50,6 @@ class DensifyConfig:
     spatial_order: bool = False
 
 
-def _row_floats(t: Tensor) -> int:
-    w = 1
-    for d in t.shape[1:]:
-        w *= int(d)
-    return w
-
-
-def _gather(src: Dict[str, Tensor], dst: Dict[str, Tensor], names, dst_rows: int, copy_rows: int,
-            src_of: Tensor, dev) -> None:
-    k = len(names)
-    PtrArr, IArr = ctypes.c_void_p * k, ctypes.c_int32 * k
-    lib = _lib.load()
-    _call("ts_gather_rows", lib.ts_gather_rows, k, PtrArr(*[src[n].data_ptr() for n in names]),
-          PtrArr(*[dst[n].data_ptr() for n in names]), IArr(*[_row_floats(src[n]) for n in names]),
-          int(dst_rows), int(copy_rows), _ptr(src_of), _stream(dev))
-
-
 class Densifier:
     def __init__(self, model, config: Optional[DensifyConfig] = None):
         self.model = model
@@ -74,14 +57,7 @@ class Densifier:
         self.means_grad_accum = torch.zeros(model.means.shape[0], dtype=torch.float32,
                                             device=model.means.device)      # :62
         self.last_counts = None      # (kept, cloned, split, new total) of the last rebuild
-        held = getattr(model, "held_by", None)          # see SplatModel.spatial_sort_: the accumulator is per row
-        if held is None:
-            try:
-                model.held_by = held = set()
-            except AttributeError:
-                held = None
-        if held is not None:
-            held.add("Densifier")
+        hold(model, "Densifier")     # see SplatModel.spatial_sort_: the accumulator is per row
 
     # ------------------------------------------------------------------ :130-132
     @torch.no_grad()
@@ -151,102 +127,54 @@ class Densifier:
         the permutation.  Not in the reference - see DensifyConfig.spatial_order."""
         from .synthetic import morton_order
         m = self.model
+        old, live, n, dev = fields_of(m)
         if perm is None:
             perm = morton_order(m.means)
-        for f in FIELDS:
-            old = getattr(m, f)
-            p = old.detach().index_select(0, perm).requires_grad_(old.requires_grad)
-            setattr(m, f, p)
-            optim.params[f] = p
-            optim.exp_avg[f] = optim.exp_avg[f].index_select(0, perm)
-            optim.exp_avg_sq[f] = optim.exp_avg_sq[f].index_select(0, perm)
-        if self.means_grad_accum.shape[0] == perm.shape[0]:
-            self.means_grad_accum = self.means_grad_accum.index_select(0, perm)
+        if perm.shape != (n,):
+            raise ValueError(f"perm must be a permutation of the {n} rows")
+        src_of = perm.to(device=dev, dtype=torch.int32)
+        install(m, optim, *rebuild(old, live, optim, src_of, n, n, n))
+        if self.means_grad_accum.shape[0] == n:
+            self._gather_accum(src_of, n, dev)
         return perm
+
+    def _gather_accum(self, src_of: Tensor, rows: int, dev) -> None:
+        accum = torch.empty((rows,), dtype=torch.float32, device=dev)
+        gather([self.means_grad_accum], [accum], rows, rows, src_of, dev)
+        self.means_grad_accum = accum
 
     # ------------------------------------------------------------------ :197-242
     @torch.no_grad()
     def update_state(self, optim, mask: Tensor, _tensors=None) -> None:
-        """model_gaussian.py:197-242: drop the rows where ``mask`` is True and append the caller's
-        rows.  Layout kept | appended, exactly the reference's ``cat((param[~mask], tensors[name]))``;
-        Adam moments of appended rows are zero; ``means_grad_accum`` keeps the surviving rows only
-        (``accum[~mask]``, :242 - shorter than the new N until the caller resets it, as in the
-        reference).  ``_tensors`` may name any subset of the six fields; missing ones append nothing,
-        and all given ones must append the same number of rows (the reference would build ragged
-        parameters otherwise).  The prune-only use is train.py:103-105."""
-        dev = _need_hip(self.model.means)
-        if mask.dtype != torch.bool or mask.shape != (self.model.means.shape[0],):
-            raise ValueError("mask must be bool [N]")
-        append = {}
-        for f, t in (_tensors or {}).items():
-            if f not in FIELDS:
-                raise KeyError(f"unknown parameter {f!r}")
-            want = tuple(getattr(self.model, f).shape[1:])
-            if tuple(t.shape[1:]) != want:
-                raise ValueError(f"{f}: rows must have shape {want}")
-            append[f] = _f32c(t.detach().to(dev))
-        live = [f for f in FIELDS if _row_floats(getattr(self.model, f)) > 0]
-        counts = {f: append[f].shape[0] for f in live if f in append}
-        extra = max(counts.values(), default=0)
-        if extra > 0 and (set(counts) != set(live) or set(counts.values()) != {extra}):
-            raise ValueError("every parameter must append the same number of rows")
-        flags = mask.to(device=dev, dtype=torch.uint8) * 4          # TS_DENSIFY_PRUNE
-        self._rebuild(optim, flags, None, append=append if extra > 0 else None)
+        """model_gaussian.py:197-242: drop the rows where ``mask`` is True and append the caller's rows (``_tensors``) -
+        ``_rows.compact``, which states the layout and the checks.  ``means_grad_accum`` keeps the surviving rows only
+        (``accum[~mask]``, :242 - shorter than the new N until the caller resets it, as in the reference).  The
+        prune-only use is train.py:103-105."""
+        n = self.model.means.shape[0]
+        kept, src_of = compact(self.model, optim, mask, _tensors)
+        self.last_counts = (kept, 0, 0, kept)
+        if kept < n or self.model.means.shape[0] > kept:           # rows were dropped or appended
+            self._gather_accum(src_of, kept, src_of.device)
 
-    # ------------------------------------------------------------------
-    def _rebuild(self, optim, flags: Tensor, z: Optional[Tensor], append=None) -> None:
+    # ------------------------------------------------------------------ :138-195
+    def _rebuild(self, optim, flags: Tensor, z: Optional[Tensor]) -> None:
         m = self.model
-        dev = _need_hip(*[getattr(m, f) for f in FIELDS], flags)
-        n = m.means.shape[0]
-        lib = _lib.load()
-        s = _stream(dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        old = {f: getattr(m, f) for f in FIELDS}
-        for f, t in old.items():
-            if not t.is_contiguous() or t.dtype != torch.float32 or t.shape[0] != n:
-                raise ValueError(f"{f} must be contiguous float32 with {n} rows")
-        with torch.cuda.device(dev):
-            ws = torch.empty((int(lib.ts_densify_ws_ints(n)),), **i32)
-            counts = torch.empty((4,), **i32)
-            src_of = torch.empty((max(2 * n, 1),), **i32)
-            _call("ts_densify_plan", lib.ts_densify_plan, n, _ptr(flags), _ptr(ws), _ptr(counts),
-                  _ptr(src_of), s)
-            K, C, S, n2 = (int(v) for v in counts.tolist())        # the one host read: sizes the tensors
-            self.last_counts = (K, C, S, n2)
-            extra = 0 if not append else max(t.shape[0] for t in append.values())
-            if K == n and C == 0 and S == 0 and extra == 0:
-                return
-            rows = n2 + extra                 # kept | cloned | split samples | caller-made rows
-            new = {f: torch.empty((rows,) + tuple(old[f].shape[1:]), **f32) for f in FIELDS}
-            live = [f for f in FIELDS if _row_floats(old[f]) > 0]
-            src = {f: old[f].detach() for f in FIELDS}
-            _gather(src, new, live, rows, n2, src_of, dev)
-            if extra:
-                for f in FIELDS:
-                    if f in append:
-                        new[f][n2:].copy_(append[f])
-            n2 = rows
-            if S > 0:
-                if z is None:
-                    z = torch.randn((2 * S, 3), **f32)
-                z = _f32c(z)
-                if z.shape != (2 * S, 3) or z.device != dev:
-                    raise ValueError(f"z must be [{2 * S}, 3] on {dev}")
-                first = K + C
-                _call("ts_split_fixup", lib.ts_split_fixup, 2 * S, src_of[first:].data_ptr(),
-                      _ptr(src["means"]), _ptr(src["scales"]), _ptr(src["quats"]), _ptr(z),
-                      new["means"][first:].data_ptr(), new["scales"][first:].data_ptr(), s)
-            new_m = {f: torch.empty_like(new[f]) for f in FIELDS}
-            new_v = {f: torch.empty_like(new[f]) for f in FIELDS}
-            _gather(optim.exp_avg, new_m, live, n2, K, src_of, dev)
-            _gather(optim.exp_avg_sq, new_v, live, n2, K, src_of, dev)
-            accum = torch.empty((K,), **f32)                        # :242
-            _gather({"a": self.means_grad_accum}, {"a": accum}, ["a"], K, K, src_of, dev)
-        self.means_grad_accum = accum
-        for f in FIELDS:
-            p = new[f].requires_grad_(old[f].requires_grad)
-            setattr(m, f, p)
-            optim.params[f] = p
-            optim.exp_avg[f] = new_m[f]
-            optim.exp_avg_sq[f] = new_v[f]
+        old, live, n, dev = fields_of(m)
+        (K, C, S, n2), src_of = plan(flags, n, dev)
+        self.last_counts = (K, C, S, n2)
+        if K == n and C == 0 and S == 0:
+            return
+        new, new_m, new_v = rebuild(old, live, optim, src_of, n2, n2, K)       # kept | cloned | split samples
+        if S > 0:
+            if z is None:
+                z = torch.randn((2 * S, 3), dtype=torch.float32, device=dev)
+            z = _f32c(z)
+            if z.shape != (2 * S, 3) or z.device != dev:
+                raise ValueError(f"z must be [{2 * S}, 3] on {dev}")
+            first = K + C
+            with torch.cuda.device(dev):
+                _call("ts_split_fixup", _lib.load().ts_split_fixup, 2 * S, src_of[first:].data_ptr(),
+                      _ptr(old["means"]), _ptr(old["scales"]), _ptr(old["quats"]), _ptr(z),
+                      new["means"][first:].data_ptr(), new["scales"][first:].data_ptr(), _stream(dev))
+        self._gather_accum(src_of, K, dev)                              # :242
+        install(m, optim, new, new_m, new_v)

@@ -15,7 +15,6 @@ There is no CPU path: tensors must be on the GPU.  The sharded trainer does not 
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
@@ -24,7 +23,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .densify import FIELDS, Densifier, _gather, _row_floats
+from ._rows import compact, fields_of, hold, install, plan, rebuild, tables
 from .ops import _call, _f32c, _need_hip, _ptr, _stream
 
 N_MAX = 51                      # TS_MCMC_N_MAX
@@ -91,10 +90,7 @@ def _rewrite(opacities: Tensor, scales: Tensor, counts: Tensor, min_opacity: flo
     dev = opacities.device
     n = opacities.shape[0]
     k = 0 if moments is None else len(moments[0])
-    PtrArr, IArr = ctypes.c_void_p * max(k, 1), ctypes.c_int32 * max(k, 1)
-    args = (None, None, None) if k == 0 else (PtrArr(*[t.data_ptr() for t in moments[0]]),
-                                              PtrArr(*[t.data_ptr() for t in moments[1]]),
-                                              IArr(*[_row_floats(t) for t in moments[0]]))
+    args = (None, None, None) if k == 0 else tables(*moments)          # exp_avg, exp_avg_sq, widths
     with torch.cuda.device(dev):
         _call("ts_mcmc_rewrite", _lib.load().ts_mcmc_rewrite, n, _ptr(counts), float(min_opacity), _ptr(opacities),
               _ptr(scales), k, *args, _stream(dev))
@@ -200,14 +196,7 @@ class McmcDensifier:
         self.last_counts = None
         self.last_dead = 0                           # dead rows the last relocation found
         self.last_picks = self.last_pick_counts = self.last_dead_rows = None     # the last draws (for tests)
-        held = getattr(model, "held_by", None)
-        if held is None:
-            try:
-                model.held_by = held = set()
-            except AttributeError:
-                held = None
-        if held is not None:
-            held.add("McmcDensifier")
+        hold(model, "McmcDensifier")
 
     # ---- the hooks
     def update_grad_accum(self, step: int, extras) -> None:
@@ -233,8 +222,8 @@ class McmcDensifier:
 
     @torch.no_grad()
     def update_state(self, optim, mask: Tensor, _tensors=None) -> None:
-        """``Densifier.update_state``: drop the rows where ``mask`` is True, append the caller's rows."""
-        Densifier(self.model).update_state(optim, mask, _tensors)
+        """``Densifier.update_state`` without an accumulator: drop the rows where ``mask`` is True, append the caller's."""
+        compact(self.model, optim, mask, _tensors)
 
     # ---- a refinement
     def _uniforms(self, m: int, u: Optional[Tensor], used: int, dev) -> Tensor:
@@ -246,47 +235,27 @@ class McmcDensifier:
             raise ValueError(f"u must hold at least {used + m} uniforms")
         return _f32c(u[used:used + m].to(dev))
 
-    def _tensors(self, optim):
-        m = self.model
-        old = {f: getattr(m, f) for f in FIELDS}
-        dev = _need_hip(*old.values())
-        n = old["means"].shape[0]
-        for f, t in old.items():
-            if not t.is_contiguous() or t.dtype != torch.float32 or t.shape[0] != n:
-                raise ValueError(f"{f} must be contiguous float32 with {n} rows")
-        live = [f for f in FIELDS if _row_floats(old[f]) > 0]
-        return old, live, n, dev
-
     @torch.no_grad()
     def relocate(self, optim, u: Optional[Tensor] = None, _used: int = 0) -> int:
         """Moves every dead row onto a live row drawn in proportion to opacity -> the number of rows moved (0 when no
         row or every row is dead).  ``self.last_dead`` is the number of dead rows found."""
-        old, live, n, dev = self._tensors(optim)
+        old, live, n, dev = fields_of(self.model)
         lib = _lib.load()
-        s = _stream(dev)
         with torch.cuda.device(dev):
             w = torch.empty((n,), dtype=torch.float64, device=dev)
             flags = torch.empty((n,), dtype=torch.uint8, device=dev)
             _call("ts_mcmc_weights", lib.ts_mcmc_weights, n, _ptr(old["opacities"].detach()), float(self.cfg.min_opacity),
-                  1, _ptr(w), _ptr(flags), s)
-            ws = torch.empty((int(lib.ts_densify_ws_ints(n)),), dtype=torch.int32, device=dev)
-            counts4 = torch.empty((4,), dtype=torch.int32, device=dev)
-            dead_rows = torch.empty((max(2 * n, 1),), dtype=torch.int32, device=dev)
-            _call("ts_densify_plan", lib.ts_densify_plan, n, _ptr(flags), _ptr(ws), _ptr(counts4), _ptr(dead_rows), s)
-            dead = int(counts4[0].item())              # the one host read: sizes the draws
+                  1, _ptr(w), _ptr(flags), _stream(dev))
+        (dead, _, _, _), dead_rows = plan(flags, n, dev)       # the dead rows, ascending; the host read sizes the draws
         self.last_dead = dead
         if dead == 0 or dead == n:
             return 0
-        uu = self._uniforms(dead, u, _used, dev)
-        picks, counts = sample_rows(w, uu)
-        _rewrite(old["opacities"].detach(), old["scales"].detach(), counts, self.cfg.min_opacity,
-                 ([optim.exp_avg[f] for f in live], [optim.exp_avg_sq[f] for f in live]))
-        k = len(live)
-        PtrArr, IArr = ctypes.c_void_p * k, ctypes.c_int32 * k
+        picks, counts = sample_rows(w, self._uniforms(dead, u, _used, dev))
+        moments = [optim.exp_avg[f] for f in live], [optim.exp_avg_sq[f] for f in live]
+        _rewrite(old["opacities"].detach(), old["scales"].detach(), counts, self.cfg.min_opacity, moments)
         with torch.cuda.device(dev):
-            _call("ts_mcmc_copy_rows", lib.ts_mcmc_copy_rows, n, dead, _ptr(dead_rows), _ptr(picks), k,
-                  PtrArr(*[old[f].data_ptr() for f in live]), PtrArr(*[optim.exp_avg[f].data_ptr() for f in live]),
-                  PtrArr(*[optim.exp_avg_sq[f].data_ptr() for f in live]), IArr(*[_row_floats(old[f]) for f in live]), s)
+            _call("ts_mcmc_copy_rows", lib.ts_mcmc_copy_rows, n, dead, _ptr(dead_rows), _ptr(picks), len(live),
+                  *tables([old[f] for f in live], *moments), _stream(dev))
         self.last_picks, self.last_pick_counts, self.last_dead_rows = picks, counts, dead_rows[:dead]
         return dead
 
@@ -294,7 +263,7 @@ class McmcDensifier:
     def add(self, optim, u: Optional[Tensor] = None, _used: int = 0) -> int:
         """Grows the set to ``min(cap_max, N * 105 // 100)`` rows: the new rows are copies of rows drawn over ALL rows in
         proportion to opacity (rewritten first), appended in draw order -> their number.  0: nothing is reallocated."""
-        old, live, n, dev = self._tensors(optim)
+        old, live, n, dev = fields_of(self.model)
         n_new = min(int(self.cfg.cap_max), n * int(self.cfg.grow_percent) // 100) - n
         if n_new <= 0:
             return 0
@@ -307,22 +276,8 @@ class McmcDensifier:
         picks.clamp_(min=0)                            # (every opacity 0 or NaN: no row was drawn; the copies are row 0)
         _rewrite(old["opacities"].detach(), old["scales"].detach(), counts, self.cfg.min_opacity,
                  ([optim.exp_avg[f] for f in live], [optim.exp_avg_sq[f] for f in live]))
-        rows = n + n_new
         src_of = torch.cat((torch.arange(n, dtype=torch.int32, device=dev), picks))
-        f32 = dict(dtype=torch.float32, device=dev)
-        new = {f: torch.empty((rows,) + tuple(old[f].shape[1:]), **f32) for f in FIELDS}
-        new_m = {f: torch.empty_like(new[f]) for f in FIELDS}
-        new_v = {f: torch.empty_like(new[f]) for f in FIELDS}
-        with torch.cuda.device(dev):
-            _gather({f: old[f].detach() for f in FIELDS}, new, live, rows, rows, src_of, dev)
-            _gather(optim.exp_avg, new_m, live, rows, n, src_of, dev)          # the appended rows' moments are zero
-            _gather(optim.exp_avg_sq, new_v, live, rows, n, src_of, dev)
-        for f in FIELDS:
-            p = new[f].requires_grad_(old[f].requires_grad)
-            setattr(self.model, f, p)
-            optim.params[f] = p
-            optim.exp_avg[f] = new_m[f]
-            optim.exp_avg_sq[f] = new_v[f]
+        install(self.model, optim, *rebuild(old, live, optim, src_of, n + n_new, n + n_new, n))   # new rows: zero moments
         self.last_picks, self.last_pick_counts = picks, counts
         return n_new
 

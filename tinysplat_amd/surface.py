@@ -19,6 +19,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._rows import compact, hold
 from .ops import _call, _f32c, _need_hip, _ptr, _stream
 
 
@@ -287,7 +288,6 @@ class SurfaceRegularizer:
         self.config = config if config is not None else SurfaceConfig()
         self.generator = generator
         self.samples: Optional[DensitySamples] = None
-        self._densifier = None
 
     def opacity_active(self, step: int) -> bool:
         c = self.config
@@ -319,25 +319,23 @@ class SurfaceRegularizer:
             return {}
         c = self.config
         if self.samples is None or self.density_update(step) or not self.samples.matches(model):
-            from .training import _hold
             self.samples = sample_points(model, c.density_samples, c.density_sample_weights, self.generator)
-            _hold(model, "SurfaceRegularizer")     # the neighbour indices are per-row state
+            hold(model, "SurfaceRegularizer")      # the neighbour indices are per-row state
         term = density_loss(model, self.samples, extras["depth"], camera, c.density_projection)
         return {"loss_density": (float(c.lambda_density), term)}
 
     @torch.no_grad()
     def after_step(self, model, step: int, optimizer, densifier=None) -> None:
         """train.py:103-105, after Adam and densification: drop the rows with ``sigmoid(opacities) < 0.5`` through
-        ``densifier.update_state`` (a private Densifier without one), which keeps the Adam moments and the gradient
-        accumulator in step."""
+        ``densifier.update_state``, which keeps the Adam moments and the densifier's own rows in step (``_rows.compact``
+        without a densifier: parameters and moments)."""
         if not self.prune_due(step):
             return
-        if densifier is None:
-            if self._densifier is None or self._densifier.model is not model:
-                from .densify import Densifier
-                self._densifier = Densifier(model)
-            densifier = self._densifier
-        densifier.update_state(optimizer, (torch.sigmoid(model.opacities) < 0.5).reshape(-1))
+        mask = (torch.sigmoid(model.opacities) < 0.5).reshape(-1)
+        if densifier is not None:
+            densifier.update_state(optimizer, mask)
+        else:
+            compact(model, optimizer, mask)
 
     def terms(self, model, step: int) -> Dict[str, tuple]:
         out = {}

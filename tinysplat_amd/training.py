@@ -16,6 +16,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._rows import hold, tables
 from .ops import _call, _f32c, _need_hip, _ptr, _stream
 from .scene import Scene
 
@@ -171,19 +172,6 @@ def photometric_loss(image: Tensor, target: Tensor, lambda_dssim: float = 0.2):
     return _PhotometricLoss.apply(image, target, lambda_dssim)
 
 
-def _hold(model, who: str) -> None:
-    """Marks a model as having per-row state kept elsewhere (Adam moments, gradient accumulator): the in-place
-    reorder of a FRESH model, SplatModel.spatial_sort_, refuses such a model."""
-    held = getattr(model, "held_by", None)
-    if held is None:
-        held = set()
-        try:
-            model.held_by = held
-        except AttributeError:          # a foreign model class with __slots__: nothing to mark
-            return
-    held.add(who)
-
-
 class Adam:
     """torch.optim.Adam (defaults) over the six parameter tensors, one HIP launch per step."""
 
@@ -204,31 +192,24 @@ class Adam:
 
     @torch.no_grad()
     def step(self) -> None:
-        names = [n for n in self.names if self.params[n].grad is not None]
-        if not names:
-            return
+        with_grad = [n for n in self.names if self.params[n].grad is not None]
+        names = [n for n in with_grad if self.params[n].numel() > 0]   # (colors_rest of an SH-0 model: nothing to update)
         ps = [self.params[n] for n in names]
-        dev = _need_hip(*ps)
-        gs = [_f32c(self.params[n].grad) for n in names]
         for p in ps:
             if not p.is_contiguous() or p.dtype != torch.float32:
                 raise ValueError("Adam parameters must be contiguous float32")
-        for n in names:
+        gs = [_f32c(p.grad) for p in ps]
+        for n in with_grad:
             self.steps[n] += 1
-        names = [n for n in names if self.params[n].numel() > 0]       # (colors_rest of an SH-0 model: nothing to update)
-        ps = [self.params[n] for n in names]
-        gs = [_f32c(self.params[n].grad) for n in names]
+        if not names:
+            return
+        dev = _need_hip(*ps)
         k = len(names)
-        PtrArr, LArr, FArr = ctypes.c_void_p * k, ctypes.c_int64 * k, ctypes.c_float * k
-        IArr = ctypes.c_int32 * k
-        lib = _lib.load()
+        pp, gp, mp, vp, _ = tables(ps, gs, [self.exp_avg[n] for n in names], [self.exp_avg_sq[n] for n in names])
         with torch.cuda.device(dev):
-            _call("ts_adam_step", lib.ts_adam_step, k, PtrArr(*[p.data_ptr() for p in ps]),
-                  PtrArr(*[g.data_ptr() for g in gs]),
-                  PtrArr(*[self.exp_avg[n].data_ptr() for n in names]),
-                  PtrArr(*[self.exp_avg_sq[n].data_ptr() for n in names]),
-                  LArr(*[p.numel() for p in ps]), FArr(*[self.lrs.get(n, 1e-3) for n in names]),
-                  IArr(*[self.steps[n] for n in names]), self.betas[0], self.betas[1], self.eps,
+            _call("ts_adam_step", _lib.load().ts_adam_step, k, pp, gp, mp, vp, (ctypes.c_int64 * k)(*[p.numel() for p in ps]),
+                  (ctypes.c_float * k)(*[self.lrs.get(n, 1e-3) for n in names]),
+                  (ctypes.c_int32 * k)(*[self.steps[n] for n in names]), self.betas[0], self.betas[1], self.eps,
                   _stream(dev))
 
     def zero_grad(self) -> None:
@@ -279,7 +260,7 @@ class TrainStep:
         # update, bit for bit: tests/test_gpu_training.py) and no parameter gradient tensor is written - model.<p>.grad
         # stays None, extras['xys'].grad is set as always.  False: backward, then one ts_adam_step launch.
         self.fused_adam = bool(fused_adam)
-        _hold(model, "TrainStep")        # per-row state now exists outside the model: see SplatModel.spatial_sort_
+        hold(model, "TrainStep")       # per-row state now exists outside the model: see SplatModel.spatial_sort_
 
     def __call__(self, camera, target_rgb: Tensor, target_depth: Optional[Tensor] = None,
                  densifier=None, step: Optional[int] = None, surface=None, appearance=None, view: Optional[int] = None):
