@@ -1281,6 +1281,29 @@ int64_t ts_affine_fit_ws_bytes(int32_t height, int32_t width);
 int ts_affine_fit_sums(int32_t height, int32_t width, const float* image, const void* target, int32_t target_is_u8,
                        void* ws, double* out22, void* stream);
 
+/* ========================================= scene editing ====================================== */
+/* DESIGN.md section 6t; the arithmetic is csrc/transform_math.h's, plain float32 with every product and sum rounded on its
+ * own, and the results are the bits of that header's host build.  The similarity x' = s R x + t arrives as host arrays that
+ * are read inside the call and travel as kernel arguments: no upload, no allocation, no synchronisation.
+ * ts_transform_gaussians: means_out <- M m + t, scales_out <- scales + log_scale, quats_out <- r (x) q (Hamilton product,
+ * w x y z, the norm of q kept, no sign rule), colors_rest_out <- D_l c_l per stored band and colour channel; colors_dc and
+ * opacities do not change and are not arguments.  xform_host: 12 floats, M = fl32(s R) row-major, then fl32(t).
+ * quat_host: 4 floats, the unit quaternion r of R.  log_scale: fl32(log s).  sh_host: D_1 (9) | D_2 (25) | D_3 (49) |
+ * D_4 (81), row-major, as many bands as k_rest needs (NULL where k_rest == 0); D_l is defined by sum_j Y_lj(d) D_l[j,k] =
+ * Y_lk(R^T d) in the basis of ts_sh_fwd.  k_rest: 0, 3, 8, 15 or 24 coefficients per channel, colors_rest [n, k_rest, 3]
+ * (may be NULL where k_rest == 0).  mask: uint8 [n] on the device or NULL; a row whose byte is 0 is copied.  Each *_out
+ * pointer may equal its input pointer; any other overlap is the caller's error.  One launch, no atomics, the same bits on
+ * every run.  n == 0: returns 0, launches nothing.  TS_E_BADARG before any launch: n < 0, another k_rest, a NULL required
+ * pointer with n > 0, a non-finite entry in a host array.
+ * ts_box_mask: inside[i] (uint8) <- 1 where |A m_i + b|_k <= 1 for k = 0, 1, 2, else 0 (a NaN mean is outside).  box_host:
+ * 12 floats, A (3x3 row-major) then b; for a box of centre c, half extents h and axes R_box: A = diag(1/h) R_box^T,
+ * b = -A c.  n == 0: returns 0.  TS_E_BADARG: n < 0; with n > 0 a NULL pointer or a non-finite entry of box_host. */
+int ts_transform_gaussians(int32_t n, int32_t k_rest, const float* xform_host, const float* quat_host, float log_scale,
+                           const float* sh_host, const uint8_t* mask, const float* means, const float* scales,
+                           const float* quats, const float* colors_rest, float* means_out, float* scales_out,
+                           float* quats_out, float* colors_rest_out, void* stream);
+int ts_box_mask(int32_t n, const float* box_host, const float* means, uint8_t* inside, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

@@ -16,6 +16,8 @@ from .mcmc import (ExponentialLr, McmcConfig, McmcDensifier, inject_noise, mcmc_
                    relocation, sample_rows)
 from .metrics import EvalResult, Evaluator, affine_color_fit, evaluate, holdout_split, image_metrics
 from .appearance import AppearanceConfig, AppearanceModel
+from .edit import (Sim3, box_mask, crop_gaussians, merge_models, orient_from_cameras, sh_rotation_matrices,
+                   transform_camera, transform_cameras, transform_gaussians, transform_points)
 from .fusion import FusionConfig, extract_mesh_tsdf, fuse_depth_maps, render_depth_alpha
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
 from .rasterizer import GaussianRasterizer
@@ -37,4 +39,6 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "sparse_depth", "FusionConfig", "fuse_depth_maps", "render_depth_alpha", "extract_mesh_tsdf", "SemanticMaps",
            "LiftResult", "lift_labels", "labels_from_votes", "gaussian_contributions", "select_gaussians", "render_labels",
            "label_iou", "McmcConfig", "McmcDensifier", "ExponentialLr", "sample_rows", "relocation", "inject_noise",
-           "mcmc_normals", "mean_opacity", "mean_scale", "AppearanceConfig", "AppearanceModel", "affine_color_fit"]
+           "mcmc_normals", "mean_opacity", "mean_scale", "AppearanceConfig", "AppearanceModel", "affine_color_fit", "Sim3",
+           "sh_rotation_matrices", "transform_gaussians", "transform_camera", "transform_cameras", "transform_points",
+           "orient_from_cameras", "box_mask", "crop_gaussians", "merge_models"]

@@ -76,6 +76,10 @@ SOURCES = [
     # rounds every product and sum of the nested lerps on its own (an fma would also break "a constant grid returns its
     # constant"), and the double sums of the total variation and the fit are compared with the host build bit for bit
     ("appearance.hip", ["-ffp-contract=off"]),
+    # transform.hip: a transformed mean, quaternion and SH coefficient are defined as the bits of the host build of
+    # transform_math.h, sums of separately rounded products in a fixed order; an fma would also keep an identity transform
+    # from returning its input
+    ("transform.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -298,6 +298,9 @@ SIGNATURES = {
     "ts_grid_tv": (c_int32, [c_int32, c_int32, c_int32, _P, c_float, _P, _P, _P, _P]),
     "ts_affine_fit_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ts_affine_fit_sums": (c_int32, [c_int32, c_int32, _P, _P, c_int32, _P, _P, _P]),
+    "ts_transform_gaussians": (c_int32, [c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_float, POINTER(c_float),
+                                         _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ts_box_mask": (c_int32, [c_int32, POINTER(c_float), _P, _P, _P]),
 }
 
 _lib = None

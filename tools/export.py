@@ -23,7 +23,15 @@ and meshes that (``extract_mesh_tsdf``: any scene that renders good depth; no ve
 ``D/<image name>.npy`` (``semantic.SemanticMaps``) of the dataset's cameras are lifted onto the Gaussians
 (``lift_labels``, all ``--semantic-classes`` classes voting) and only the Gaussians whose class is one of
 ``--keep-classes a,b,...`` - or all but those of ``--drop-classes a,b,...``, unlabelled ones included - are exported; ``--min-share S`` leaves a Gaussian unlabelled whose top class has less than
-that share of its votes.  Needs a GPU: there is no CPU path.
+that share of its votes.
+
+``--rotate w,x,y,z``, ``--translate x,y,z`` and ``--scale s`` together form one similarity ``x' = s R x + t`` that moves
+the scene (``edit.transform_gaussians``: means, scales, rotations and the spherical harmonics of every band);
+``--orient-cameras`` (with ``--dataset-dir``) first turns the cameras' mean up direction to +z, centres them and scales
+the farthest one to distance 1 (``edit.orient_from_cameras``), and the manual similarity is applied after it.
+``--crop-box cx,cy,cz,hx,hy,hz`` keeps the Gaussians whose mean is inside the axis-aligned box of that centre and those
+half extents in the NEW frame.  Order: class cut, transform, crop, export; ``--mesher tsdf`` renders from the cameras moved
+with the scene.  Needs a GPU: there is no CPU path.
 """
 import argparse
 import sys
@@ -54,6 +62,13 @@ def parse(argv=None):
     ap.add_argument("--keep-classes", type=class_list, default=None, help="a,b,...: export the Gaussians of these classes")
     ap.add_argument("--drop-classes", type=class_list, default=None, help="a,b,...: export all but these classes")
     ap.add_argument("--min-share", type=float, default=0.0, help="least share of a Gaussian's votes its class must have")
+    ap.add_argument("--rotate", type=float_list(4), default=None, help="w,x,y,z: rotate the scene by this quaternion")
+    ap.add_argument("--translate", type=float_list(3), default=None, help="x,y,z: move the scene (after rotation and scale)")
+    ap.add_argument("--scale", type=float, default=None, help="scale the scene about the origin")
+    ap.add_argument("--orient-cameras", action="store_true",
+                    help="z up, centred and unit-sized by the cameras of --dataset-dir, before the manual transform")
+    ap.add_argument("--crop-box", type=float_list(6), default=None,
+                    help="cx,cy,cz,hx,hy,hz: keep the Gaussians inside this axis-aligned box of the new frame")
     args = ap.parse_args(argv)
     mesh = args.filetype in ("OBJ", "MESH_PLY")
     if args.limit is not None and args.filetype != "SPLAT":
@@ -77,8 +92,16 @@ def parse(argv=None):
     for c in (args.keep_classes or []) + (args.drop_classes or []):
         if not 0 <= c < args.semantic_classes:
             ap.error(f"class {c} is outside [0, {args.semantic_classes})")
-    if (args.mesher == "tsdf" or args.semantic_dir is not None) != (args.dataset_dir is not None):
+    if args.orient_cameras and args.dataset_dir is None:
+        ap.error("--orient-cameras needs --dataset-dir")
+    if (args.mesher == "tsdf" or args.semantic_dir is not None or args.orient_cameras) != (args.dataset_dir is not None):
         ap.error("--dataset-dir goes with --mesher tsdf or --semantic-dir")
+    if args.scale is not None and not (args.scale > 0 and args.scale < float("inf")):
+        ap.error("--scale must be positive and finite")
+    if args.rotate is not None and not sum(v * v for v in args.rotate) > 0:
+        ap.error("--rotate needs a quaternion that is not zero")
+    if args.crop_box is not None and not all(h > 0 for h in args.crop_box[3:]):
+        ap.error("--crop-box needs half extents > 0")
     if args.mesher == "tsdf" and args.colors:
         ap.error("--colors goes with --mesher density")
     return args
@@ -93,6 +116,34 @@ def class_list(text):
     if len(set(ids)) != len(ids):
         raise argparse.ArgumentTypeError(f"{text!r}: a class is named twice")
     return ids
+
+
+def float_list(count):
+    """'a,b,...' -> [a, b, ...], exactly ``count`` finite numbers."""
+    def parse_list(text):
+        try:
+            values = [float(t) for t in text.split(",")]
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"{text!r}: {count} comma-separated numbers expected")
+        if len(values) != count or not all(v == v and abs(v) != float("inf") for v in values):
+            raise argparse.ArgumentTypeError(f"{text!r}: {count} comma-separated finite numbers expected")
+        return values
+    return parse_list
+
+
+def scene_transform(args, cameras=None):
+    """The similarity of --orient-cameras (first) and --rotate / --translate / --scale (after it), or None."""
+    from tinysplat_amd.edit import Sim3, orient_from_cameras
+    manual = args.rotate is not None or args.translate is not None or args.scale is not None
+    if not manual and not args.orient_cameras:
+        return None
+    t = Sim3.identity()
+    if args.orient_cameras:
+        t = orient_from_cameras(cameras)
+    if manual:
+        t = Sim3.from_quat(args.rotate or (1.0, 0.0, 0.0, 0.0), args.translate or (0.0, 0.0, 0.0),
+                           1.0 if args.scale is None else args.scale) @ t
+    return t
 
 
 def cut_by_class(model, cameras, args):
@@ -138,8 +189,20 @@ def main(argv=None):
         raise SystemExit("no GPU: tinysplat_amd has no CPU path")
     from tinysplat_amd import MeshConfig, extract_mesh, formats
     model = load_model(args.input_file, args.device)
+    cameras = dataset_cameras(args.dataset_dir, args.colmap_path) if args.dataset_dir is not None else None
     if args.semantic_dir is not None:
-        model = cut_by_class(model, dataset_cameras(args.dataset_dir, args.colmap_path), args)
+        model = cut_by_class(model, cameras, args)
+    transform = scene_transform(args, cameras)
+    if transform is not None:
+        from tinysplat_amd.edit import transform_cameras, transform_gaussians
+        model = transform_gaussians(model, transform)
+        cameras = transform_cameras(cameras, transform) if cameras is not None else None
+        print("scene transform:\n" + "\n".join(" ".join(f"{v: .9g}" for v in row) for row in transform.matrix()))
+    if args.crop_box is not None:
+        from tinysplat_amd.edit import crop_gaussians
+        before = model.num_points
+        model = crop_gaussians(model, args.crop_box[:3], args.crop_box[3:])
+        print(f"--crop-box keeps {model.num_points} of {before} Gaussians")
     if args.filetype == "PLY":
         formats.export_ply(model, args.output_file)
     elif args.filetype == "SPLAT":
@@ -148,7 +211,6 @@ def main(argv=None):
         res = {} if args.resolution is None else {"resolution": args.resolution}
         if args.mesher == "tsdf":
             from tinysplat_amd import FusionConfig, extract_mesh_tsdf
-            cameras = dataset_cameras(args.dataset_dir, args.colmap_path)
             mesh = extract_mesh_tsdf(model, cameras, FusionConfig(target_faces=args.target_faces, **res), args.device)
         else:
             mesh = extract_mesh(model, MeshConfig(colors=args.colors, target_faces=args.target_faces, **res))

@@ -118,6 +118,20 @@ def appearance_config(args):
     return AppearanceConfig(grid=grid, lr=args.appearance_lr, tv_weight=args.appearance_tv)
 
 
+def _frame_parser():
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    g = ap.add_argument_group("scene frame")
+    g.add_argument("--normalize-scene", action="store_true",
+                   help="train in a frame with z up, the cameras centred and the farthest one at distance 1 "
+                        "(edit.orient_from_cameras); the transform is printed as a 4x4 matrix")
+    return ap
+
+
+def parse_frame(argv=None):
+    """The scene frame's option, a namespace of its own like the depth prior's."""
+    return _frame_parser().parse_known_args(argv)[0]
+
+
 def parse(argv=None):
     depth_ap, strategy_ap, appearance_ap = _depth_parser(), _strategy_parser(), _appearance_parser()
     parse_depth(argv)                                          # checks the depth prior's options
@@ -126,10 +140,12 @@ def parse(argv=None):
     _depth, argv = depth_ap.parse_known_args(argv)
     _strategy, argv = strategy_ap.parse_known_args(argv)
     _appearance, argv = appearance_ap.parse_known_args(argv)
+    _frame, argv = _frame_parser().parse_known_args(argv)
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter,
                                  epilog=depth_ap.format_help().split("\n\n", 1)[-1] + "\n" +
                                  strategy_ap.format_help().split("\n\n", 1)[-1] + "\n" +
-                                 appearance_ap.format_help().split("\n\n", 1)[-1])
+                                 appearance_ap.format_help().split("\n\n", 1)[-1] + "\n" +
+                                 _frame_parser().format_help().split("\n\n", 1)[-1])
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--max-iter", type=int, default=10_000)
@@ -161,6 +177,17 @@ def parse(argv=None):
     return args
 
 
+def normalize_scene(dataset):
+    """Moves the dataset's cameras and point cloud into the frame of ``orient_from_cameras`` and prints the transform."""
+    from tinysplat_amd.edit import orient_from_cameras, transform_cameras, transform_points
+    t = orient_from_cameras(dataset.cameras)
+    dataset.cameras = transform_cameras(dataset.cameras, t)
+    dataset.pcd.xyz = transform_points(dataset.pcd.xyz, t)
+    dataset.spatial_extent *= t.scale
+    print("scene transform:\n" + "\n".join(" ".join(f"{v: .9g}" for v in row) for row in t.matrix()))
+    return t
+
+
 def main(argv=None):
     args, depth, strategy, look = parse(argv), parse_depth(argv), parse_strategy(argv), parse_appearance(argv)
     import torch
@@ -174,6 +201,8 @@ def main(argv=None):
                       device=args.device, principal_point=args.principal_point)
     print(f"{len(dataset.cameras)} cameras ({sum(dataset.resampled)} resampled), {dataset.pcd.xyz.shape[0]} points, "
           f"extent {dataset.spatial_extent:.3f}")
+    if parse_frame(argv).normalize_scene:
+        normalize_scene(dataset)
     model = from_pcd(dataset.pcd, sh_degree=args.sh_degree, device=args.device)
     cameras, targets, evaluator, corrected = dataset.cameras, dataset.targets, None, None
     depth_targets = depth_schedule = None
