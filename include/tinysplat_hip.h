@@ -1304,6 +1304,21 @@ int ts_transform_gaussians(int32_t n, int32_t k_rest, const float* xform_host, c
                            float* quats_out, float* colors_rest_out, void* stream);
 int ts_box_mask(int32_t n, const float* box_host, const float* means, uint8_t* inside, void* stream);
 
+/* ======================================== camera pose gradient ================================ */
+/* DESIGN.md section 6u; the arithmetic and the order of the sum are csrc/pose_math.h's, and the result is the bits of that
+ * header's host build.  ts_pose_grad: out6 (double, device) <- (dL/dv [3], dL/domega [3]) at delta = 0 of the left
+ * perturbation V(delta) = Exp(delta) V of the view matrix V = [R | t], from means [n, 3], quats [n, 4] (raw, w x y z) and
+ * the gradient rows v_means [n, 3] = dL/dmeans, v_quats [n, 4] = dL/dquats of a backward pass through a frame rendered
+ * with V (float32, device).  view34_host: the 12 floats of V's first three rows, row-major, on the host; read inside
+ * the call and passed as a kernel argument.  R must be orthonormal for the result to be the pose gradient.  Every product
+ * and sum is a double operation; the rows are added in an order that depends on n alone, without atomics: the same 48
+ * bytes on every run, stream and workspace.  Two launches.  ws: >= ts_pose_ws_bytes(n) bytes (48 per 1024 rows), 8-byte
+ * aligned like out6.  n == 0: out6 <- six zeros (the row pointers and ws may be NULL).  TS_E_BADARG before any launch:
+ * n < 0, a NULL view34_host or out6, with n > 0 a NULL row pointer or ws, a misaligned pointer. */
+int64_t ts_pose_ws_bytes(int32_t n);
+int ts_pose_grad(int32_t n, const float* view34_host, const float* means, const float* quats, const float* v_means,
+                 const float* v_quats, void* ws, double* out6, void* stream);
+
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark
  * that SURVEY.md 8(d) D1 asks the roofline to be quoted against as well.  sink: >= 1 float. */

@@ -20,6 +20,7 @@ from .edit import (Sim3, box_mask, crop_gaussians, merge_models, orient_from_cam
                    transform_camera, transform_cameras, transform_gaussians, transform_points)
 from .fusion import FusionConfig, extract_mesh_tsdf, fuse_depth_maps, render_depth_alpha
 from .init import PointCloud, from_pcd, knn_points, read_point_cloud_ply
+from .pose import PoseConfig, PoseModel, pose_gradient, refine_pose, se3_exp, se3_log
 from .rasterizer import GaussianRasterizer
 from .scene import Scene
 from .semantic import (LiftResult, SemanticMaps, gaussian_contributions, label_iou, labels_from_votes, lift_labels,
@@ -41,4 +42,5 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "label_iou", "McmcConfig", "McmcDensifier", "ExponentialLr", "sample_rows", "relocation", "inject_noise",
            "mcmc_normals", "mean_opacity", "mean_scale", "AppearanceConfig", "AppearanceModel", "affine_color_fit", "Sim3",
            "sh_rotation_matrices", "transform_gaussians", "transform_camera", "transform_cameras", "transform_points",
-           "orient_from_cameras", "box_mask", "crop_gaussians", "merge_models"]
+           "orient_from_cameras", "box_mask", "crop_gaussians", "merge_models", "PoseConfig", "PoseModel", "pose_gradient",
+           "refine_pose", "se3_exp", "se3_log"]

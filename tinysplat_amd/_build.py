@@ -80,6 +80,9 @@ SOURCES = [
     # transform_math.h, sums of separately rounded products in a fixed order; an fma would also keep an identity transform
     # from returning its input
     ("transform.hip", ["-ffp-contract=off"]),
+    # pose.hip: a row's six terms and the sums over the rows are defined as the bits of the host build of pose_math.h,
+    # double products and sums each rounded on its own in a fixed order; an fma would make the two builds two functions
+    ("pose.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

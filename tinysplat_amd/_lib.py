@@ -301,6 +301,8 @@ SIGNATURES = {
     "ts_transform_gaussians": (c_int32, [c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_float, POINTER(c_float),
                                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ts_box_mask": (c_int32, [c_int32, POINTER(c_float), _P, _P, _P]),
+    "ts_pose_ws_bytes": (c_int64, [c_int32]),
+    "ts_pose_grad": (c_int32, [c_int32, POINTER(c_float), _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -140,7 +140,8 @@ def _target(targets, i: int) -> Tensor:
 
 
 @torch.no_grad()
-def evaluate(model, cameras: Sequence, targets, device, background=None, color_correct: bool = False) -> EvalResult:
+def evaluate(model, cameras: Sequence, targets, device, background=None, color_correct: bool = False,
+             refine_poses: int = 0, pose_config=None) -> EvalResult:
     """Renders every camera forward-only (``frame.render_view``, the viewer's path: its image is the training forward's
     bit for bit) on a fixed background - black unless given, the reference model's ``torch.zeros(3)``; the training loop
     draws a random one per step - and measures it against ``targets[i]`` (a ``dataset.Targets``, whose uint8 images are
@@ -148,7 +149,10 @@ def evaluate(model, cameras: Sequence, targets, device, background=None, color_c
     the only device-to-host copy comes after the last view has been enqueued.  The model is left as found: background,
     SH degree, requires_grad flags, no .grad; no random number is drawn.  ``color_correct``: held-out views have no
     colour grid (appearance.py), so each render is first mapped by its own least-squares affine fit to its target
-    (``color_corrected``) and then measured; False, the default: the render is measured as it is."""
+    (``color_corrected``) and then measured; False, the default: the render is measured as it is.
+    ``refine_poses``: after pose training the scene has drifted against the held-out cameras, so each view is first
+    aligned to its target by that many steps of ``pose.refine_pose`` (Gaussians frozen, the model untouched bit for bit;
+    ``pose_config``: its ``PoseConfig``) and measured from the aligned camera; 0, the default: the cameras as given."""
     from .rasterizer import GaussianRasterizer
     dev = torch.device(device)
     cameras = list(cameras)
@@ -161,6 +165,11 @@ def evaluate(model, cameras: Sequence, targets, device, background=None, color_c
                         else torch.as_tensor(background, dtype=torch.float32).to(dev))
     try:
         for i, camera in enumerate(cameras):
+            if int(refine_poses) > 0:
+                from .pose import refine_pose
+                camera, _history = refine_pose(model, camera, _target(targets, i), dev, steps=int(refine_poses),
+                                               config=pose_config, appearance_fit=color_correct,
+                                               background=model.background)
             image, _extras = render(camera, None, model.active_sh_degree)
             if color_correct:
                 image = color_corrected(image, _target(targets, i))
@@ -189,16 +198,19 @@ class Evaluator:
     ``step % every == 0``, and on demand through ``final(step)``.  ``rows`` keeps (step, N, psnr, ssim, l1) - the
     reference's table line (scripts/train.py:142-149) with held-out means, N the number of Gaussians; ``results`` the
     ``EvalResult`` behind each row.  Every row is handed to ``on_result(row, result)`` if given and appended to
-    ``csv_path`` if given (the header is written when the file is created)."""
+    ``csv_path`` if given (the header is written when the file is created).  ``refine_poses`` / ``pose_config``: as
+    ``evaluate``'s - every view is aligned to its image first, which leaves the model untouched, so training with the
+    evaluator attached stays what it is without."""
     HEADER = ("step", "n", "psnr", "ssim", "l1")
 
     def __init__(self, model, cameras, targets, device, every: int, on_result: Optional[Callable] = None,
-                 csv_path=None, background=None, color_correct: bool = False):
+                 csv_path=None, background=None, color_correct: bool = False, refine_poses: int = 0, pose_config=None):
         if int(every) < 0:
             raise ValueError("Evaluator: every must not be negative (0: only final())")
         self.model, self.cameras, self.targets, self.device = model, list(cameras), targets, device
         self.every, self.on_result, self.background = int(every), on_result, background
         self.color_correct = bool(color_correct)
+        self.refine_poses, self.pose_config = int(refine_poses), pose_config
         self.csv_path = None if csv_path is None else Path(csv_path)
         self.rows: List[tuple] = []
         self.results: List[EvalResult] = []
@@ -212,7 +224,9 @@ class Evaluator:
 
     def _evaluate(self, step: int):
         result = evaluate(self.model, self.cameras, self.targets, self.device, self.background,
-                          **({"color_correct": True} if self.color_correct else {}))
+                          **({"color_correct": True} if self.color_correct else {}),
+                          **({"refine_poses": self.refine_poses, "pose_config": self.pose_config}
+                             if self.refine_poses > 0 else {}))
         row = (int(step), int(self.model.means.shape[0]), result.psnr, result.ssim, result.l1)
         self.rows.append(row)
         self.results.append(result)

@@ -263,7 +263,8 @@ class TrainStep:
         hold(model, "TrainStep")       # per-row state now exists outside the model: see SplatModel.spatial_sort_
 
     def __call__(self, camera, target_rgb: Tensor, target_depth: Optional[Tensor] = None,
-                 densifier=None, step: Optional[int] = None, surface=None, appearance=None, view: Optional[int] = None):
+                 densifier=None, step: Optional[int] = None, surface=None, appearance=None, view: Optional[int] = None,
+                 poses=None):
         """``densifier`` (densify.Densifier) + ``step`` add train.py:99-102 after the Adam update:
         gradient accumulation and, on the policy's steps, clone / split / prune.  A densifier with a ``loss_terms(model,
         step)`` method (mcmc.McmcDensifier) adds its terms to the loss as ``surface`` does.
@@ -275,9 +276,21 @@ class TrainStep:
         ``appearance`` (appearance.AppearanceModel) + ``view`` (the camera's index among the training views) put the
         view's colour grid between the render and the loss: the loss reads ``appearance.apply(rgb, view)``, the backward
         pass goes through it into the frame, and ``appearance.step(view)`` updates the view's grid after it; ``out`` gains
-        ``appearance_tv``.  The fused in-backward Adam of the Gaussians stays on.  None: the step is exactly today's."""
+        ``appearance_tv``.  The fused in-backward Adam of the Gaussians stays on.  None: the step is exactly today's.
+        ``poses`` (pose.PoseModel) + ``view`` render ``poses.camera(view)`` in place of ``camera`` and refine that view's
+        pose: the backward pass writes the gradient tensors (the two-launch Adam: the fused update
+        keeps no rows to reduce), ``ts_pose_grad`` reduces the rows of means and quats before Adam moves them, and
+        ``poses.step(view, g)`` follows; ``out`` gains ``pose_grad``.  A SuGaR density term active at ``step`` is refused:
+        its gradient on the means did not come through the camera.  None: the step is exactly today's."""
         if appearance is not None and view is None:
             raise ValueError("appearance needs the index of the rendered view")
+        if poses is not None:
+            if view is None:
+                raise ValueError("poses needs the index of the rendered view")
+            if surface is not None and step is not None and surface.density_active(step):
+                raise ValueError("poses cannot be refined while the SuGaR density term is active: it puts gradient on the "
+                                 "means that did not come through the camera and would enter the pose gradient")
+            camera = poses.camera(view)
         terms = {}
         if surface is not None:
             if step is None:
@@ -327,7 +340,8 @@ class TrainStep:
             loss = loss + extra
         # `direct`: the loss launches already produced dloss / d(rgb, depth) - they go straight into the frame's backward
         run_backward = (lambda: torch.autograd.backward(*direct)) if direct is not None else loss.backward
-        if self.fused_adam and not terms:
+        pose_grad = None
+        if self.fused_adam and not terms and poses is None:
             from .frame import fused_adam
             with fused_adam(self.optimizer):
                 run_backward()
@@ -335,7 +349,12 @@ class TrainStep:
                 self.optimizer.step()
         else:
             run_backward()
+            if poses is not None:                              # the rows of this frame, before Adam moves means and quats
+                from .pose import pose_gradient
+                pose_grad = pose_gradient(self.model, camera)
             self.optimizer.step()
+        if poses is not None:
+            poses.step(view, pose_grad)
         appearance_tv = None if appearance is None else appearance.step(view)
         xys_grad = extras["xys"].grad                          # consumed by densification (F2)
         if densifier is not None:
@@ -353,6 +372,8 @@ class TrainStep:
             out[name] = term.detach()
         if appearance_tv is not None:
             out["appearance_tv"] = appearance_tv
+        if pose_grad is not None:
+            out["pose_grad"] = pose_grad
         return out
 
 
@@ -390,7 +411,7 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
         sh_increment_interval: int = 500, max_sh_degree: int = 3, lambda_dssim: float = 0.2,
         lambda_depth: float = 0.2, depth_schedule: Optional[Scheduler] = None, densifier=None,
         lrs: Optional[Dict[str, float]] = None, rng=None, generator: Optional[torch.Generator] = None,
-        on_step=None, surface=None, lr_schedule=None, appearance=None):
+        on_step=None, surface=None, lr_schedule=None, appearance=None, poses=None):
     """The training loop of scripts/train.py:45-106 (steps 1-7) on in-memory cameras / targets:
     SH degree schedule (:49-50, model_gaussian.py:126-128), random background (:51), camera pick
     (:54), render + loss (:55-69), the opacity-entropy (:71-75) and SuGaR density (:77-91)
@@ -401,7 +422,10 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
     rates are written into ``Adam.lrs`` before the step (``mcmc.ExponentialLr``: the reference's ``update_learning_rate``
     TODO, model_gaussian.py:122-124); None, the default: the rates stay constant.  ``appearance``: an
     ``appearance.AppearanceConfig`` (a model with one grid per camera is made from it) or an ``AppearanceModel``: every
-    step goes through the picked camera's colour grid; None, the default: no colour model."""
+    step goes through the picked camera's colour grid; None, the default: no colour model.
+    ``poses``: a ``pose.PoseConfig`` (a ``PoseModel`` over ``cameras`` is made from it) or a ``PoseModel``: every step
+    renders the picked view's refined camera and updates its pose; not together with a SuGaR
+    density window that opens within ``max_iter``; None, the default: the cameras are taken as exact."""
     dev = torch.device(device)
     scene = Scene(cameras, model, device=dev, rng=rng)
     step_fn = TrainStep(model, dev, lambda_dssim, lambda_depth, lrs, scene=scene)
@@ -414,6 +438,18 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
             appearance = AppearanceModel(len(cameras), appearance, dev)
         if appearance.num_views != len(cameras):
             raise ValueError(f"the appearance model has {appearance.num_views} views, the run {len(cameras)} cameras")
+    if poses is not None:
+        from .pose import PoseConfig, PoseModel
+        if isinstance(poses, PoseConfig):
+            poses = PoseModel(cameras, poses)
+        if poses.num_views != len(cameras):
+            raise ValueError(f"the pose model has {poses.num_views} views, the run {len(cameras)} cameras")
+        sc = None if surface is None else surface.config
+        if sc is not None and sc.regularize_density and max(1, sc.regularize_density_start) < min(int(max_iter) + 1, sc.regularize_density_end):
+            raise ValueError("poses cannot be refined in a run whose SuGaR density term becomes active: it puts gradient "
+                             "on the means that did not come through the camera")
+    # what a step takes beside the index of its view; empty: the step is called as it always was
+    per_view = {k: v for k, v in (("appearance", appearance), ("poses", poses)) if v is not None}
     pick = scene._sampler
     out = None
     for step in range(1, int(max_iter) + 1):
@@ -427,7 +463,7 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
             step_fn.optimizer.lrs.update(lr_schedule(step))
         out = step_fn(cameras[i], targets[i], depth_targets[i] if use_depth else None,
                       densifier=densifier, step=step, surface=surface,
-                      **({} if appearance is None else dict(appearance=appearance, view=i)))
+                      **per_view, **({} if not per_view else dict(view=i)))
         if on_step is not None:
             on_step(step, out)
     return out

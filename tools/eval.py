@@ -12,7 +12,11 @@ is the training loss's (pytorch_msssim: valid filtering), not the zero-padded SS
 (``semantic.lift_labels``), renders the labels at the evaluated views and prints their mean IoU against those views'
 maps.  ``--color-correct`` first maps every render to its target by a least-squares affine colour fit (3x4, per view) and
 measures the result: the numbers to quote for a scene trained with ``tools/train.py --appearance``, whose held-out views
-have no colour transform of their own.  Needs a GPU: there is no CPU path.
+have no colour transform of their own.  ``--refine-poses K`` first aligns every evaluated view to its image by K pose steps with
+the Gaussians frozen (``pose.refine_pose``): the numbers to quote for a scene trained with ``tools/train.py --optimize-poses``,
+which has drifted against the held-out cameras.  ``--poses poses.pth`` puts the corrections that run saved onto the cameras
+they were trained on (all cameras, or those ``--holdout`` leaves for training) before anything is rendered from them.  Needs
+a GPU: there is no CPU path.
 """
 import argparse
 import csv
@@ -40,6 +44,9 @@ def parse(argv=None):
     ap.add_argument("--csv", type=str, default=None, help="write the per-view table and the means to this CSV file")
     ap.add_argument("--color-correct", action="store_true",
                     help="measure every render after its least-squares affine colour fit to the target")
+    ap.add_argument("--refine-poses", type=int, default=0, metavar="K",
+                    help="align every evaluated view to its image by K pose steps before it is measured")
+    ap.add_argument("--poses", type=str, default=None, help="pose corrections saved by tools/train.py --poses-out")
     ap.add_argument("--semantic-dir", type=str, default=None,
                     help="label maps <image name>.npy: also print the mIoU of the rendered labels on the evaluated views")
     ap.add_argument("--semantic-classes", type=int, default=150, help="labels of the maps: 0 .. this - 1, 255 ignored")
@@ -51,6 +58,8 @@ def parse(argv=None):
         ap.error(f"SCENE must end in one of {', '.join(READERS)}")
     if args.holdout < 0 or (args.max_image_dimension is not None and args.max_image_dimension < 1):
         ap.error("--holdout must not be negative and --max-image-dimension must be at least 1")
+    if args.refine_poses < 0:
+        ap.error("--refine-poses must not be negative")
     return args
 
 
@@ -78,6 +87,23 @@ def semantic_line(model, cameras, train, views, args):
             f"labels lifted from {len(train)} training views")
 
 
+def apply_poses(cameras, train, path):
+    """Replaces the cameras the corrections at ``path`` were trained on by their refined copies -> how many."""
+    import torch
+    from tinysplat_amd.pose import PoseModel
+    views = int(torch.load(str(path), map_location="cpu")["quats"].shape[0])
+    on = train if views == len(train) else list(range(len(cameras))) if views == len(cameras) else None
+    if on is None:
+        raise SystemExit(f"{path} holds {views} corrections; the dataset has {len(cameras)} cameras, {len(train)} for training")
+    try:
+        refined = PoseModel.load(path, [cameras[i] for i in on]).cameras()
+    except ValueError as e:
+        raise SystemExit(f"{path}: {e}")
+    for i, camera in zip(on, refined):
+        cameras[i] = camera
+    return views
+
+
 def main(argv=None):
     args = parse(argv)
     import torch
@@ -91,16 +117,20 @@ def main(argv=None):
     model = getattr(formats, READERS[Path(args.scene).suffix.lower()])(args.scene, args.device)
     train, test = holdout_split([c.name for c in dataset.cameras], args.holdout)
     views = test if args.holdout else train
+    if args.poses:
+        print(f"{apply_poses(dataset.cameras, train, args.poses)} pose corrections from {args.poses}")
     if not views:
         raise SystemExit(f"--holdout {args.holdout} selects none of the {len(dataset.cameras)} cameras")
     result = evaluate(model, [dataset.cameras[i] for i in views], Targets([dataset.targets.images_u8[i] for i in views]),
-                      args.device, **({"color_correct": True} if args.color_correct else {}))
+                      args.device, **({"color_correct": True} if args.color_correct else {}),
+                      **({"refine_poses": args.refine_poses} if args.refine_poses else {}))
     rows = table_rows(result)
     width = max(len(r[0]) for r in rows)
     print(f"{'view':<{width}}  {'PSNR':>9}  {'SSIM':>8}  {'L1':>8}")
     for name, psnr, ssim, l1, _mse in rows:
         print(f"{name:<{width}}  {psnr:9.4f}  {ssim:8.5f}  {l1:8.5f}")
-    print(f"{len(views)} views, {model.num_points} Gaussians" + (", colour-corrected" if args.color_correct else ""))
+    print(f"{len(views)} views, {model.num_points} Gaussians" + (", colour-corrected" if args.color_correct else "")
+          + (f", poses aligned by {args.refine_poses} steps" if args.refine_poses else ""))
     if args.semantic_dir:
         print(semantic_line(model, dataset.cameras, train, views, args))
     if args.csv:

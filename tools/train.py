@@ -24,7 +24,12 @@ between the render and the loss (``tinysplat_amd.AppearanceModel``: a 3x4 exposu
 ``--appearance-grid L H W`` of them) so that exposure and white balance that change from photo to photo do not end up in the
 scene; ``--appearance-out`` saves the transforms, and with ``--eval-holdout`` the table is also printed (and written to
 ``<metrics-csv stem>_cc.csv``) for renders mapped to their targets by a least-squares affine colour fit, since held-out
-views have no transform.  Flags the reference's parser has keep its names and defaults.  Needs a GPU: there is no CPU path.
+views have no transform.  ``--optimize-poses`` refines every training camera's pose with the scene (``tinysplat_amd.PoseModel``:
+an SE(3) correction per view, ``--pose-lr`` for both rates, ``--pose-reg`` its decay towards the identity), prints the table of
+corrections at the end and saves them with ``--poses-out``; the saved scene then lives in the refined cameras' frame, so with
+``--eval-holdout`` every held-out view is first aligned to its image by ``--eval-refine-poses K`` steps with the Gaussians
+frozen (30 unless given; 0 and without ``--optimize-poses``: the cameras as they are).  Flags the reference's parser has keep
+its names and defaults.  Needs a GPU: there is no CPU path.
 """
 import argparse
 import sys
@@ -118,6 +123,44 @@ def appearance_config(args):
     return AppearanceConfig(grid=grid, lr=args.appearance_lr, tv_weight=args.appearance_tv)
 
 
+def _pose_parser():
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    g = ap.add_argument_group("camera pose refinement")
+    g.add_argument("--optimize-poses", action="store_true", help="refine the training cameras' poses with the scene")
+    g.add_argument("--pose-lr", type=float, default=1e-5, help="Adam rate of a pose's translation and rotation")
+    g.add_argument("--pose-reg", type=float, default=1e-6, help="decay of a correction towards the identity")
+    g.add_argument("--poses-out", type=str, default=None, help="save the trained corrections to this file")
+    g.add_argument("--eval-refine-poses", type=int, default=None, metavar="K",
+                   help="align every held-out view by K pose steps before it is measured (30 with --optimize-poses, else 0)")
+    return ap
+
+
+EVAL_REFINE_STEPS = 30           # --eval-refine-poses where --optimize-poses and --eval-holdout are both given
+
+
+def parse_pose(argv=None):
+    """The pose refinement's options, a namespace of their own like the depth prior's."""
+    ap = _pose_parser()
+    args, _rest = ap.parse_known_args(argv)
+    if args.pose_lr < 0 or args.pose_reg < 0 or (args.eval_refine_poses is not None and args.eval_refine_poses < 0):
+        ap.error("--pose-lr, --pose-reg and --eval-refine-poses must not be negative")
+    if args.poses_out is not None and not args.optimize_poses:
+        ap.error("--poses-out needs --optimize-poses")
+    if args.eval_refine_poses is None:
+        args.eval_refine_poses = EVAL_REFINE_STEPS if args.optimize_poses else 0
+    return args
+
+
+def print_corrections(poses, cameras) -> None:
+    """The table of the trained corrections: per view its rotation angle and the length of its translation."""
+    import numpy as np
+    table = poses.corrections()
+    print(f"{'camera':<32} {'steps':>7} {'rotation (deg)':>15} {'translation':>12}")
+    for i, (angle, shift) in enumerate(table):
+        print(f"{str(getattr(cameras[i], 'name', i)):<32} {poses.steps[i]:>7} {np.degrees(angle):>15.5f} {shift:>12.6f}")
+    print(f"{'mean':<32} {'':>7} {np.degrees(table[:, 0].mean()):>15.5f} {table[:, 1].mean():>12.6f}")
+
+
 def _frame_parser():
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     g = ap.add_argument_group("scene frame")
@@ -141,11 +184,15 @@ def parse(argv=None):
     _strategy, argv = strategy_ap.parse_known_args(argv)
     _appearance, argv = appearance_ap.parse_known_args(argv)
     _frame, argv = _frame_parser().parse_known_args(argv)
+    parse_pose(argv)
+    pose_ap = _pose_parser()
+    _pose, argv = pose_ap.parse_known_args(argv)
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter,
                                  epilog=depth_ap.format_help().split("\n\n", 1)[-1] + "\n" +
                                  strategy_ap.format_help().split("\n\n", 1)[-1] + "\n" +
                                  appearance_ap.format_help().split("\n\n", 1)[-1] + "\n" +
-                                 _frame_parser().format_help().split("\n\n", 1)[-1])
+                                 _frame_parser().format_help().split("\n\n", 1)[-1] + "\n" +
+                                 pose_ap.format_help().split("\n\n", 1)[-1])
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--max-iter", type=int, default=10_000)
@@ -190,6 +237,7 @@ def normalize_scene(dataset):
 
 def main(argv=None):
     args, depth, strategy, look = parse(argv), parse_depth(argv), parse_strategy(argv), parse_appearance(argv)
+    posing = parse_pose(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: tinysplat_amd has no CPU path")
@@ -226,13 +274,13 @@ def main(argv=None):
         depth_targets = None if depth_targets is None else [depth_targets[i] for i in train]
         evaluator = Evaluator(model, *held, args.device, args.eval_interval or len(cameras),
                               on_result=lambda row, _result: print(Evaluator.format(row), flush=True),
-                              csv_path=args.metrics_csv)
+                              csv_path=args.metrics_csv, refine_poses=posing.eval_refine_poses)
         if look.appearance != "none":                         # held-out views have no transform: also measure them colour-corrected
             cc_csv = None if args.metrics_csv is None else \
                 str(Path(args.metrics_csv).with_name(Path(args.metrics_csv).stem + "_cc" + Path(args.metrics_csv).suffix))
             corrected = Evaluator(model, *held, args.device, args.eval_interval or len(cameras), csv_path=cc_csv,
                                   on_result=lambda row, _result: print("colour-corrected | " + Evaluator.format(row), flush=True),
-                                  color_correct=True)
+                                  color_correct=True, refine_poses=posing.eval_refine_poses)
         print(f"{len(cameras)} training cameras, {len(test)} held out")
     if strategy.strategy == "mcmc":
         from tinysplat_amd.mcmc import McmcConfig, McmcDensifier
@@ -256,6 +304,12 @@ def main(argv=None):
         from tinysplat_amd.appearance import AppearanceModel
         appearance = AppearanceModel(len(cameras), appearance_config(look), args.device)
         print(f"appearance: {len(cameras)} grids of {'x'.join(map(str, appearance.config.grid))} colour matrices")
+    poses = None
+    if posing.optimize_poses:
+        from tinysplat_amd.pose import PoseConfig, PoseModel
+        poses = PoseModel(cameras, PoseConfig(lr_translation=posing.pose_lr, lr_rotation=posing.pose_lr,
+                                              weight_decay=posing.pose_reg))
+        print(f"poses: {poses.num_views} corrections, rate {posing.pose_lr:g}, decay {posing.pose_reg:g}")
 
     def on_step(step, out):
         for f in callbacks:
@@ -265,6 +319,8 @@ def main(argv=None):
                                                       depth_schedule=depth_schedule)
         if appearance is not None:
             extra["appearance"] = appearance
+        if poses is not None:
+            extra["poses"] = poses
         out = fit(model, cameras, targets, args.device, args.max_iter, max_sh_degree=args.sh_degree,
                   densifier=densifier, on_step=on_step if callbacks else None, lr_schedule=lr_schedule, **extra)
     finally:
@@ -277,6 +333,11 @@ def main(argv=None):
     if appearance is not None and look.appearance_out:
         appearance.save(look.appearance_out)
         print(f"wrote {look.appearance_out}: {appearance.num_views} appearance grids")
+    if poses is not None:
+        print_corrections(poses, cameras)
+        if posing.poses_out:
+            poses.save(posing.poses_out)
+            print(f"wrote {posing.poses_out}: {poses.num_views} pose corrections")
     if out is not None:
         print(f"step {args.max_iter}: loss {float(out['loss']):.6f}")
         if depth_targets is not None and "depth_l1" in out:
