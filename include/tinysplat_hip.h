@@ -668,6 +668,27 @@ int ts_photometric_loss_planes(int32_t height, int32_t width, const float* image
  * (train.py:58-69).  One small launch instead of a dozen one-element tensor operations on the caller's side. */
 int ts_photometric_loss_reduce(int32_t height, int32_t width, float w_l1, float w_ssim, float w_depth,
                                const float* ws, float* out4, void* stream);
+/* The masked loss (csrc/mask_math.h).  Additive entries: the ABI version is unchanged.
+ * mask: uint8 [height, width]; byte b weighs its pixel by m = b / 255.0f (255: the pixel counts, 0: it is ignored).
+ * Each entry is its sibling above evaluated on the substituted image X' = blend(X, Y, m) - X where b == 255,
+ * fmaf(m, X - Y, Y) otherwise - with the depth term m |depth - depth_target| and the gradients
+ *   v_image = m * dL/dX',   v_depth (or v_image[..., 3]) = m * w_depth * sign(depth - depth_target).
+ * Same weights (NOT renormalised by the mask's area), same workspace (ts_photometric_ws_floats) and layout of the
+ * partial sums, same ts_photometric_loss_reduce afterwards.  An all-255 mask gives the sibling's bits; a pixel with
+ * b == 0 gets a gradient of exactly zero.  TS_E_BADARG, before any launch: what the sibling refuses, and a NULL mask.
+ * ts_mask_blend: out[height, width, 3] <- X' for image, target [height, width, 3] (height, width >= 1). */
+int ts_photometric_loss_rgbd_masked(int32_t height, int32_t width, int32_t pixel_floats, const float* image,
+                                    const float* target, const float* depth_target, const uint8_t* mask, float w_l1,
+                                    float w_ssim, float w_depth, float* ws, float* v_image, void* stream);
+int ts_photometric_loss_masked(int32_t height, int32_t width, const float* image, const float* target,
+                               const uint8_t* mask, float w_l1, float w_ssim, float* ws, float* v_image,
+                               void* stream);
+int ts_photometric_loss_planes_masked(int32_t height, int32_t width, const float* image, const float* depth,
+                                      const float* target, const float* depth_target, const uint8_t* mask,
+                                      float w_l1, float w_ssim, float w_depth, float* ws, float* v_image,
+                                      float* v_depth, void* stream);
+int ts_mask_blend(int32_t height, int32_t width, const float* image, const float* target, const uint8_t* mask,
+                  float* out, void* stream);
 
 /* torch.optim.Adam (defaults: no amsgrad, no weight decay; train.py:26) on up to TS_ADAM_MAX_TENSORS
  * tensors with per-tensor learning rates (model_gaussian.py:112-120) in one launch.  The pointer
@@ -1152,6 +1173,14 @@ int ts_jpeg_encode(const void* image, int32_t dtype, int32_t pixel_stride, int32
 int64_t ts_image_metrics_ws_bytes(int32_t height, int32_t width);
 int ts_image_metrics(int32_t height, int32_t width, int32_t pixel_floats, const float* image, const void* target,
                      int32_t target_is_u8, void* ws, double* out4, void* stream);
+/* The same four values over the pixels a mask keeps: mask uint8 [height, width], m = b / 255.0f,
+ *   mse = sum m (x - y)^2 / (3 sum m),  l1 = sum m |x - y| / (3 sum m),  ssim = sum m_c S(x', y) / (3 sum m_c),
+ * m_c the weight of the window's centre pixel, x' the substituted image of the masked loss; psnr from mse.  A mask
+ * that keeps nothing gives NaN.  An all-255 mask gives ts_image_metrics' bytes.  ws: >= ts_image_metrics_masked_ws_bytes
+ * bytes (40 per wave).  TS_E_BADARG as ts_image_metrics, and for a NULL mask. */
+int64_t ts_image_metrics_masked_ws_bytes(int32_t height, int32_t width);
+int ts_image_metrics_masked(int32_t height, int32_t width, int32_t pixel_floats, const float* image, const void* target,
+                            int32_t target_is_u8, const uint8_t* mask, void* ws, double* out4, void* stream);
 
 /* Depth priors: stored dense depth maps scale-matched to the SfM points (csrc/depth_prior_math.h:
  * the arithmetic, the key's layout, the fit's row and its status codes).  Additive entries: the ABI version is unchanged.

@@ -14,6 +14,7 @@ from .depth import DepthPriors, SparseDepth, match_scale, sparse_depth
 from .jpeg import JpegEncoder, encode_jpeg
 from .mcmc import (ExponentialLr, McmcConfig, McmcDensifier, inject_noise, mcmc_normals, mean_opacity, mean_scale,
                    relocation, sample_rows)
+from .masks import TrainingMasks, combine_masks, dilate_ignored, mask_coverage, masks_from_labels
 from .metrics import EvalResult, Evaluator, affine_color_fit, evaluate, holdout_split, image_metrics
 from .appearance import AppearanceConfig, AppearanceModel
 from .edit import (Sim3, box_mask, crop_gaussians, merge_models, orient_from_cameras, sh_rotation_matrices,
@@ -43,4 +44,5 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "mcmc_normals", "mean_opacity", "mean_scale", "AppearanceConfig", "AppearanceModel", "affine_color_fit", "Sim3",
            "sh_rotation_matrices", "transform_gaussians", "transform_camera", "transform_cameras", "transform_points",
            "orient_from_cameras", "box_mask", "crop_gaussians", "merge_models", "PoseConfig", "PoseModel", "pose_gradient",
-           "refine_pose", "se3_exp", "se3_log"]
+           "refine_pose", "se3_exp", "se3_log", "TrainingMasks", "masks_from_labels", "dilate_ignored", "combine_masks",
+           "mask_coverage"]

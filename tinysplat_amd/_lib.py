@@ -174,6 +174,13 @@ SIGNATURES = {
     "ts_photometric_loss_planes": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P,
                                              _P]),
     "ts_photometric_loss_reduce": (c_int32, [c_int32, c_int32, c_float, c_float, c_float, _P, _P, _P]),
+    # the masked loss: the siblings above with a uint8 [H, W] mask behind the targets
+    "ts_photometric_loss_masked": (c_int32, [c_int32, c_int32, _P, _P, _P, c_float, c_float, _P, _P, _P]),
+    "ts_photometric_loss_rgbd_masked": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, c_float, c_float, c_float,
+                                                  _P, _P, _P]),
+    "ts_photometric_loss_planes_masked": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, c_float, c_float, c_float,
+                                                    _P, _P, _P, _P]),
+    "ts_mask_blend": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P]),
     "ts_adam_step": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, _P]),
     "ts_sh_colors_bwd_adam": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _ADAM, _P]),
     "ts_project_bwd_adam": (c_int32, [c_int32, _P, _P, _P, _P, _P, _CAM, c_int32, _P, _P, _P, _P, _P, _P, _ADAM, _P]),
@@ -276,6 +283,8 @@ SIGNATURES = {
                                  _P, _P]),
     "ts_image_metrics_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ts_image_metrics": (c_int32, [c_int32, c_int32, c_int32, _P, _P, c_int32, _P, _P, _P]),
+    "ts_image_metrics_masked_ws_bytes": (c_int64, [c_int32, c_int32]),
+    "ts_image_metrics_masked": (c_int32, [c_int32, c_int32, c_int32, _P, _P, c_int32, _P, _P, _P, _P]),
     "ts_depth_prior_project": (c_int32, [c_int32, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ts_depth_prior_mark": (c_int32, [c_int64, _P, _P, _P]),
     "ts_depth_prior_gather": (c_int32, [c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

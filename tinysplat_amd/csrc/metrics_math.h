@@ -29,6 +29,7 @@
 #define TS_METRICS_COLS 64                   // map columns per wave
 #define TS_METRICS_CHANNELS 3                // waves per workgroup: one per colour channel
 #define TS_METRICS_PARTIALS 3                // doubles per wave: {sum of S, sum of (x - y)^2, sum of |x - y|}
+#define TS_METRICS_MASKED_PARTIALS 5         // masked: + {sum of m over pixels, sum of m over window centres}
 #define TS_METRICS_SEG_MIN 8
 #define TS_METRICS_SEG_MAX 64
 #define TS_METRICS_WORKGROUPS 768            // the grid the segmentation aims at: three workgroups on each of 256 CUs

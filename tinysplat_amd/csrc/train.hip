@@ -18,6 +18,9 @@
 #include "host_util.h"
 #include "adam_math.h"
 #include "gauss_window.h"
+#include "mask_math.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -119,17 +122,42 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 struct RowRegs { float xm, xe, ym, ye; };              // one pixel row of a wave: main / extra columns of X and Y
+struct RowRegsMasked : RowRegs { uint8_t mm, me; };    // ... and their mask bytes
 
+// The 256 weights of a mask byte (mask_math.h), one division per value and workgroup; the caller's next barrier
+// publishes them.
+__device__ __forceinline__ void fill_mask_table(float* lut, int threads) {
+    for (int i = threadIdx.x; i < 256; i += threads) lut[i] = ts_mask_weight((uint8_t)i);
+}
+
+// kMasked: M is a uint8 [H, W] mask and the pass runs on the substituted image X' = blend(X, Y, m)
+// (mask_math.h), blended where X is fetched; the depth wave weighs its term by m.  A compile-time flag: the unmasked
+// instantiation is the kernel as it was, instruction for instruction - its arguments too: the mask is a trailing pack
+// that is empty without one (the kernel inlined into a wrapper of the old signature allocates four registers more and
+// loses the third wave per SIMD).
+template <typename... Mask>
 __global__ __launch_bounds__(64 * kRowsWaves) void ssim_fwd_rows_kernel(int H, int W, int xs, int seg,
                                                                          const float* __restrict__ X,
                                                                          const float* __restrict__ Xd,
                                                                          const float* __restrict__ Y,
                                                                          const float* __restrict__ D,
                                                                          float* __restrict__ dmaps,
-                                                                         float* __restrict__ sums) {
+                                                                         float* __restrict__ sums,
+                                                                         Mask... mask) {
+    constexpr bool kMasked = sizeof...(Mask) == 1;
+    static_assert(sizeof...(Mask) <= 1, "no mask or one");
     __shared__ float line[3][2][2][kLine];                     // [channel wave][parity][X | Y][column]
     constexpr float g[kWin] = {TS_GAUSS_WINDOW};
     const int lane = threadIdx.x & 63, c = threadIdx.x >> 6;
+    float* lut = nullptr;
+    const uint8_t* __restrict__ M = nullptr;
+    if constexpr (kMasked) {
+        M = (mask, ...);
+        __shared__ float mask_lut[256];
+        lut = mask_lut;
+        fill_mask_table(lut, 64 * kRowsWaves);
+        __syncthreads();                                       // (before the depth wave leaves)
+    }
     const int Ho = H - kHalo, Wo = W - kHalo;
     const int x0 = blockIdx.x * kCols, o0 = blockIdx.y * seg;
     const int rows = min(seg, Ho - o0);                        // map rows of this wave (>= 1)
@@ -152,17 +180,24 @@ __global__ __launch_bounds__(64 * kRowsWaves) void ssim_fwd_rows_kernel(int H, i
             const bool use_b = last_block && in_b;
             for (int t0 = 0; t0 < own_rows; t0 += kWin) {
                 float va[kWin], vb[kWin], ta[kWin], tb[kWin];
+                uint8_t ma[kMasked ? kWin : 1], mb[kMasked ? kWin : 1];
 #pragma unroll
                 for (int i = 0; i < kWin; ++i) {
                     const size_t y = (size_t)(o0 + min(t0 + i, own_rows - 1));
                     va[i] = da[y * stride]; vb[i] = db[y * stride];
                     ta[i] = D[y * W + xa_d]; tb[i] = D[y * W + xb_d];
+                    if constexpr (kMasked) { ma[i] = M[y * W + xa_d]; mb[i] = M[y * W + xb_d]; }
                 }
 #pragma unroll
                 for (int i = 0; i < kWin; ++i) {
                     if (t0 + i < own_rows) {
-                        depth_sum += in_a ? fabsf(va[i] - ta[i]) : 0.0f;
-                        depth_sum += use_b ? fabsf(vb[i] - tb[i]) : 0.0f;
+                        if constexpr (kMasked) {               // m |d - D|, the product fused into the sum: exact at m = 0 and 1
+                            depth_sum = in_a ? __builtin_fmaf(lut[ma[i]], fabsf(va[i] - ta[i]), depth_sum) : depth_sum;
+                            depth_sum = use_b ? __builtin_fmaf(lut[mb[i]], fabsf(vb[i] - tb[i]), depth_sum) : depth_sum;
+                        } else {
+                            depth_sum += in_a ? fabsf(va[i] - ta[i]) : 0.0f;
+                            depth_sum += use_b ? fabsf(vb[i] - tb[i]) : 0.0f;
+                        }
                     }
                 }
             }
@@ -182,11 +217,16 @@ __global__ __launch_bounds__(64 * kRowsWaves) void ssim_fwd_rows_kernel(int H, i
     const float* const ya_p = Y + (size_t)xa_c * 3 + c;
     const float* const yb_p = Y + (size_t)xb_c * 3 + c;
     float* const dmap_lane = dmaps + (size_t)c * Ho * Wo + min(xa, Wo - 1);
-    auto fetch = [&](int y) -> RowRegs {
+    using Regs = std::conditional_t<kMasked, RowRegsMasked, RowRegs>;
+    auto fetch = [&](int y) -> Regs {
         const size_t rx = (size_t)y * W * xs, ry = (size_t)y * W * 3;
-        RowRegs r;
+        Regs r;
         r.xm = xa_p[rx]; r.ym = ya_p[ry];
         r.xe = xb_p[rx]; r.ye = yb_p[ry];
+        if constexpr (kMasked) {                               // the same clamped columns
+            const size_t rm = (size_t)y * W;
+            r.mm = M[rm + xa_c]; r.me = M[rm + xb_c];
+        }
         return r;                                              // (zeroed where they are consumed: a select here would wait for the load)
     };
 
@@ -200,7 +240,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void ssim_fwd_rows_kernel(int H, i
     // has been consumed (its wait then finds loads a whole batch old) 59 - 62 us - the launch is ~0.6 VALU-bound by then.
     constexpr int kBatch = 6, kRing = kWin + 1;
     static_assert(kRing == 2 * kBatch, "two batches per unrolled body");
-    RowRegs rb[2 * kBatch];
+    Regs rb[2 * kBatch];
 #pragma unroll
     for (int i = 0; i < kBatch; ++i) rb[i] = fetch(o0 + min(i, total - 1));
     float ring[5][kRing];
@@ -211,11 +251,16 @@ __global__ __launch_bounds__(64 * kRowsWaves) void ssim_fwd_rows_kernel(int H, i
             const int t = base + s;
             if (t >= total) continue;                          // wave-uniform (no break: the unrolled body keeps static ring indices)
             const int y = o0 + t;
-            const RowRegs cur = rb[s];
+            const Regs cur = rb[s];
+            float cxm = cur.xm, cxe = cur.xe;
+            if constexpr (kMasked) {                           // everything below reads the substituted image
+                cxm = ts_mask_blend_value(cur.xm, cur.ym, cur.mm, lut[cur.mm]);
+                cxe = ts_mask_blend_value(cur.xe, cur.ye, cur.me, lut[cur.me]);
+            }
             // this wave's share of the L1 sums: its own rows and main columns; the last segment / column block also
             // takes the ten trailing rows / columns nobody else starts at
-            const float xm = in_a ? cur.xm : 0.0f, ym = in_a ? cur.ym : 0.0f;
-            const float xe = in_b ? cur.xe : 0.0f, ye = in_b ? cur.ye : 0.0f;
+            const float xm = in_a ? cxm : 0.0f, ym = in_a ? cur.ym : 0.0f;
+            const float xe = in_b ? cxe : 0.0f, ye = in_b ? cur.ye : 0.0f;
             if (t < rows || last_seg) l1_sum += fabsf(xm - ym) + (last_block ? fabsf(xe - ye) : 0.0f);
             float* lx = line[c][t & 1][0];
             float* ly = line[c][t & 1][1];
@@ -271,16 +316,26 @@ __global__ __launch_bounds__(64 * kRowsWaves) void ssim_fwd_rows_kernel(int H, i
 // Pass 2: gradient w.r.t. X.  The transpose of the valid filter is a full correlation of the three
 // partial maps (zero outside the (Ho, Wo) map):  gX = F^T dm + 2 X F^T dq + Y F^T dr, scaled by
 // w_ssim, plus w_l1 * sign(X - Y).
-__global__ __launch_bounds__(kThreads) void ssim_bwd_kernel(int H, int W, int xs,
-                                                            const float* __restrict__ X,
-                                                            const float* __restrict__ Xd,
-                                                            const float* __restrict__ Y,
-                                                            const float* __restrict__ D,
-                                                            const float* __restrict__ dmaps,
-                                                            float w_l1, float w_ssim, float w_depth,
-                                                            float* __restrict__ gX, float* __restrict__ gXd) {
+// kMasked: the gradient is taken at the substituted image X' (as pass 1 read it) and what is written is m times it,
+// dL/dX = m dL/dX'; the depth gradient is m w_depth sign(d - D).
+template <bool kMasked>
+__device__ __forceinline__ void ssim_bwd_body(int H, int W, int xs,
+                                              const float* __restrict__ X,
+                                              const float* __restrict__ Xd,
+                                              const float* __restrict__ Y,
+                                              const float* __restrict__ D,
+                                              const uint8_t* __restrict__ M,
+                                              const float* __restrict__ dmaps,
+                                              float w_l1, float w_ssim, float w_depth,
+                                              float* __restrict__ gX, float* __restrict__ gXd) {
     __shared__ float p0[kPatch][kPatch + 1], p1[kPatch][kPatch + 1], p2[kPatch][kPatch + 1];
     __shared__ float h0[kPatch][kTile + 1], h1[kPatch][kTile + 1], h2[kPatch][kTile + 1];
+    float* lut = nullptr;
+    if constexpr (kMasked) {
+        __shared__ float mask_lut[256];
+        lut = mask_lut;
+        fill_mask_table(lut, kThreads);                        // (published by the first barrier of the channel loop)
+    }
     float g[kWin];
     gauss_window(g);
     const int Ho = H - kHalo, Wo = W - kHalo;
@@ -322,10 +377,27 @@ __global__ __launch_bounds__(kThreads) void ssim_bwd_kernel(int H, int W, int xs
             if (y >= H || x >= W) continue;
             const float a = fa[j], b = fb[j], d = fd[j];
             const size_t pix = (size_t)y * W + x;
-            const float xv = X[pix * xs + c], yv = Y[pix * 3 + c];
+            float xv = X[pix * xs + c];
+            const float yv = Y[pix * 3 + c];
+            if constexpr (kMasked) {
+                const uint8_t mb = M[pix];
+                xv = ts_mask_blend_value(xv, yv, mb, lut[mb]);
+            }
             const float diff = xv - yv;
             const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-            const float gv = w_l1 * sgn + w_ssim * (a + 2.0f * xv * b + yv * d);
+            float gv;
+            if constexpr (kMasked) {
+                // The expression below, with the roundings the compiler gives it in the unmasked kernel spelled out:
+                // there the file's default contraction fuses the inner sums, and the outer sum as fma(w_l1, sgn, w_ssim t)
+                // for the first pixel of a strip but as fma(w_ssim, t, w_l1 sgn) for the other three.  An all-255 mask
+                // must give that kernel's bits (tests/test_gpu_masks.py holds the two together), so nothing is left
+                // to the compiler here.
+#pragma clang fp contract(off)
+                const float t = __builtin_fmaf(yv, d, __builtin_fmaf(xv + xv, b, a));
+                gv = j == 0 ? __builtin_fmaf(w_l1, sgn, w_ssim * t) : __builtin_fmaf(w_ssim, t, w_l1 * sgn);
+            } else {
+                gv = w_l1 * sgn + w_ssim * (a + 2.0f * xv * b + yv * d);
+            }
             if (c == 0) gacc[j][0] = gv; else if (c == 1) gacc[j][1] = gv; else gacc[j][2] = gv;
           }
         }
@@ -338,11 +410,17 @@ __global__ __launch_bounds__(kThreads) void ssim_bwd_kernel(int H, int W, int xs
             const int y = y0 + r0 + j, x = x0 + q;
             if (y >= H || x >= W) continue;
             const size_t pix = (size_t)y * W + x;
+            float m = 1.0f;
+            if constexpr (kMasked) {
+                m = lut[M[pix]];
+                gacc[j][0] *= m; gacc[j][1] *= m; gacc[j][2] *= m;
+            }
             if (xs == 4) {
                 float gd = 0.0f;                     // gradient of the depth channel (zero without a target)
                 if (D) {
                     const float dd = X[pix * 4 + 3] - D[pix];
                     gd = w_depth * (dd > 0.f ? 1.f : (dd < 0.f ? -1.f : 0.f));
+                    if constexpr (kMasked) gd *= m;
                 }
                 reinterpret_cast<float4*>(gX)[pix] = make_float4(gacc[j][0], gacc[j][1], gacc[j][2], gd);
             } else {
@@ -352,12 +430,51 @@ __global__ __launch_bounds__(kThreads) void ssim_bwd_kernel(int H, int W, int xs
                     if (D) {
                         const float dd = Xd[pix] - D[pix];
                         gd = w_depth * (dd > 0.f ? 1.f : (dd < 0.f ? -1.f : 0.f));
+                        if constexpr (kMasked) gd *= m;
                     }
                     gXd[pix] = gd;
                 }
             }
         }
     }
+}
+
+__global__ __launch_bounds__(kThreads) void ssim_bwd_kernel(int H, int W, int xs,
+                                                            const float* __restrict__ X,
+                                                            const float* __restrict__ Xd,
+                                                            const float* __restrict__ Y,
+                                                            const float* __restrict__ D,
+                                                            const float* __restrict__ dmaps,
+                                                            float w_l1, float w_ssim, float w_depth,
+                                                            float* __restrict__ gX, float* __restrict__ gXd) {
+    ssim_bwd_body<false>(H, W, xs, X, Xd, Y, D, nullptr, dmaps, w_l1, w_ssim, w_depth, gX, gXd);
+}
+
+__global__ __launch_bounds__(kThreads) void ssim_bwd_masked_kernel(int H, int W, int xs,
+                                                                   const float* __restrict__ X,
+                                                                   const float* __restrict__ Xd,
+                                                                   const float* __restrict__ Y,
+                                                                   const float* __restrict__ D,
+                                                                   const uint8_t* __restrict__ M,
+                                                                   const float* __restrict__ dmaps,
+                                                                   float w_l1, float w_ssim, float w_depth,
+                                                                   float* __restrict__ gX, float* __restrict__ gXd) {
+    ssim_bwd_body<true>(H, W, xs, X, Xd, Y, D, M, dmaps, w_l1, w_ssim, w_depth, gX, gXd);
+}
+
+// X' = blend(X, Y, m) of an [H, W, 3] image: the image the masked loss reads, written out (ts_mask_blend)
+__global__ __launch_bounds__(kThreads) void mask_blend_kernel(long long pixels, const float* __restrict__ X,
+                                                              const float* __restrict__ Y,
+                                                              const uint8_t* __restrict__ M, float* __restrict__ out) {
+    __shared__ float lut[256];
+    fill_mask_table(lut, kThreads);
+    __syncthreads();
+    const long long p = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (p >= pixels) return;
+    const uint8_t b = M[p];
+    const float m = lut[b];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[3 * p + k] = ts_mask_blend_value(X[3 * p + k], Y[3 * p + k], b, m);
 }
 
 struct AdamTable {
@@ -454,10 +571,67 @@ void launch_ssim_fwd(int height, int width, int xs, const float* image, const fl
     const size_t plane3 = (size_t)3 * (height - kHalo) * (width - kHalo) * 3;
     const int seg = ssim_segment_rows(height - kHalo, width - kHalo);
     const dim3 grid((width - kHalo + kCols - 1) / kCols, (height - kHalo + seg - 1) / seg);
-    hipLaunchKernelGGL(ssim_fwd_rows_kernel, grid, dim3(64 * kRowsWaves), 0, s, height, width, xs, seg, image, depth,
+    hipLaunchKernelGGL(ssim_fwd_rows_kernel<>, grid, dim3(64 * kRowsWaves), 0, s, height, width, xs, seg, image, depth,
                        target, depth_target, ws, ws + plane3);
 }
+
+// the masked pair: the same grids, workspace and sums as the unmasked entries
+int launch_masked_loss(int height, int width, int xs, const float* image, const float* depth, const float* target,
+                       const float* depth_target, const uint8_t* mask, float w_l1, float w_ssim, float w_depth,
+                       float* ws, float* v_image, float* v_depth, hipStream_t s) {
+    const size_t plane3 = (size_t)3 * (height - kHalo) * (width - kHalo) * 3;
+    const int seg = ssim_segment_rows(height - kHalo, width - kHalo);
+    const dim3 rows_grid((width - kHalo + kCols - 1) / kCols, (height - kHalo + seg - 1) / seg);
+    hipLaunchKernelGGL(ssim_fwd_rows_kernel<const uint8_t*>, rows_grid, dim3(64 * kRowsWaves), 0, s, height, width, xs,
+                       seg, image, depth, target, depth_target, ws, ws + plane3, mask);
+    if (v_image) {
+        const dim3 grid((width + kTile - 1) / kTile, (height + kTile - 1) / kTile);
+        hipLaunchKernelGGL(ssim_bwd_masked_kernel, grid, dim3(kThreads), 0, s, height, width, xs, image, depth, target,
+                           depth_target, mask, ws, w_l1, w_ssim, w_depth, v_image, v_depth);
+    }
+    return launch_status();
+}
 }  // namespace
+
+int ts_photometric_loss_rgbd_masked(int32_t height, int32_t width, int32_t pixel_floats, const float* image,
+                                    const float* target, const float* depth_target, const uint8_t* mask, float w_l1,
+                                    float w_ssim, float w_depth, float* ws, float* v_image, void* stream) {
+    if (height <= kHalo || width <= kHalo) return TS_E_BADARG;
+    if (pixel_floats != 3 && pixel_floats != 4) return TS_E_BADARG;
+    if (depth_target && pixel_floats != 4) return TS_E_BADARG;
+    if (!image || !target || !ws || !mask) return TS_E_BADARG;
+    return launch_masked_loss(height, width, (int)pixel_floats, image, nullptr, target, depth_target, mask, w_l1,
+                              w_ssim, w_depth, ws, v_image, nullptr, (hipStream_t)stream);
+}
+
+int ts_photometric_loss_masked(int32_t height, int32_t width, const float* image, const float* target,
+                               const uint8_t* mask, float w_l1, float w_ssim, float* ws, float* v_image,
+                               void* stream) {
+    return ts_photometric_loss_rgbd_masked(height, width, 3, image, target, nullptr, mask, w_l1, w_ssim, 0.0f, ws,
+                                           v_image, stream);
+}
+
+int ts_photometric_loss_planes_masked(int32_t height, int32_t width, const float* image, const float* depth,
+                                      const float* target, const float* depth_target, const uint8_t* mask,
+                                      float w_l1, float w_ssim, float w_depth, float* ws, float* v_image,
+                                      float* v_depth, void* stream) {
+    if (height <= kHalo || width <= kHalo) return TS_E_BADARG;
+    if (!image || !target || !ws || !mask || (depth_target && !depth) || (v_depth && (!depth || !v_image)))
+        return TS_E_BADARG;
+    return launch_masked_loss(height, width, 3, image, depth, target, depth_target, mask, w_l1, w_ssim, w_depth, ws,
+                              v_image, v_depth, (hipStream_t)stream);
+}
+
+int ts_mask_blend(int32_t height, int32_t width, const float* image, const float* target, const uint8_t* mask,
+                  float* out, void* stream) {
+    if (height <= 0 || width <= 0 || !image || !target || !mask || !out) return TS_E_BADARG;
+    const long long pixels = (long long)height * width;
+    const long long blocks = (pixels + kThreads - 1) / kThreads;
+    if (blocks > INT32_MAX) return TS_E_BADARG;
+    hipLaunchKernelGGL(mask_blend_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, pixels, image,
+                       target, mask, out);
+    return launch_status();
+}
 
 int ts_photometric_loss_rgbd(int32_t height, int32_t width, int32_t pixel_floats, const float* image,
                              const float* target, const float* depth_target, float w_l1,

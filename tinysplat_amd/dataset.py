@@ -231,6 +231,9 @@ class Dataset:
         dev = torch.device(device)
         rec = read_reconstruction(colmap_path)
         self.cameras, images_u8, self.resampled = [], [], []
+        # each image's CameraSetup and the (width, height) of its file: what warps a source-sized mask exactly as its
+        # photo was warped (masks.TrainingMasks)
+        self.setups, self.source_sizes = [], []
         for img in rec.images.values():
             if img.camera_id not in rec.cameras:
                 raise ValueError(f"image {img.name} names camera {img.camera_id}, which cameras.bin does not hold")
@@ -246,6 +249,8 @@ class Dataset:
             self.cameras.append(setup.camera)
             images_u8.append(src)
             self.resampled.append(setup.resample)
+            self.setups.append(setup)
+            self.source_sizes.append((int(pixels.shape[1]), int(pixels.shape[0])))
         self.targets = Targets(images_u8)
 
         positions = np.stack([c.position for c in self.cameras]) if self.cameras else np.zeros((0, 3))

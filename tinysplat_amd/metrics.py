@@ -14,7 +14,7 @@ window is zero-padded at the image border; that is a different number, usually a
 from __future__ import annotations
 
 import csv
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -28,13 +28,17 @@ from .ops import _call, _need_hip, _ptr, _stream
 COLUMNS = ("mse", "l1", "ssim", "psnr")          # the four doubles of ts_image_metrics, in its order
 
 
-def image_metrics(image: Tensor, target: Tensor, out: Optional[Tensor] = None) -> Tensor:
+def image_metrics(image: Tensor, target: Tensor, out: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> Tensor:
     """{mse, l1, ssim, psnr} of ``image`` (float32 [H, W, 3 or 4]; a fourth channel, the frame's depth, is ignored)
     against ``target`` ([H, W, 3], float32 or uint8 whose bytes stand for b / 255) -> a float64 [4] device tensor, or
     ``out`` (float64 [4], contiguous: a row of a larger table will do).  A uint8 target gives the same bits as its
     float32 quotients b / 255 (IEEE division, what ``target.to(float32) / 255.0`` is on the host; on the device torch
     multiplies by the reciprocal, one ulp off for some bytes).  Two launches on the current stream, no host
-    synchronisation."""
+    synchronisation.
+    ``mask`` (uint8 or bool [H, W]): the values over the pixels the mask keeps, byte b weighing its
+    pixel by m = b / 255: mse and l1 are sums of m (x - y)^2 and m |x - y| over 3 sum m, ssim the SSIM map of the masked
+    loss's substituted image weighed by the window centres' m, psnr from that mse.  A mask that keeps nothing gives NaN;
+    an all-255 mask the unmasked bytes.  None, the default: the launches as they always were."""
     dev = _need_hip(image, target)
     if image.dim() != 3 or image.shape[2] not in (3, 4) or image.dtype != torch.float32:
         raise ValueError("image must be float32 [H, W, 3] or [H, W, 4]")
@@ -49,6 +53,16 @@ def image_metrics(image: Tensor, target: Tensor, out: Optional[Tensor] = None) -
         raise ValueError("out must be a contiguous float64 [4] tensor on the image's device")
     image, target = image.contiguous(), target.contiguous()
     lib = _lib.load()
+    if mask is not None:
+        from .masks import as_mask
+        mask = as_mask(mask)
+        if tuple(mask.shape) != (h, w) or mask.device != dev:
+            raise ValueError(f"mask must be uint8 or bool [{h}, {w}] on {dev}, got {tuple(mask.shape)} on {mask.device}")
+        ws = torch.empty((int(lib.ts_image_metrics_masked_ws_bytes(h, w)),), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _call("ts_image_metrics_masked", lib.ts_image_metrics_masked, h, w, xs, _ptr(image), _ptr(target),
+                  int(target.dtype == torch.uint8), _ptr(mask), _ptr(ws), _ptr(out), _stream(dev))
+        return out
     ws = torch.empty((int(lib.ts_image_metrics_ws_bytes(h, w)),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         _call("ts_image_metrics", lib.ts_image_metrics, h, w, xs, _ptr(image), _ptr(target),
@@ -110,12 +124,18 @@ def color_corrected(image: Tensor, target: Tensor) -> Tensor:
 class EvalResult:
     """``table``: float64 [V, 4], a row of {mse, l1, ssim, psnr} per view; ``names``: the views' names.  The properties
     are means of the per-view values: the reference's per-camera mean, and the convention of the 3DGS papers (a mean of
-    per-view PSNRs, not the PSNR of the mean error)."""
+    per-view PSNRs, not the PSNR of the mean error).  A view whose mask keeps nothing has NaN in its row (DESIGN.md
+    section 6v): the means leave such values out, and ``empty`` names the views with one."""
     table: np.ndarray
     names: List[str]
+    empty: List[str] = field(default_factory=list)
 
     def _mean(self, column: str) -> float:
-        return float(self.table[:, COLUMNS.index(column)].mean())
+        values = self.table[:, COLUMNS.index(column)]
+        if np.isnan(values).any():                     # views whose mask keeps nothing (NaN if none is left)
+            kept = values[~np.isnan(values)]
+            return float(kept.mean()) if kept.size else float("nan")
+        return float(values.mean())
 
     @property
     def mse(self) -> float:
@@ -141,7 +161,7 @@ def _target(targets, i: int) -> Tensor:
 
 @torch.no_grad()
 def evaluate(model, cameras: Sequence, targets, device, background=None, color_correct: bool = False,
-             refine_poses: int = 0, pose_config=None) -> EvalResult:
+             refine_poses: int = 0, pose_config=None, masks=None) -> EvalResult:
     """Renders every camera forward-only (``frame.render_view``, the viewer's path: its image is the training forward's
     bit for bit) on a fixed background - black unless given, the reference model's ``torch.zeros(3)``; the training loop
     draws a random one per step - and measures it against ``targets[i]`` (a ``dataset.Targets``, whose uint8 images are
@@ -152,12 +172,19 @@ def evaluate(model, cameras: Sequence, targets, device, background=None, color_c
     (``color_corrected``) and then measured; False, the default: the render is measured as it is.
     ``refine_poses``: after pose training the scene has drifted against the held-out cameras, so each view is first
     aligned to its target by that many steps of ``pose.refine_pose`` (Gaussians frozen, the model untouched bit for bit;
-    ``pose_config``: its ``PoseConfig``) and measured from the aligned camera; 0, the default: the cameras as given."""
+    ``pose_config``: its ``PoseConfig``) and measured from the aligned camera; 0, the default: the cameras as given.
+    ``masks``: a sequence indexed like the targets of uint8 or bool [H, W] tensors or None per view (DESIGN.md section
+    6v): a masked view is measured over its kept pixels (``image_metrics(..., mask=)``); one whose mask keeps nothing
+    gets a NaN row, is left out of the result's means and is named in its ``empty``.  With ``color_correct`` the affine
+    fit of a masked view still uses ALL its pixels (a masked fit is not built): ignored content pulls on the fit, only
+    the measurement leaves it out.  Pose alignment likewise reads the whole image.  None: the calls as they always were."""
     from .rasterizer import GaussianRasterizer
     dev = torch.device(device)
     cameras = list(cameras)
     if len(cameras) == 0 or len(targets) != len(cameras):
         raise ValueError(f"{len(cameras)} cameras, {len(targets)} targets: evaluation needs one target per camera, at least one")
+    if masks is not None and len(masks) != len(cameras):
+        raise ValueError(f"{len(masks)} masks for {len(cameras)} cameras: masks needs one entry (or None) per camera")
     render = GaussianRasterizer(model, cameras, device=dev)
     table = torch.empty((len(cameras), 4), dtype=torch.float64, device=dev)
     found = model.background
@@ -173,11 +200,17 @@ def evaluate(model, cameras: Sequence, targets, device, background=None, color_c
             image, _extras = render(camera, None, model.active_sh_degree)
             if color_correct:
                 image = color_corrected(image, _target(targets, i))
-            image_metrics(image, _target(targets, i), out=table[i])
+            if masks is None or masks[i] is None:
+                image_metrics(image, _target(targets, i), out=table[i])
+            else:
+                image_metrics(image, _target(targets, i), out=table[i], mask=masks[i])
     finally:
         model.background = found
     names = [str(getattr(c, "name", i)) for i, c in enumerate(cameras)]
-    return EvalResult(table.cpu().numpy(), names)
+    table = table.cpu().numpy()
+    if masks is None:
+        return EvalResult(table, names)
+    return EvalResult(table, names, [n for n, row in zip(names, table) if np.isnan(row).any()])
 
 
 def holdout_split(names: Sequence[str], every: int = 8, offset: int = 0) -> Tuple[List[int], List[int]]:
@@ -200,17 +233,20 @@ class Evaluator:
     ``EvalResult`` behind each row.  Every row is handed to ``on_result(row, result)`` if given and appended to
     ``csv_path`` if given (the header is written when the file is created).  ``refine_poses`` / ``pose_config``: as
     ``evaluate``'s - every view is aligned to its image first, which leaves the model untouched, so training with the
-    evaluator attached stays what it is without."""
+    evaluator attached stays what it is without.  ``masks``: as ``evaluate``'s, indexed like the targets: the rows are
+    means over the views' kept pixels, and over the views that keep any."""
     HEADER = ("step", "n", "psnr", "ssim", "l1")
 
     def __init__(self, model, cameras, targets, device, every: int, on_result: Optional[Callable] = None,
-                 csv_path=None, background=None, color_correct: bool = False, refine_poses: int = 0, pose_config=None):
+                 csv_path=None, background=None, color_correct: bool = False, refine_poses: int = 0, pose_config=None,
+                 masks=None):
         if int(every) < 0:
             raise ValueError("Evaluator: every must not be negative (0: only final())")
         self.model, self.cameras, self.targets, self.device = model, list(cameras), targets, device
         self.every, self.on_result, self.background = int(every), on_result, background
         self.color_correct = bool(color_correct)
         self.refine_poses, self.pose_config = int(refine_poses), pose_config
+        self.masks = masks                         # indexed like the targets (``evaluate``'s ``masks``)
         self.csv_path = None if csv_path is None else Path(csv_path)
         self.rows: List[tuple] = []
         self.results: List[EvalResult] = []
@@ -226,7 +262,8 @@ class Evaluator:
         result = evaluate(self.model, self.cameras, self.targets, self.device, self.background,
                           **({"color_correct": True} if self.color_correct else {}),
                           **({"refine_poses": self.refine_poses, "pose_config": self.pose_config}
-                             if self.refine_poses > 0 else {}))
+                             if self.refine_poses > 0 else {}),
+                          **({} if self.masks is None else {"masks": self.masks}))
         row = (int(step), int(self.model.means.shape[0]), result.psnr, result.ssim, result.l1)
         self.rows.append(row)
         self.results.append(result)

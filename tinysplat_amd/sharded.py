@@ -1090,11 +1090,18 @@ class _ShardedFrame(torch.autograd.Function):
         return grads + (None,) * 11
 
 
-def render_sharded(model_shard, camera, device, layout: ShardLayout, exchange: Exchange, with_depth: bool = False):
+def render_sharded(model_shard, camera, device, layout: ShardLayout, exchange: Exchange, with_depth: bool = False,
+                   mask=None):
     """This rank's stripe of the reference frame (rasterize.py:26-62) from the Gaussians ALL ranks own.
     ``model_shard`` holds the rows ``layout.owned`` of the model.  -> (out[rows, W, 3 or 4] with RGB clamped to
     <= 1 and, with ``with_depth``, the depth map as channel 3; (row_begin_px, row_end_px); xys[n_owned, 2] whose
-    ``.grad`` receives the owned Gaussians' 2-D position gradients in backward)."""
+    ``.grad`` receives the owned Gaussians' 2-D position gradients in backward).
+    ``mask``: refused.  The sharded trainer does not take training masks: a rank's loss runs on
+    its stripe of the frame, and the masked loss is defined and tested on whole images only."""
+    if mask is not None:
+        raise ValueError("the sharded trainer does not take masks: a rank's loss runs on its stripe of the frame, and the "
+                         "masked loss (DESIGN.md section 6v) is built for whole images only - train masked scenes on "
+                         "one GPU (training.fit(..., masks=))")
     view, projview, origin = camera_on_device(camera, device)
     out, xys, _ = _ShardedFrame.apply(model_shard.means, model_shard.scales, model_shard.quats,
                                       model_shard.opacities, model_shard.colors_dc, model_shard.colors_rest,

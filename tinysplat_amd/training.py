@@ -35,9 +35,18 @@ def _loss_values(lib, h, w, w_l1, w_ssim, w_depth, ws, dev) -> Tensor:
     return out
 
 
+def _mask_arg(mask, h: int, w: int, dev) -> Tensor:
+    """A loss function's ``mask`` as the kernels read it: contiguous uint8 [H, W] on ``dev`` (masks.as_mask: bool -> 0 / 255)."""
+    from .masks import as_mask
+    mask = as_mask(mask)
+    if tuple(mask.shape) != (h, w) or mask.device != dev:
+        raise ValueError(f"mask must be uint8 or bool [{h}, {w}] on {dev}, got {tuple(mask.shape)} on {mask.device}")
+    return mask
+
+
 class _PhotometricLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, image, target, lambda_dssim):
+    def forward(ctx, image, target, lambda_dssim, mask=None):
         dev = _need_hip(image, target)
         if image.dim() != 3 or image.shape[2] != 3 or image.shape != target.shape:
             raise ValueError("image and target must both be [H, W, 3]")
@@ -52,8 +61,12 @@ class _PhotometricLoss(torch.autograd.Function):
         lam = float(lambda_dssim)
         with torch.cuda.device(dev):
             w_l1, w_ssim = (1.0 - lam) / (3.0 * h * w), -lam / (3.0 * ho * wo)
-            _call("ts_photometric_loss", lib.ts_photometric_loss, h, w, _ptr(image), _ptr(target),
-                  w_l1, w_ssim, _ptr(ws), _ptr(v_image), _stream(dev))
+            if mask is None:
+                _call("ts_photometric_loss", lib.ts_photometric_loss, h, w, _ptr(image), _ptr(target),
+                      w_l1, w_ssim, _ptr(ws), _ptr(v_image), _stream(dev))
+            else:
+                _call("ts_photometric_loss_masked", lib.ts_photometric_loss_masked, h, w, _ptr(image), _ptr(target),
+                      _ptr(_mask_arg(mask, h, w, dev)), w_l1, w_ssim, _ptr(ws), _ptr(v_image), _stream(dev))
             loss, l1, ssim, _ = _loss_values(lib, h, w, w_l1, w_ssim, 0.0, ws, dev).unbind(0)
         ctx.save_for_backward(v_image)
         ctx.mark_non_differentiable(l1, ssim)
@@ -62,14 +75,14 @@ class _PhotometricLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, v_loss, _v_l1, _v_ssim):
         (v_image,) = ctx.saved_tensors
-        return (None if v_image is None else v_image * v_loss), None, None
+        return (None if v_image is None else v_image * v_loss), None, None, None
 
 
 class _FrameLoss(torch.autograd.Function):
     """train.py:58-69 on the adapter's 4-channel output (RGB + depth) in one pair of launches."""
 
     @staticmethod
-    def forward(ctx, frame, target, depth_target, lambda_dssim, lambda_depth):
+    def forward(ctx, frame, target, depth_target, lambda_dssim, lambda_depth, mask=None):
         dev = _need_hip(frame, target)
         if frame.dim() != 3 or frame.shape[2] != 4 or not frame.is_contiguous():
             raise ValueError("frame must be a contiguous [H, W, 4] tensor (RGB + depth)")
@@ -87,8 +100,13 @@ class _FrameLoss(torch.autograd.Function):
         lam, lamd = float(lambda_dssim), float(lambda_depth) if dt is not None else 0.0
         with torch.cuda.device(dev):
             w_l1, w_ssim, w_depth = (1.0 - lam) / (3.0 * h * w), -lam / (3.0 * ho * wo), lamd / (h * w)
-            _call("ts_photometric_loss_rgbd", lib.ts_photometric_loss_rgbd, h, w, 4, _ptr(frame),
-                  _ptr(target), _ptr(dt), w_l1, w_ssim, w_depth, _ptr(ws), _ptr(v_frame), _stream(dev))
+            if mask is None:
+                _call("ts_photometric_loss_rgbd", lib.ts_photometric_loss_rgbd, h, w, 4, _ptr(frame),
+                      _ptr(target), _ptr(dt), w_l1, w_ssim, w_depth, _ptr(ws), _ptr(v_frame), _stream(dev))
+            else:
+                _call("ts_photometric_loss_rgbd_masked", lib.ts_photometric_loss_rgbd_masked, h, w, 4, _ptr(frame),
+                      _ptr(target), _ptr(dt), _ptr(_mask_arg(mask, h, w, dev)), w_l1, w_ssim, w_depth, _ptr(ws),
+                      _ptr(v_frame), _stream(dev))
             loss, l1, ssim, ldepth = _loss_values(lib, h, w, w_l1, w_ssim, w_depth, ws, dev).unbind(0)
         ctx.save_for_backward(v_frame)
         ctx.mark_non_differentiable(l1, ssim, ldepth)
@@ -97,15 +115,18 @@ class _FrameLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, v_loss, *_):
         (v_frame,) = ctx.saved_tensors
-        return (None if v_frame is None else v_frame * v_loss), None, None, None, None   # out of place: retain_graph re-runs this (train.py:71)
+        return (None if v_frame is None else v_frame * v_loss), None, None, None, None, None   # out of place: retain_graph re-runs this (train.py:71)
 
 
 def planes_loss_and_gradient(rgb: Tensor, depth: Tensor, target: Tensor, depth_target: Optional[Tensor],
-                             lambda_dssim: float, lambda_depth: float, want_rgb: bool = True, want_depth: bool = True):
+                             lambda_dssim: float, lambda_depth: float, want_rgb: bool = True, want_depth: bool = True,
+                             mask: Optional[Tensor] = None):
     """train.py:58-69 on the adapter's two outputs as it hands them out (rgb[H,W,3] and depth[H,W], both contiguous:
     frame.render_frame_planes) in one pair of launches, WITHOUT autograd: -> (values[4] = {loss, l1, ssim, depth l1},
     dloss/drgb or None, dloss/ddepth or None).  ``TrainStep`` hands the two gradients straight to
-    ``torch.autograd.backward`` - no loss node, no ``grad * 1.0`` passes over 33 MB."""
+    ``torch.autograd.backward`` - no loss node, no ``grad * 1.0`` passes over 33 MB.
+    ``mask`` (uint8 or bool [H, W]): the masked pair of launches - the loss of the substituted
+    image, gradients times the pixel's weight; None: the launches as they always were."""
     dev = _need_hip(rgb, depth, target)
     if rgb.dim() != 3 or rgb.shape[2] != 3 or not rgb.is_contiguous() or not depth.is_contiguous():
         raise ValueError("rgb must be a contiguous [H, W, 3] tensor and depth a contiguous [H, W] one")
@@ -124,8 +145,13 @@ def planes_loss_and_gradient(rgb: Tensor, depth: Tensor, target: Tensor, depth_t
     lam, lamd = float(lambda_dssim), float(lambda_depth) if dt is not None else 0.0
     w_l1, w_ssim, w_depth = (1.0 - lam) / (3.0 * h * w), -lam / (3.0 * ho * wo), lamd / (h * w)
     with torch.cuda.device(dev):
-        _call("ts_photometric_loss_rgbd", lib.ts_photometric_loss_planes, h, w, _ptr(rgb), _ptr(depth),
-              _ptr(target), _ptr(dt), w_l1, w_ssim, w_depth, _ptr(ws), _ptr(v_rgb), _ptr(v_depth), _stream(dev))
+        if mask is None:
+            _call("ts_photometric_loss_rgbd", lib.ts_photometric_loss_planes, h, w, _ptr(rgb), _ptr(depth),
+                  _ptr(target), _ptr(dt), w_l1, w_ssim, w_depth, _ptr(ws), _ptr(v_rgb), _ptr(v_depth), _stream(dev))
+        else:
+            _call("ts_photometric_loss_planes_masked", lib.ts_photometric_loss_planes_masked, h, w, _ptr(rgb), _ptr(depth),
+                  _ptr(target), _ptr(dt), _ptr(_mask_arg(mask, h, w, dev)), w_l1, w_ssim, w_depth, _ptr(ws), _ptr(v_rgb),
+                  _ptr(v_depth), _stream(dev))
         values = _loss_values(lib, h, w, w_l1, w_ssim, w_depth, ws, dev)
     return values, v_rgb, v_depth
 
@@ -134,9 +160,10 @@ class _PlanesLoss(torch.autograd.Function):
     """``planes_loss_and_gradient`` as a differentiable function of rgb and depth."""
 
     @staticmethod
-    def forward(ctx, rgb, depth, target, depth_target, lambda_dssim, lambda_depth):
+    def forward(ctx, rgb, depth, target, depth_target, lambda_dssim, lambda_depth, mask=None):
         values, v_rgb, v_depth = planes_loss_and_gradient(rgb, depth, target, depth_target, lambda_dssim, lambda_depth,
-                                                          ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+                                                          ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                                          **({} if mask is None else {"mask": mask}))
         loss, l1, ssim, ldepth = values.unbind(0)
         ctx.has_depth = v_depth is not None
         ctx.save_for_backward(*(t for t in (v_rgb, v_depth) if t is not None))
@@ -148,28 +175,33 @@ class _PlanesLoss(torch.autograd.Function):
         saved = ctx.saved_tensors
         v_rgb = saved[0] * v_loss if saved else None             # out of place: retain_graph re-runs this (train.py:71)
         v_depth = saved[1] * v_loss if ctx.has_depth else None   # None: no depth target, the kernels take "no gradient"
-        return v_rgb, v_depth, None, None, None, None
+        return v_rgb, v_depth, None, None, None, None, None
 
 
 def planes_loss(rgb: Tensor, depth: Tensor, target: Tensor, depth_target: Optional[Tensor] = None,
-                lambda_dssim: float = 0.2, lambda_depth: float = 0.2):
+                lambda_dssim: float = 0.2, lambda_depth: float = 0.2, mask: Optional[Tensor] = None):
     """``frame_loss`` on the frame as two planes: ``(loss, l1, ssim, depth_l1)``, differentiable w.r.t. ``rgb`` and
-    ``depth``."""
-    return _PlanesLoss.apply(rgb, depth, target, depth_target, lambda_dssim, lambda_depth)
+    ``depth``.  ``mask``: as ``photometric_loss``'s."""
+    return _PlanesLoss.apply(rgb, depth, target, depth_target, lambda_dssim, lambda_depth, mask)
 
 
 def frame_loss(frame: Tensor, target: Tensor, depth_target: Optional[Tensor] = None,
-               lambda_dssim: float = 0.2, lambda_depth: float = 0.2):
+               lambda_dssim: float = 0.2, lambda_depth: float = 0.2, mask: Optional[Tensor] = None):
     """Total training loss of train.py:58-69 on the adapter's [H, W, 4] output (RGB already clamped,
     channel 3 = depth): ``(1-l) L1 + l (1 - SSIM) [+ l_depth * mean|depth - depth_target|]``.
-    Returns ``(loss, l1, ssim, depth_l1)``; differentiable w.r.t. ``frame``."""
-    return _FrameLoss.apply(frame, target, depth_target, lambda_dssim, lambda_depth)
+    Returns ``(loss, l1, ssim, depth_l1)``; differentiable w.r.t. ``frame``.  ``mask``: as ``photometric_loss``'s; the
+    depth term becomes ``mean(m |depth - depth_target|)``."""
+    return _FrameLoss.apply(frame, target, depth_target, lambda_dssim, lambda_depth, mask)
 
 
-def photometric_loss(image: Tensor, target: Tensor, lambda_dssim: float = 0.2):
+def photometric_loss(image: Tensor, target: Tensor, lambda_dssim: float = 0.2, mask: Optional[Tensor] = None):
     """``(1 - lambda) * mean|image - target| + lambda * (1 - SSIM(image, target))`` on HWC images
-    (the loss of train.py:58-63).  Returns ``(loss, l1, ssim)``; differentiable w.r.t. ``image``."""
-    return _PhotometricLoss.apply(image, target, lambda_dssim)
+    (the loss of train.py:58-63).  Returns ``(loss, l1, ssim)``; differentiable w.r.t. ``image``.
+    ``mask`` (uint8 or bool [H, W] on the image's device): byte b weighs its pixel by m = b / 255.
+    The loss is then the same loss, with the same weights (not renormalised by the mask's area), of the substituted image
+    ``m image + (1 - m) target``, and the gradient is m times that loss's: an ignored pixel (0) gets exactly zero, an
+    all-255 mask gives the unmasked bits.  None, the default: the launches as they always were."""
+    return _PhotometricLoss.apply(image, target, lambda_dssim, mask)
 
 
 class Adam:
@@ -264,7 +296,7 @@ class TrainStep:
 
     def __call__(self, camera, target_rgb: Tensor, target_depth: Optional[Tensor] = None,
                  densifier=None, step: Optional[int] = None, surface=None, appearance=None, view: Optional[int] = None,
-                 poses=None):
+                 poses=None, mask: Optional[Tensor] = None):
         """``densifier`` (densify.Densifier) + ``step`` add train.py:99-102 after the Adam update:
         gradient accumulation and, on the policy's steps, clone / split / prune.  A densifier with a ``loss_terms(model,
         step)`` method (mcmc.McmcDensifier) adds its terms to the loss as ``surface`` does.
@@ -281,7 +313,11 @@ class TrainStep:
         pose: the backward pass writes the gradient tensors (the two-launch Adam: the fused update
         keeps no rows to reduce), ``ts_pose_grad`` reduces the rows of means and quats before Adam moves them, and
         ``poses.step(view, g)`` follows; ``out`` gains ``pose_grad``.  A SuGaR density term active at ``step`` is refused:
-        its gradient on the means did not come through the camera.  None: the step is exactly today's."""
+        its gradient on the means did not come through the camera.  None: the step is exactly today's.
+        ``mask`` (uint8 or bool [H, W], aligned with ``target_rgb``) leaves pixels out of the loss:
+        whichever of the three loss paths the render selects runs its masked launches, on the image after ``appearance``;
+        everything else, the fused Adam included, is as without.  None: the step is exactly today's."""
+        masked = {} if mask is None else {"mask": mask}
         if appearance is not None and view is None:
             raise ValueError("appearance needs the index of the rendered view")
         if poses is not None:
@@ -313,7 +349,7 @@ class TrainStep:
             # the adapter's one-node path hands out two contiguous images: the whole loss (train.py:58-69) on
             # them in one pair of launches, gradients back as two planes
             values, v_rgb, v_depth = planes_loss_and_gradient(shown, depth, target_rgb, target_depth, self.lambda_dssim,
-                                                              self.lambda_depth)
+                                                              self.lambda_depth, **masked)
             loss, l1, ssim, depth_l1 = values.unbind(0)
             direct = ([shown] + ([depth] if v_depth is not None else []), [v_rgb] + ([v_depth] if v_depth is not None else []))
         elif (frame is not None and frame.dim() == 3 and frame.shape[2] == 4 and frame.is_contiguous()
@@ -322,13 +358,17 @@ class TrainStep:
             # whole loss (train.py:58-69) on it in place, no slicing / re-packing of image or gradient
             if appearance is None:
                 loss, l1, ssim, depth_l1 = frame_loss(frame, target_rgb, target_depth, self.lambda_dssim,
-                                                      self.lambda_depth)
+                                                      self.lambda_depth, **masked)
             else:                                              # the applied image is a tensor of its own: the two-plane loss
                 loss, l1, ssim, depth_l1 = planes_loss(shown, extras["depth"].contiguous(), target_rgb, target_depth,
-                                                       self.lambda_dssim, self.lambda_depth)
+                                                       self.lambda_dssim, self.lambda_depth, **masked)
         else:
-            loss, l1, ssim = photometric_loss(shown, target_rgb, self.lambda_dssim)
-            if target_depth is not None:                          # train.py:65-69
+            loss, l1, ssim = photometric_loss(shown, target_rgb, self.lambda_dssim, **masked)
+            if target_depth is not None and mask is not None:     # m |d - D|: the mean still runs over all pixels
+                from .masks import mask_weights
+                depth_l1 = (mask_weights(mask) * (extras["depth"] - target_depth)).abs().mean()
+                loss = loss + self.lambda_depth * depth_l1
+            elif target_depth is not None:                        # train.py:65-69
                 depth_l1 = (extras["depth"] - target_depth).abs().mean()
                 loss = loss + self.lambda_depth * depth_l1
         if terms:                                              # train.py:71-75: loss += lambda * term
@@ -411,7 +451,7 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
         sh_increment_interval: int = 500, max_sh_degree: int = 3, lambda_dssim: float = 0.2,
         lambda_depth: float = 0.2, depth_schedule: Optional[Scheduler] = None, densifier=None,
         lrs: Optional[Dict[str, float]] = None, rng=None, generator: Optional[torch.Generator] = None,
-        on_step=None, surface=None, lr_schedule=None, appearance=None, poses=None):
+        on_step=None, surface=None, lr_schedule=None, appearance=None, poses=None, masks=None):
     """The training loop of scripts/train.py:45-106 (steps 1-7) on in-memory cameras / targets:
     SH degree schedule (:49-50, model_gaussian.py:126-128), random background (:51), camera pick
     (:54), render + loss (:55-69), the opacity-entropy (:71-75) and SuGaR density (:77-91)
@@ -425,7 +465,12 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
     step goes through the picked camera's colour grid; None, the default: no colour model.
     ``poses``: a ``pose.PoseConfig`` (a ``PoseModel`` over ``cameras`` is made from it) or a ``PoseModel``: every step
     renders the picked view's refined camera and updates its pose; not together with a SuGaR
-    density window that opens within ``max_iter``; None, the default: the cameras are taken as exact."""
+    density window that opens within ``max_iter``; None, the default: the cameras are taken as exact.
+    ``masks``: a sequence aligned with ``cameras`` (a ``masks.TrainingMasks`` will do) of uint8 or bool [H, W] tensors or
+    None per view: the pixels each view's loss leaves out; None, the default, and a view whose
+    entry is None: the step as it always was."""
+    if masks is not None and len(masks) != len(cameras):
+        raise ValueError(f"{len(masks)} masks for {len(cameras)} cameras: masks needs one entry (or None) per camera")
     dev = torch.device(device)
     scene = Scene(cameras, model, device=dev, rng=rng)
     step_fn = TrainStep(model, dev, lambda_dssim, lambda_depth, lrs, scene=scene)
@@ -463,7 +508,8 @@ def fit(model, cameras, targets, device, max_iter: int, depth_targets=None,
             step_fn.optimizer.lrs.update(lr_schedule(step))
         out = step_fn(cameras[i], targets[i], depth_targets[i] if use_depth else None,
                       densifier=densifier, step=step, surface=surface,
-                      **per_view, **({} if not per_view else dict(view=i)))
+                      **per_view, **({} if not per_view else dict(view=i)),
+                      **({} if masks is None or masks[i] is None else dict(mask=masks[i])))
         if on_step is not None:
             on_step(step, out)
     return out

@@ -14,7 +14,10 @@ maps.  ``--color-correct`` first maps every render to its target by a least-squa
 measures the result: the numbers to quote for a scene trained with ``tools/train.py --appearance``, whose held-out views
 have no colour transform of their own.  ``--refine-poses K`` first aligns every evaluated view to its image by K pose steps with
 the Gaussians frozen (``pose.refine_pose``): the numbers to quote for a scene trained with ``tools/train.py --optimize-poses``,
-which has drifted against the held-out cameras.  ``--poses poses.pth`` puts the corrections that run saved onto the cameras
+which has drifted against the held-out cameras.  ``--masks-dir D`` (one mask per photo below ``--dataset-dir``, nonzero keeps)
+and ``--mask-classes a,b`` (classes of the label maps of ``--semantic-dir`` to ignore, grown by ``--mask-dilate`` pixels) measure
+every view over its kept pixels only, as ``tools/train.py`` takes them; a view whose mask keeps nothing is left out of the
+means.  ``--poses poses.pth`` puts the corrections that run saved onto the cameras
 they were trained on (all cameras, or those ``--holdout`` leaves for training) before anything is rendered from them.  Needs
 a GPU: there is no CPU path.
 """
@@ -25,6 +28,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
 
 READERS = {".ply": "load_ply", ".pth": "load_checkpoint", ".pt": "load_checkpoint", ".splat": "load_splat"}
 HEADER = ("view", "psnr", "ssim", "l1", "mse")
@@ -51,7 +55,10 @@ def parse(argv=None):
                     help="label maps <image name>.npy: also print the mIoU of the rendered labels on the evaluated views")
     ap.add_argument("--semantic-classes", type=int, default=150, help="labels of the maps: 0 .. this - 1, 255 ignored")
     ap.add_argument("--min-share", type=float, default=0.0, help="least share of a Gaussian's votes its class must have")
+    from train import add_mask_arguments, mask_classes
+    add_mask_arguments(ap, semantic=False)
     args = ap.parse_args(argv)
+    args.classes = mask_classes(args, ap.error)
     if not 1 <= args.semantic_classes <= 255 or not 0.0 <= args.min_share <= 1.0:
         ap.error("--semantic-classes must be in 1..255 and --min-share in [0, 1]")
     if Path(args.scene).suffix.lower() not in READERS:
@@ -121,8 +128,15 @@ def main(argv=None):
         print(f"{apply_poses(dataset.cameras, train, args.poses)} pose corrections from {args.poses}")
     if not views:
         raise SystemExit(f"--holdout {args.holdout} selects none of the {len(dataset.cameras)} cameras")
+    masked = {}
+    if args.masks_dir is not None or args.classes:
+        from tinysplat_amd.masks import dataset_masks
+        # (--semantic-dir is taken as given here, as the label maps of the mIoU line are)
+        masks = dataset_masks(dataset, None if args.masks_dir is None else base / args.masks_dir, args.semantic_dir,
+                              args.classes, args.mask_dilate, args.semantic_classes, args.device)
+        masked = {"masks": [masks[i] for i in views]}
     result = evaluate(model, [dataset.cameras[i] for i in views], Targets([dataset.targets.images_u8[i] for i in views]),
-                      args.device, **({"color_correct": True} if args.color_correct else {}),
+                      args.device, **masked, **({"color_correct": True} if args.color_correct else {}),
                       **({"refine_poses": args.refine_poses} if args.refine_poses else {}))
     rows = table_rows(result)
     width = max(len(r[0]) for r in rows)
@@ -130,7 +144,9 @@ def main(argv=None):
     for name, psnr, ssim, l1, _mse in rows:
         print(f"{name:<{width}}  {psnr:9.4f}  {ssim:8.5f}  {l1:8.5f}")
     print(f"{len(views)} views, {model.num_points} Gaussians" + (", colour-corrected" if args.color_correct else "")
-          + (f", poses aligned by {args.refine_poses} steps" if args.refine_poses else ""))
+          + (f", poses aligned by {args.refine_poses} steps" if args.refine_poses else "")
+          + (", over the masks' kept pixels" if masked else "")
+          + (f"; nothing kept in: {', '.join(result.empty)}" if result.empty else ""))
     if args.semantic_dir:
         print(semantic_line(model, dataset.cameras, train, views, args))
     if args.csv:

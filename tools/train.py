@@ -28,7 +28,12 @@ views have no transform.  ``--optimize-poses`` refines every training camera's p
 an SE(3) correction per view, ``--pose-lr`` for both rates, ``--pose-reg`` its decay towards the identity), prints the table of
 corrections at the end and saves them with ``--poses-out``; the saved scene then lives in the refined cameras' frame, so with
 ``--eval-holdout`` every held-out view is first aligned to its image by ``--eval-refine-poses K`` steps with the Gaussians
-frozen (30 unless given; 0 and without ``--optimize-poses``: the cameras as they are).  Flags the reference's parser has keep
+frozen (30 unless given; 0 and without ``--optimize-poses``: the cameras as they are).  ``--masks-dir D`` reads one mask per
+photo from ``<dataset-dir>/D`` (``a.jpg.png``, COLMAP's ``mask_path`` convention, then ``a.png``, then ``a.jpg.npy``; nonzero
+keeps the pixel; a mask of the photo's size is undistorted with it) and ``--mask-classes a,b`` with ``--semantic-dir D`` ignores
+those classes of the label maps ``<dataset-dir>/D/<image name>.npy``, grown by ``--mask-dilate`` pixels (10, the SSIM
+window's reach); both together combine.  Ignored pixels take no part in the loss (``tinysplat_amd.masks``), and with
+``--eval-holdout`` the held-out views are measured over their kept pixels only.  Flags the reference's parser has keep
 its names and defaults.  Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -161,6 +166,46 @@ def print_corrections(poses, cameras) -> None:
     print(f"{'mean':<32} {'':>7} {np.degrees(table[:, 0].mean()):>15.5f} {table[:, 1].mean():>12.6f}")
 
 
+def _mask_parser():
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    add_mask_arguments(ap.add_argument_group("masks"))
+    return ap
+
+
+def add_mask_arguments(g, semantic: bool = True):
+    """The mask options tools/train.py and tools/eval.py share."""
+    g.add_argument("--masks-dir", type=str, default=None, help="below --dataset-dir: one mask per photo, nonzero keeps")
+    g.add_argument("--mask-classes", type=str, default=None, metavar="a,b",
+                   help="ignore these classes of the label maps of --semantic-dir")
+    g.add_argument("--mask-dilate", type=int, default=10, help="grow what --mask-classes ignores by this many pixels")
+    if semantic:
+        g.add_argument("--semantic-dir", type=str, default=None, help="below --dataset-dir: <image name>.npy label maps")
+        g.add_argument("--semantic-classes", type=int, default=150, help="labels of the maps: 0 .. this - 1, 255 ignored")
+
+
+def mask_classes(args, error):
+    """--mask-classes as a list of labels, checked -> [] where not given."""
+    if args.mask_classes is None:
+        return []
+    try:
+        classes = [int(v) for v in args.mask_classes.split(",") if v.strip()]
+    except ValueError:
+        error("--mask-classes must be a comma-separated list of labels")
+    if not classes or args.semantic_dir is None:
+        error("--mask-classes needs at least one label and --semantic-dir")
+    if args.mask_dilate < 0 or not 1 <= args.semantic_classes <= 255 or any(not 0 <= c < args.semantic_classes for c in classes):
+        error("--mask-dilate must not be negative and the labels of --mask-classes must lie in [0, --semantic-classes)")
+    return classes
+
+
+def parse_masks(argv=None):
+    """The mask options, a namespace of its own like the depth prior's; ``classes`` holds the labels to drop."""
+    ap = _mask_parser()
+    args = ap.parse_known_args(argv)[0]
+    args.classes = mask_classes(args, ap.error)
+    return args
+
+
 def _frame_parser():
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     g = ap.add_argument_group("scene frame")
@@ -184,6 +229,8 @@ def parse(argv=None):
     _strategy, argv = strategy_ap.parse_known_args(argv)
     _appearance, argv = appearance_ap.parse_known_args(argv)
     _frame, argv = _frame_parser().parse_known_args(argv)
+    parse_masks(argv)
+    _masks, argv = _mask_parser().parse_known_args(argv)
     parse_pose(argv)
     pose_ap = _pose_parser()
     _pose, argv = pose_ap.parse_known_args(argv)
@@ -192,6 +239,7 @@ def parse(argv=None):
                                  strategy_ap.format_help().split("\n\n", 1)[-1] + "\n" +
                                  appearance_ap.format_help().split("\n\n", 1)[-1] + "\n" +
                                  _frame_parser().format_help().split("\n\n", 1)[-1] + "\n" +
+                                 _mask_parser().format_help().split("\n\n", 1)[-1] + "\n" +
                                  pose_ap.format_help().split("\n\n", 1)[-1])
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--sh-degree", type=int, default=3)
@@ -237,7 +285,7 @@ def normalize_scene(dataset):
 
 def main(argv=None):
     args, depth, strategy, look = parse(argv), parse_depth(argv), parse_strategy(argv), parse_appearance(argv)
-    posing = parse_pose(argv)
+    posing, masking = parse_pose(argv), parse_masks(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: tinysplat_amd has no CPU path")
@@ -253,6 +301,15 @@ def main(argv=None):
         normalize_scene(dataset)
     model = from_pcd(dataset.pcd, sh_degree=args.sh_degree, device=args.device)
     cameras, targets, evaluator, corrected = dataset.cameras, dataset.targets, None, None
+    masks = held_masks = None
+    if masking.masks_dir is not None or masking.classes:
+        from tinysplat_amd.masks import dataset_masks, mask_coverage
+        masks = dataset_masks(dataset, None if masking.masks_dir is None else base / masking.masks_dir,
+                              None if masking.semantic_dir is None else base / masking.semantic_dir, masking.classes,
+                              masking.mask_dilate, masking.semantic_classes, args.device)
+        shares = [mask_coverage(m) for m in masks]
+        print(f"masks for {len(masks)} cameras: {100.0 * sum(shares) / len(shares):.1f} % of the pixels kept "
+              f"(least {100.0 * min(shares):.1f} %)")
     depth_targets = depth_schedule = None
     if depth.regularize_depth:
         from tinysplat_amd import DepthPriors
@@ -272,15 +329,18 @@ def main(argv=None):
         held = ([cameras[i] for i in test], Targets([targets.images_u8[i] for i in test]))
         cameras, targets = [cameras[i] for i in train], Targets([targets.images_u8[i] for i in train])
         depth_targets = None if depth_targets is None else [depth_targets[i] for i in train]
+        if masks is not None:
+            masks, held_masks = [masks[i] for i in train], [masks[i] for i in test]
+        masked = {} if held_masks is None else {"masks": held_masks}
         evaluator = Evaluator(model, *held, args.device, args.eval_interval or len(cameras),
                               on_result=lambda row, _result: print(Evaluator.format(row), flush=True),
-                              csv_path=args.metrics_csv, refine_poses=posing.eval_refine_poses)
+                              csv_path=args.metrics_csv, refine_poses=posing.eval_refine_poses, **masked)
         if look.appearance != "none":                         # held-out views have no transform: also measure them colour-corrected
             cc_csv = None if args.metrics_csv is None else \
                 str(Path(args.metrics_csv).with_name(Path(args.metrics_csv).stem + "_cc" + Path(args.metrics_csv).suffix))
             corrected = Evaluator(model, *held, args.device, args.eval_interval or len(cameras), csv_path=cc_csv,
                                   on_result=lambda row, _result: print("colour-corrected | " + Evaluator.format(row), flush=True),
-                                  color_correct=True, refine_poses=posing.eval_refine_poses)
+                                  color_correct=True, refine_poses=posing.eval_refine_poses, **masked)
         print(f"{len(cameras)} training cameras, {len(test)} held out")
     if strategy.strategy == "mcmc":
         from tinysplat_amd.mcmc import McmcConfig, McmcDensifier
@@ -321,6 +381,8 @@ def main(argv=None):
             extra["appearance"] = appearance
         if poses is not None:
             extra["poses"] = poses
+        if masks is not None:
+            extra["masks"] = masks
         out = fit(model, cameras, targets, args.device, args.max_iter, max_sh_degree=args.sh_degree,
                   densifier=densifier, on_step=on_step if callbacks else None, lr_schedule=lr_schedule, **extra)
     finally:
