@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define TS_ABI_VERSION 8
+#define TS_ABI_VERSION 9
 
 #define TS_E_BADARG (-1)  /* null pointer / negative size / unsupported channel count */
 #define TS_E_DEGREE (-2)  /* SH degree out of range or exceeds stored coefficients */
@@ -635,58 +635,57 @@ int ts_shard_rank_bwd_b(const ts_frame* fo, const ts_rank_step* r, void* stream)
 
 /* ============ training-step ops around the path (scripts/train.py:58-63,97) ===== */
 
-/* Photometric loss of the training step and its gradient w.r.t. the rendered image:
- *   L = c_l1 * mean|X - Y| + c_ssim * (1 - SSIM(X, Y))     (train.py:58-63 with c = 1-lambda, lambda)
- * X = image[H,W,3], Y = target[H,W,3], HWC float32.  SSIM as pytorch_msssim.SSIM(data_range=1,
- * size_average=True, channel=3) (model_gaussian.py:57): 11-tap Gaussian window (sigma 1.5), valid
- * filtering, K = (0.01, 0.03).  The entry writes per-block partial sums to the tail of `ws`
- * (2 floats per 32x32 tile: SSIM-map sum, |X-Y| sum) and, if v_image != NULL,
- *   v_image = w_l1 * sign(X - Y) + w_ssim * dSSIMsum/dX      (caller passes w_l1 = c_l1 / (3 H W),
- *                                                             w_ssim = -c_ssim / (3 (H-10)(W-10))).
- * ws: >= ts_photometric_ws_floats(H, W) floats; the partial sums ({ssim, l1, depth l1} per wave of pass 1; any
- * number of triples: (ts_photometric_ws_floats - 9 (H-10)(W-10)) / 3) start at ws + 9 (H-10)(W-10). */
+/* Photometric loss of the training step (train.py:58-69) and its gradient w.r.t. the rendered image, one descriptor
+ * for every image layout, with or without a mask:
+ *   L = c_l1 * mean|X - Y| + c_ssim * (1 - SSIM(X, Y)) [+ c_depth * mean|depth - D|]   (c = 1-lambda, lambda, lambda_depth)
+ * X = the first three floats of every pixel of `image`, Y = target[H,W,3], D = depth_target[H,W], float32.  SSIM as
+ * pytorch_msssim.SSIM(data_range=1, size_average=True, channel=3) (model_gaussian.py:57): 11-tap Gaussian window
+ * (sigma 1.5), valid filtering, K = (0.01, 0.03).  The rendered depth is channel 3 of `image` (pixel_floats == 4: the
+ * compositing kernels' own RGB + depth output, no slicing / re-packing of a 33 MB image and its gradient per step) or
+ * the plane `depth` (pixel_floats == 3: ts_raster_fwd_planes); without either there is no depth term.
+ * The entry leaves the three partial-derivative maps and the partial sums in `ws` - {ssim, l1, depth l1} per wave of
+ * pass 1 at ws + 9 (H-10)(W-10), (ts_photometric_ws_floats - 9 (H-10)(W-10)) / 3 triples - and, if v_image != NULL,
+ *   v_image[..., :3] = w_l1 * sign(X - Y) + w_ssim * dSSIMsum/dX      (caller passes w_l1 = c_l1 / (3 H W),
+ *   depth gradient   = w_depth * sign(depth - D)                        w_ssim = -c_ssim / (3 (H-10)(W-10)),
+ *                                                                       w_depth = c_depth / (H W))
+ * the depth gradient going to v_image[..., 3] (pixel_floats == 4) or to the plane v_depth; it is 0 everywhere without
+ * a depth target.
+ * TS_LOSS_MASKED (csrc/mask_math.h): byte b of mask[H,W] weighs its pixel by m = b / 255.0f
+ * (255: the pixel counts, 0: it is ignored).  The loss is then evaluated on the substituted image X' = blend(X, Y, m)
+ * - X where b == 255, fmaf(m, X - Y, Y) otherwise - with the depth term m |depth - D| and the gradients
+ *   v_image = m * dL/dX',   depth gradient = m * w_depth * sign(depth - D).
+ * Same weights (NOT renormalised by the mask's area), same workspace and partial sums.  An all-255 mask gives the
+ * unmasked bits; a pixel with b == 0 gets a gradient of exactly zero.
+ * TS_E_BADARG, before any launch: a NULL descriptor, image, target or ws; height or width <= 10; pixel_floats other
+ * than 3 or 4; unknown flag bits; TS_LOSS_MASKED with a NULL mask, or a mask without the flag; a depth plane with
+ * pixel_floats == 4; a depth target with neither a fourth channel nor a depth plane; v_depth without a depth plane or
+ * without v_image. */
 int64_t ts_photometric_ws_floats(int32_t height, int32_t width);
-/* Same loss on the compositing kernels' own output: `image` has pixel_floats (3 or 4) floats per
- * pixel; with 4, channel 3 is the rendered depth and, when depth_target[H,W] != NULL, the depth L1 of
- * train.py:65-69 is evaluated too: per-tile sums {ssim, l1, depth l1} at ws + 9 (H-10)(W-10) (3 per
- * tile) and v_image[..., 3] = w_depth * sign(depth - target) (0 without a target).  v_image has the
- * layout of `image`.  Saves slicing / re-packing a 33 MB image and its gradient per training step. */
-int ts_photometric_loss_rgbd(int32_t height, int32_t width, int32_t pixel_floats, const float* image,
-                             const float* target, const float* depth_target, float w_l1,
-                             float w_ssim, float w_depth, float* ws, float* v_image, void* stream);
-int ts_photometric_loss(int32_t height, int32_t width, const float* image, const float* target,
-                        float w_l1, float w_ssim, float* ws, float* v_image, void* stream);
-/* ABI 5: the same loss on the frame as two planes (ts_raster_fwd_planes): image[H,W,3], depth[H,W] (may be NULL
- * without a depth target), gradients v_image[H,W,3] and v_depth[H,W] (NULL: not wanted; v_depth = 0 everywhere
- * without a depth target).  Sums as ts_photometric_loss_rgbd. */
-int ts_photometric_loss_planes(int32_t height, int32_t width, const float* image, const float* depth,
-                               const float* target, const float* depth_target, float w_l1, float w_ssim,
-                               float w_depth, float* ws, float* v_image, float* v_depth, void* stream);
-/* ABI 8: the loss VALUE from the partial sums an entry above left in `ws` (same height, width and weights):
+#define TS_LOSS_MASKED 1
+typedef struct ts_loss {
+    int32_t height, width;
+    int32_t pixel_floats;        /* 3 or 4: floats per pixel of image and v_image; 4: channel 3 is the depth */
+    int32_t flags;               /* TS_LOSS_MASKED: mask is read (the masked kernels); 0: mask must be NULL */
+    const float* image;          /* [H, W, pixel_floats] */
+    const float* depth;          /* [H, W] plane, only with pixel_floats == 3; NULL otherwise */
+    const float* target;         /* [H, W, 3] */
+    const float* depth_target;   /* [H, W] or NULL: no depth term */
+    const uint8_t* mask;         /* [H, W] */
+    float w_l1, w_ssim, w_depth;
+    float* ws;                   /* >= ts_photometric_ws_floats(H, W) */
+    float* v_image;              /* layout of image, or NULL: forward only */
+    float* v_depth;              /* [H, W] or NULL; only with a depth plane and v_image */
+} ts_loss;
+int32_t ts_loss_struct_bytes(void);      /* sizeof(ts_loss): bindings check their mirror against it */
+int ts_photometric_loss_rgbd(const ts_loss* loss, void* stream);
+/* ABI 8: the loss VALUE from the partial sums the entry above left in `ws` (same height, width and weights):
  *   out4 = {loss, mean|X - Y|, SSIM, mean|depth - depth_target|}   (device floats; sums taken in double, fixed order)
  * with loss = (1 - lambda) * out4[1] + lambda * (1 - out4[2]) + lambda_depth * out4[3] as the weights encode it
  * (train.py:58-69).  One small launch instead of a dozen one-element tensor operations on the caller's side. */
 int ts_photometric_loss_reduce(int32_t height, int32_t width, float w_l1, float w_ssim, float w_depth,
                                const float* ws, float* out4, void* stream);
-/* The masked loss (csrc/mask_math.h).  Additive entries: the ABI version is unchanged.
- * mask: uint8 [height, width]; byte b weighs its pixel by m = b / 255.0f (255: the pixel counts, 0: it is ignored).
- * Each entry is its sibling above evaluated on the substituted image X' = blend(X, Y, m) - X where b == 255,
- * fmaf(m, X - Y, Y) otherwise - with the depth term m |depth - depth_target| and the gradients
- *   v_image = m * dL/dX',   v_depth (or v_image[..., 3]) = m * w_depth * sign(depth - depth_target).
- * Same weights (NOT renormalised by the mask's area), same workspace (ts_photometric_ws_floats) and layout of the
- * partial sums, same ts_photometric_loss_reduce afterwards.  An all-255 mask gives the sibling's bits; a pixel with
- * b == 0 gets a gradient of exactly zero.  TS_E_BADARG, before any launch: what the sibling refuses, and a NULL mask.
- * ts_mask_blend: out[height, width, 3] <- X' for image, target [height, width, 3] (height, width >= 1). */
-int ts_photometric_loss_rgbd_masked(int32_t height, int32_t width, int32_t pixel_floats, const float* image,
-                                    const float* target, const float* depth_target, const uint8_t* mask, float w_l1,
-                                    float w_ssim, float w_depth, float* ws, float* v_image, void* stream);
-int ts_photometric_loss_masked(int32_t height, int32_t width, const float* image, const float* target,
-                               const uint8_t* mask, float w_l1, float w_ssim, float* ws, float* v_image,
-                               void* stream);
-int ts_photometric_loss_planes_masked(int32_t height, int32_t width, const float* image, const float* depth,
-                                      const float* target, const float* depth_target, const uint8_t* mask,
-                                      float w_l1, float w_ssim, float w_depth, float* ws, float* v_image,
-                                      float* v_depth, void* stream);
+/* ts_mask_blend: out[height, width, 3] <- the substituted image X' of TS_LOSS_MASKED for image, target
+ * [height, width, 3] (height, width >= 1). */
 int ts_mask_blend(int32_t height, int32_t width, const float* image, const float* target, const uint8_t* mask,
                   float* out, void* stream);
 

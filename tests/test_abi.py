@@ -36,7 +36,7 @@ def test_binding_covers_the_header_and_version_matches():
     from tinysplat_amd import _lib
     assert sorted(_lib.SIGNATURES) == _declared()
     lib = _lib.load()
-    assert lib.ts_abi_version() == _lib.ABI_VERSION == 8
+    assert lib.ts_abi_version() == _lib.ABI_VERSION == 9
     assert lib.ts_scan_ws_ints(1) >= 1 and lib.ts_scan_ws_ints(10_000_000) >= 10_000_000 // 1024
     # the loss workspace: three maps x three channels of (H-10)(W-10) floats, then one {ssim, l1, depth} triple per wave
     # of the sliding-window pass - four waves per workgroup, 64 map columns x `seg` map rows each, seg in [8, 64] chosen so
@@ -80,6 +80,7 @@ def test_binding_covers_the_header_and_version_matches():
     assert ctypes.sizeof(_lib.TsCamera) == 56        # incl. wide_tiles + hints (ABI 3; the second word was `reserved` until round 4)
     assert ctypes.sizeof(_lib.TsStripes) == 4 * (_lib.MAX_RANKS + 2)
     assert lib.ts_frame_struct_bytes() == ctypes.sizeof(_lib.TsFrame)
+    assert lib.ts_loss_struct_bytes() == ctypes.sizeof(_lib.TsLoss)
     assert lib.ts_frame_fwd_project(None, None) == -1 and lib.ts_frame_bwd_params(None, None) == -1
     # the binding's names for the header's flag bits and hints
     defines = dict(re.findall(r"^#define TS_((?:FRAME|RASTER|HINT)_[A-Z_]+)[ \t]+(\d+|\(1 << \d+\))",

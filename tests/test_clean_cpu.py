@@ -258,4 +258,4 @@ def test_entry_argument_checks():
     assert lib.ts_clean_components(8, 0, None, None, p, None) == -1      # the labels are still written
     assert lib.ts_clean_components(8, 0, None, p, None, None) == -1
     assert lib.ts_clean_components(0, 0, None, None, None, None) == 0
-    assert lib.ts_abi_version() == 8 == _lib.ABI_VERSION
+    assert lib.ts_abi_version() == 9 == _lib.ABI_VERSION

@@ -115,7 +115,7 @@ def test_entry_argument_checks():
     # nothing to do: no launch, whatever the pointers; the degree is still checked
     assert call(a1=0) == 0 and lib.ts_field_colors(20, 0, None, None, None, None, None, None, 0, 0, None, None) == 0
     assert call(a1=0, a9=4) == -2 and call(a0=0, a1=0) == -1
-    assert lib.ts_abi_version() == 8 == _lib.ABI_VERSION
+    assert lib.ts_abi_version() == 9 == _lib.ABI_VERSION
 
 
 def test_config_and_mesh_fields():

@@ -145,7 +145,7 @@ def test_entry_argument_checks():
     assert lib.ts_segment_sum(8, 2, 4, p, p, p, p, p, p, None) == bad
     assert lib.ts_segment_sum(8, 1, 0, p, p, p, p, p, p, None) == bad
     assert lib.ts_segment_sum(8, 1, 4, p, None, p, p, p, p, None) == bad
-    assert lib.ts_abi_version() == 8
+    assert lib.ts_abi_version() == 9
 
 
 def test_density_entries_refuse_cpu_tensors_and_small_models():

@@ -172,7 +172,7 @@ def test_new_symbols_are_declared_exported_and_bound():
     lib = _lib.load()
     for name in ENTRIES:
         assert re.search(rf"\b{name}\s*\(", header) and name in _lib.SIGNATURES and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 8 and lib.ts_abi_version() == 8
+    assert _lib.ABI_VERSION == 9 and lib.ts_abi_version() == 9
     import tinysplat_amd
     for name in ("DepthPriors", "SparseDepth", "match_scale", "sparse_depth"):
         assert name in tinysplat_amd.__all__ and hasattr(tinysplat_amd, name)

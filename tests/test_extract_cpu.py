@@ -236,7 +236,7 @@ def test_entry_argument_checks():
         assert lib.ts_extract_chunk_bytes(n, rays, steps) == bad
     one, two = lib.ts_extract_chunk_bytes(2000, 1000, 21), lib.ts_extract_chunk_bytes(2000, 2000, 21)
     assert 0 < one < two and one >= lib.ts_knn_ws_bytes(2000, 21000, 16) + 1000 * 21 * (12 + 128)
-    assert lib.ts_abi_version() == 8
+    assert lib.ts_abi_version() == 9
 
 
 def test_extraction_refuses_cpu_tensors_and_small_models():

@@ -152,6 +152,27 @@ def test_timed_training_step_is_the_untimed_step(monkeypatch):
     _check_table(table, TRAIN_KEYS)
 
 
+def test_timed_masked_training_step_records_the_loss_under_its_one_name(monkeypatch):
+    """A masked step issues the entries of an unmasked one: the loss pair appears under ``ts_photometric_loss_rgbd``
+    whichever layout and mask the step ran, once."""
+    from tinysplat_amd.synthetic import make_scene
+    from tinysplat_amd.training import TrainStep
+    n, sh = 3000, 1
+    model, cam = make_scene(n, sh, W, H, seed=21, scale_mult=12.0)
+    model = model.to(DEV)
+    with torch.no_grad():
+        tgt, extras = GaussianRasterizer(model, None, device=torch.device(DEV))(cam, None, sh)
+    tgt, tgt_d = tgt.clone(), extras["depth"].clone()
+    _set(monkeypatch, {})
+    for nm in NAMES:
+        setattr(model, nm, getattr(model, nm).detach().clone())
+    step = TrainStep(model, DEV)
+    mask = torch.full((H, W), 255, dtype=torch.uint8, device=DEV)
+    _, table = _timed(lambda: step(cam, tgt, tgt_d, mask=mask), True)
+    assert step.optimizer.fused_steps == 1
+    _check_table(table, TRAIN_KEYS)
+
+
 def test_timed_sharded_frame_is_the_untimed_frame(monkeypatch):
     model, cam = scene_args(2000, 1, W, H, seed=24, scale_mult=12.0)
     model = model.to(DEV)

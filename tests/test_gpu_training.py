@@ -59,7 +59,7 @@ def test_frame_loss_on_rgbd_output_equals_the_separate_losses(h, w, with_depth):
 
 @pytest.mark.parametrize("h,w,with_depth", [(64, 96, True), (77, 131, False), (120, 50, True)])
 def test_planes_loss_is_the_frame_loss_bit_for_bit(h, w, with_depth):
-    """ABI 5: the fused loss on rgb[H,W,3] + depth[H,W] (ts_photometric_loss_planes) against the same loss on the
+    """ABI 5: the fused loss on rgb[H,W,3] + depth[H,W] (ts_loss with a depth plane) against the same loss on the
     interleaved [H,W,4] frame: values and both gradient planes identical; no depth gradient without a target."""
     g = torch.Generator().manual_seed(h * w)
     frame = torch.rand(h, w, 4, generator=g)
@@ -80,6 +80,28 @@ def test_planes_loss_is_the_frame_loss_bit_for_bit(h, w, with_depth):
         assert torch.equal(dep.grad, xd.grad[:, :, 3])
     else:
         assert dep.grad is None or torch.all(dep.grad == 0)
+
+
+@pytest.mark.parametrize("h,w", [(11, 11), (21, 75)])
+def test_photometric_loss_is_the_planes_loss_without_a_depth_target_bit_for_bit(h, w):
+    """The three-channel loss and the two-plane loss are one implementation: without a depth target the depth plane is
+    never compared with anything, so loss, l1, ssim and the image gradient are the same bytes whatever the plane holds.
+    The smallest image, and the smallest with a second column block's worth of halo."""
+    g = torch.Generator().manual_seed(h * w)
+    img = torch.rand(h, w, 3, generator=g)
+    tgt = (img + 0.2 * torch.randn(h, w, 3, generator=g)).clamp(0, 1).to(DEV)
+    dep = (2.0 + 8.0 * torch.rand(h, w, generator=g)).to(DEV).requires_grad_(True)
+    x = img.to(DEV).requires_grad_(True)
+    one = photometric_loss(x * 1.0, tgt, 0.2)
+    (2.0 * one[0]).backward()
+    y = img.to(DEV).requires_grad_(True)
+    two = planes_loss(y * 1.0, dep * 1.0, tgt, None, 0.2, 0.3)
+    (2.0 * two[0]).backward()
+    assert len(one) == 3 and len(two) == 4
+    for a, b in zip(one, two):
+        assert torch.equal(a, b)
+    assert torch.equal(x.grad, y.grad) and x.grad.abs().max().item() > 0.0
+    assert dep.grad is None or torch.all(dep.grad == 0)
 
 
 @pytest.mark.parametrize("h,w", [(11, 11), (11, 75), (12, 11), (55, 139), (57, 74), (99, 75), (100, 203)])

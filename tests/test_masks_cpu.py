@@ -149,18 +149,34 @@ def test_argument_errors_of_the_masked_entries_without_a_gpu():
     from tinysplat_amd import _lib
     lib = _lib.load()
     f, b, d = (ctypes.c_float * 4)(), (ctypes.c_uint8 * 4)(), (ctypes.c_double * 8)()
-    # a null mask; H or W <= 10; the siblings' own refusals
-    assert lib.ts_photometric_loss_masked(64, 64, f, f, None, 0.1, -0.1, f, None, None) == -1
-    assert lib.ts_photometric_loss_masked(10, 64, f, f, b, 0.1, -0.1, f, None, None) == -1
-    assert lib.ts_photometric_loss_masked(64, 10, f, f, b, 0.1, -0.1, f, None, None) == -1
-    assert lib.ts_photometric_loss_masked(64, 64, None, f, b, 0.1, -0.1, f, None, None) == -1
-    assert lib.ts_photometric_loss_rgbd_masked(64, 64, 4, f, f, None, None, 0.1, -0.1, 0.0, f, None, None) == -1
-    assert lib.ts_photometric_loss_rgbd_masked(64, 64, 5, f, f, None, b, 0.1, -0.1, 0.0, f, None, None) == -1
-    assert lib.ts_photometric_loss_rgbd_masked(64, 64, 3, f, f, f, b, 0.1, -0.1, 0.1, f, None, None) == -1   # depth target, 3 floats
-    assert lib.ts_photometric_loss_rgbd_masked(8, 64, 4, f, f, None, b, 0.1, -0.1, 0.0, f, None, None) == -1
-    assert lib.ts_photometric_loss_planes_masked(64, 64, f, f, f, None, None, 0.1, -0.1, 0.0, f, None, None, None) == -1
-    assert lib.ts_photometric_loss_planes_masked(64, 9, f, f, f, None, b, 0.1, -0.1, 0.0, f, None, None, None) == -1
-    assert lib.ts_photometric_loss_planes_masked(64, 64, f, None, f, f, b, 0.1, -0.1, 0.1, f, None, None, None) == -1  # depth target, no depth
+    P = lambda a: ctypes.cast(a, ctypes.c_void_p).value     # noqa: E731
+
+    def refused(**fields):
+        """the entry's answer to a descriptor that is sound (64 x 64, 3 floats, image, target and workspace set) but for
+        ``fields``"""
+        loss = _lib.TsLoss(**{**dict(height=64, width=64, pixel_floats=3, image=P(f), target=P(f), w_l1=0.1, w_ssim=-0.1,
+                                     ws=P(f)), **fields})
+        return lib.ts_photometric_loss_rgbd(ctypes.byref(loss), None) == -1
+    masked = dict(flags=_lib.LOSS_MASKED, mask=P(b))
+    rgbd, planes = dict(pixel_floats=4), dict(depth=P(f))
+    assert lib.ts_photometric_loss_rgbd(None, None) == -1                                    # no descriptor
+    # the mask and its flag come together; no other flag bit exists
+    assert refused(flags=_lib.LOSS_MASKED) and refused(**rgbd, flags=_lib.LOSS_MASKED)
+    assert refused(**planes, flags=_lib.LOSS_MASKED)
+    assert refused(mask=P(b)) and refused(**rgbd, mask=P(b)) and refused(**planes, mask=P(b))
+    assert refused(flags=2) and refused(**{**masked, "flags": 3}) and refused(flags=-2)
+    # H or W <= 10, a null image, target or workspace, floats per pixel other than 3 or 4: with and without the mask
+    for more in ({}, masked):
+        assert refused(height=10, **more) and refused(width=10, **more)
+        assert refused(height=8, **rgbd, **more) and refused(width=9, **planes, **more)
+        assert refused(image=None, **more) and refused(target=None, **more) and refused(ws=None, **more)
+        assert refused(pixel_floats=5, **more) and refused(pixel_floats=2, **more)
+        # a depth target needs a rendered depth: the fourth channel or the plane, and never both
+        assert refused(depth_target=P(f), w_depth=0.1, **more)
+        assert refused(**rgbd, **planes, **more)
+        # the depth plane's gradient needs the plane, and the image's gradient beside it
+        assert refused(v_image=P(f), v_depth=P(f), **more) and refused(**rgbd, v_image=P(f), v_depth=P(f), **more)
+        assert refused(**planes, v_depth=P(f), **more)
     assert lib.ts_mask_blend(64, 64, f, f, None, f, None) == -1 and lib.ts_mask_blend(0, 64, f, f, b, f, None) == -1
     assert lib.ts_mask_blend(64, 64, f, f, b, None, None) == -1
     # the metrics entry: a null mask, small sizes, and a row whose byte offsets do not fit 32 bits

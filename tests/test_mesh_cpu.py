@@ -193,7 +193,7 @@ def test_entry_argument_checks():
         assert lib.ts_mesh_chunk_bytes(n, bricks) == bad
     one, two = lib.ts_mesh_chunk_bytes(2000, 10), lib.ts_mesh_chunk_bytes(2000, 20)
     assert 0 < one < two and one >= lib.ts_knn_ws_bytes(2000, 7290, 16) + 7290 * (12 + 128 + 4) + 10 * 20
-    assert lib.ts_abi_version() == 8
+    assert lib.ts_abi_version() == 9
 
 
 def test_mesh_config_validation():

@@ -431,4 +431,4 @@ def test_entry_argument_checks():
     assert lib.ts_simplify_faces(0, 4, p, p, p, p, None) == -1
     assert lib.ts_simplify_faces(8, 0, None, None, None, None, None) == 0
     assert lib.ts_simplify_faces(0, 0, None, None, None, None, None) == 0
-    assert lib.ts_abi_version() == 8 == _lib.ABI_VERSION
+    assert lib.ts_abi_version() == 9 == _lib.ABI_VERSION

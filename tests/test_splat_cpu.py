@@ -171,7 +171,7 @@ def test_entry_argument_checks():
         assert lib.ts_splat_unpack(*a) == -1, i
     assert lib.ts_splat_unpack(-1, *good[1:]) == -1 and lib.ts_splat_unpack(4, ctypes.c_void_p(8), *good[2:]) == -1
     assert lib.ts_splat_unpack(0, *([None] * 7)) == 0
-    assert lib.ts_abi_version() == 8 == _lib.ABI_VERSION
+    assert lib.ts_abi_version() == 9 == _lib.ABI_VERSION
 
 
 def test_load_splat_refuses_a_file_that_is_not_whole_records(tmp_path):

@@ -407,7 +407,7 @@ def test_entries_report_argument_errors_without_a_gpu():
     assert lib.ts_box_mask(-1, f12, None, None, None) == -1 and lib.ts_box_mask(0, None, None, None, None) == 0
     assert lib.ts_box_mask(4, None, 1, 1, None) == -1 and lib.ts_box_mask(4, f12, None, 1, None) == -1
     assert lib.ts_box_mask(4, f12, 1, None, None) == -1 and lib.ts_box_mask(4, bad12, 1, 1, None) == -1
-    assert lib.ts_abi_version() == 8
+    assert lib.ts_abi_version() == 9
 
 
 def test_module_refuses_cpu_tensors_and_held_models():

@@ -211,7 +211,7 @@ def test_new_symbols_are_declared_exported_and_bound():
     lib = _lib.load()
     for name in ENTRIES:
         assert re.search(rf"\b{name}\s*\(", header) and name in _lib.SIGNATURES and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 8 and lib.ts_abi_version() == 8
+    assert _lib.ABI_VERSION == 9 and lib.ts_abi_version() == 9
     assert lib.ts_tsdf_camera_bytes() == ctypes.sizeof(_lib.TsTsdfCamera)
     import tinysplat_amd
     for name in ("FusionConfig", "fuse_depth_maps", "render_depth_alpha", "extract_mesh_tsdf"):

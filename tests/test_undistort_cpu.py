@@ -239,7 +239,7 @@ def test_entry_argument_checks():
     a = list(good)
     a[9] = ctypes.c_void_p(260)                                            # out not 16-byte aligned
     assert lib.ts_undistort_image(*a) == -1
-    assert lib.ts_abi_version() == 8 == _lib.ABI_VERSION
+    assert lib.ts_abi_version() == 9 == _lib.ABI_VERSION
 
 
 def test_cpu_tensors_and_bad_arguments_are_refused():

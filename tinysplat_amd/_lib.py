@@ -14,7 +14,7 @@ from pathlib import Path
 # compile-time switches in a process of their own); a variant build needs TS_ALLOW_VARIANT_LIB=1 as usual
 LIB_PATH = Path(os.environ["TS_LIB_PATH"]) if os.environ.get("TS_LIB_PATH") else \
     Path(__file__).resolve().parent / "csrc" / "libtinysplat_hip.so"
-ABI_VERSION = 8
+ABI_VERSION = 9
 HINT_BALANCED_WALK = 1           # ts_camera.hints: TS_HINT_BALANCED_WALK
 HINT_COOP_SPLIT = 1 << 20        # ts_camera.hints: TS_HINT_COOP_SPLIT
 # the header's TS_RASTER_* and TS_FRAME_* flag bits under the same names (tests/test_abi.py compares them)
@@ -120,6 +120,19 @@ class TsTsdfCamera(ctypes.Structure):
     _fields_ = [("view", c_float * 12), ("proj", c_float * 12), ("planes", c_float * (TSDF_PLANES * 5)),
                 ("width", c_int32), ("height", c_int32), ("depth", c_void_p)]
 
+
+LOSS_MASKED = 1                  # TS_LOSS_MASKED
+
+
+class TsLoss(ctypes.Structure):
+    """struct ts_loss of include/tinysplat_hip.h: the training loss on any image layout, with or without a mask.
+    Pointers travel as integer addresses; unset ones stay NULL."""
+    _fields_ = ([("height", c_int32), ("width", c_int32), ("pixel_floats", c_int32), ("flags", c_int32)]
+                + [(name, c_void_p) for name in ("image", "depth", "target", "depth_target", "mask")]
+                + [("w_l1", c_float), ("w_ssim", c_float), ("w_depth", c_float)]
+                + [(name, c_void_p) for name in ("ws", "v_image", "v_depth")])
+
+
 ENTRY_PROBE = ctypes.CFUNCTYPE(None, ctypes.c_char_p, c_int32, c_void_p)      # ts_entry_probe
 
 # name -> (restype, argtypes); mirrors include/tinysplat_hip.h declaration by declaration
@@ -169,17 +182,9 @@ SIGNATURES = {
     "ts_bench_stream_read": (c_int32, [_P, c_int64, _P, _P]),
     "ts_bench_gather48": (c_int32, [_P, _P, c_int64, _P, _P]),
     "ts_photometric_ws_floats": (c_int64, [c_int32, c_int32]),
-    "ts_photometric_loss": (c_int32, [c_int32, c_int32, _P, _P, c_float, c_float, _P, _P, _P]),
-    "ts_photometric_loss_rgbd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P]),
-    "ts_photometric_loss_planes": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P,
-                                             _P]),
+    "ts_loss_struct_bytes": (c_int32, []),
+    "ts_photometric_loss_rgbd": (c_int32, [POINTER(TsLoss), _P]),
     "ts_photometric_loss_reduce": (c_int32, [c_int32, c_int32, c_float, c_float, c_float, _P, _P, _P]),
-    # the masked loss: the siblings above with a uint8 [H, W] mask behind the targets
-    "ts_photometric_loss_masked": (c_int32, [c_int32, c_int32, _P, _P, _P, c_float, c_float, _P, _P, _P]),
-    "ts_photometric_loss_rgbd_masked": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, c_float, c_float, c_float,
-                                                  _P, _P, _P]),
-    "ts_photometric_loss_planes_masked": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, c_float, c_float, c_float,
-                                                    _P, _P, _P, _P]),
     "ts_mask_blend": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P]),
     "ts_adam_step": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, _P]),
     "ts_sh_colors_bwd_adam": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _ADAM, _P]),
@@ -350,6 +355,8 @@ def load() -> ctypes.CDLL:
         raise HipLibraryError("struct ts_frame: the ctypes mirror does not match the library's layout")
     if lib.ts_rank_step_struct_bytes() != ctypes.sizeof(TsRankStep):
         raise HipLibraryError("struct ts_rank_step: the ctypes mirror does not match the library's layout")
+    if lib.ts_loss_struct_bytes() != ctypes.sizeof(TsLoss):
+        raise HipLibraryError("struct ts_loss: the ctypes mirror does not match the library's layout")
     if lib.ts_tsdf_camera_bytes() != ctypes.sizeof(TsTsdfCamera):
         raise HipLibraryError("struct ts_tsdf_camera: the ctypes mirror does not match the library's layout")
     _lib = lib

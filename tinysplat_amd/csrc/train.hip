@@ -73,7 +73,7 @@ __device__ __forceinline__ void horizontal_strip(const float (*p)[kPatch + 1], i
 // dS/d filt(XY) written to dmaps[3][3 channels][Ho][Wo] (planar), and the L1 sums.
 // X has `xs` floats per pixel (3: an RGB image; 4: the compositing kernels' RGB+depth output, whose
 // channel 3 is compared with the depth target D when D != nullptr, train.py:65-69).
-// Xd (with xs == 3): the depth as its own [H,W] plane (ts_photometric_loss_planes).
+// Xd (with xs == 3): the depth as its own [H,W] plane (ts_loss.depth).
 // A SLIDING WINDOW (round 6).  One wave owns 64 columns
 // of the SSIM map for one colour channel and walks `seg` map rows from the top: a pixel row is read once (64 + 10
 // columns, the next rows already in flight), filtered horizontally through a wave-private LDS line - no workgroup
@@ -564,62 +564,38 @@ int64_t ts_photometric_ws_floats(int32_t height, int32_t width) {
     return 3 * ho * wo * 3 + 3 * waves;
 }
 
-namespace {
-// pass 1 of the loss: per-wave sums behind the three partial-derivative maps in ws
-void launch_ssim_fwd(int height, int width, int xs, const float* image, const float* depth, const float* target,
-                     const float* depth_target, float* ws, hipStream_t s) {
-    const size_t plane3 = (size_t)3 * (height - kHalo) * (width - kHalo) * 3;
-    const int seg = ssim_segment_rows(height - kHalo, width - kHalo);
-    const dim3 grid((width - kHalo + kCols - 1) / kCols, (height - kHalo + seg - 1) / seg);
-    hipLaunchKernelGGL(ssim_fwd_rows_kernel<>, grid, dim3(64 * kRowsWaves), 0, s, height, width, xs, seg, image, depth,
-                       target, depth_target, ws, ws + plane3);
-}
+int32_t ts_loss_struct_bytes(void) { return (int32_t)sizeof(ts_loss); }
 
-// the masked pair: the same grids, workspace and sums as the unmasked entries
-int launch_masked_loss(int height, int width, int xs, const float* image, const float* depth, const float* target,
-                       const float* depth_target, const uint8_t* mask, float w_l1, float w_ssim, float w_depth,
-                       float* ws, float* v_image, float* v_depth, hipStream_t s) {
-    const size_t plane3 = (size_t)3 * (height - kHalo) * (width - kHalo) * 3;
-    const int seg = ssim_segment_rows(height - kHalo, width - kHalo);
-    const dim3 rows_grid((width - kHalo + kCols - 1) / kCols, (height - kHalo + seg - 1) / seg);
-    hipLaunchKernelGGL(ssim_fwd_rows_kernel<const uint8_t*>, rows_grid, dim3(64 * kRowsWaves), 0, s, height, width, xs,
-                       seg, image, depth, target, depth_target, ws, ws + plane3, mask);
-    if (v_image) {
-        const dim3 grid((width + kTile - 1) / kTile, (height + kTile - 1) / kTile);
-        hipLaunchKernelGGL(ssim_bwd_masked_kernel, grid, dim3(kThreads), 0, s, height, width, xs, image, depth, target,
-                           depth_target, mask, ws, w_l1, w_ssim, w_depth, v_image, v_depth);
+// The loss pair on any layout (xs = pixel_floats, Xd = depth, gXd = v_depth), with or without the mask (DESIGN.md
+// section 6v): pass 1 leaves the per-wave sums behind the three partial-derivative maps in ws, pass 2 the gradients.
+int ts_photometric_loss_rgbd(const ts_loss* l, void* stream) {
+    if (!l || l->height <= kHalo || l->width <= kHalo) return TS_E_BADARG;
+    if (l->pixel_floats != 3 && l->pixel_floats != 4) return TS_E_BADARG;
+    if (!l->image || !l->target || !l->ws) return TS_E_BADARG;
+    if ((l->flags & ~TS_LOSS_MASKED) || ((l->flags & TS_LOSS_MASKED) != 0) != (l->mask != nullptr)) return TS_E_BADARG;
+    if (l->depth && l->pixel_floats != 3) return TS_E_BADARG;
+    if (l->depth_target && l->pixel_floats == 3 && !l->depth) return TS_E_BADARG;
+    if (l->v_depth && (!l->depth || !l->v_image)) return TS_E_BADARG;
+    const int H = l->height, W = l->width, xs = l->pixel_floats;
+    const size_t plane3 = (size_t)3 * (H - kHalo) * (W - kHalo) * 3;
+    const int seg = ssim_segment_rows(H - kHalo, W - kHalo);
+    const dim3 rows_grid((W - kHalo + kCols - 1) / kCols, (H - kHalo + seg - 1) / seg), rows_block(64 * kRowsWaves);
+    const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile);
+    hipStream_t s = (hipStream_t)stream;
+    if (!l->mask) {
+        hipLaunchKernelGGL(ssim_fwd_rows_kernel<>, rows_grid, rows_block, 0, s, H, W, xs, seg, l->image, l->depth,
+                           l->target, l->depth_target, l->ws, l->ws + plane3);
+        if (l->v_image)
+            hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(kThreads), 0, s, H, W, xs, l->image, l->depth, l->target,
+                               l->depth_target, l->ws, l->w_l1, l->w_ssim, l->w_depth, l->v_image, l->v_depth);
+    } else {
+        hipLaunchKernelGGL(ssim_fwd_rows_kernel<const uint8_t*>, rows_grid, rows_block, 0, s, H, W, xs, seg, l->image,
+                           l->depth, l->target, l->depth_target, l->ws, l->ws + plane3, l->mask);
+        if (l->v_image)
+            hipLaunchKernelGGL(ssim_bwd_masked_kernel, grid, dim3(kThreads), 0, s, H, W, xs, l->image, l->depth, l->target,
+                               l->depth_target, l->mask, l->ws, l->w_l1, l->w_ssim, l->w_depth, l->v_image, l->v_depth);
     }
     return launch_status();
-}
-}  // namespace
-
-int ts_photometric_loss_rgbd_masked(int32_t height, int32_t width, int32_t pixel_floats, const float* image,
-                                    const float* target, const float* depth_target, const uint8_t* mask, float w_l1,
-                                    float w_ssim, float w_depth, float* ws, float* v_image, void* stream) {
-    if (height <= kHalo || width <= kHalo) return TS_E_BADARG;
-    if (pixel_floats != 3 && pixel_floats != 4) return TS_E_BADARG;
-    if (depth_target && pixel_floats != 4) return TS_E_BADARG;
-    if (!image || !target || !ws || !mask) return TS_E_BADARG;
-    return launch_masked_loss(height, width, (int)pixel_floats, image, nullptr, target, depth_target, mask, w_l1,
-                              w_ssim, w_depth, ws, v_image, nullptr, (hipStream_t)stream);
-}
-
-int ts_photometric_loss_masked(int32_t height, int32_t width, const float* image, const float* target,
-                               const uint8_t* mask, float w_l1, float w_ssim, float* ws, float* v_image,
-                               void* stream) {
-    return ts_photometric_loss_rgbd_masked(height, width, 3, image, target, nullptr, mask, w_l1, w_ssim, 0.0f, ws,
-                                           v_image, stream);
-}
-
-int ts_photometric_loss_planes_masked(int32_t height, int32_t width, const float* image, const float* depth,
-                                      const float* target, const float* depth_target, const uint8_t* mask,
-                                      float w_l1, float w_ssim, float w_depth, float* ws, float* v_image,
-                                      float* v_depth, void* stream) {
-    if (height <= kHalo || width <= kHalo) return TS_E_BADARG;
-    if (!image || !target || !ws || !mask || (depth_target && !depth) || (v_depth && (!depth || !v_image)))
-        return TS_E_BADARG;
-    return launch_masked_loss(height, width, 3, image, depth, target, depth_target, mask, w_l1, w_ssim, w_depth, ws,
-                              v_image, v_depth, (hipStream_t)stream);
 }
 
 int ts_mask_blend(int32_t height, int32_t width, const float* image, const float* target, const uint8_t* mask,
@@ -633,39 +609,6 @@ int ts_mask_blend(int32_t height, int32_t width, const float* image, const float
     return launch_status();
 }
 
-int ts_photometric_loss_rgbd(int32_t height, int32_t width, int32_t pixel_floats, const float* image,
-                             const float* target, const float* depth_target, float w_l1,
-                             float w_ssim, float w_depth, float* ws, float* v_image, void* stream) {
-    if (height <= kHalo || width <= kHalo) return TS_E_BADARG;
-    if (pixel_floats != 3 && pixel_floats != 4) return TS_E_BADARG;
-    if (depth_target && pixel_floats != 4) return TS_E_BADARG;
-    if (!image || !target || !ws) return TS_E_BADARG;
-    const dim3 grid((width + kTile - 1) / kTile, (height + kTile - 1) / kTile);
-    const size_t plane3 = (size_t)3 * (height - kHalo) * (width - kHalo) * 3;
-    hipStream_t s = (hipStream_t)stream;
-    launch_ssim_fwd(height, width, (int)pixel_floats, image, nullptr, target, depth_target, ws, s);
-    if (v_image)
-        hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(kThreads), 0, s, height, width,
-                           (int)pixel_floats, image, (const float*)nullptr, target, depth_target, ws, w_l1, w_ssim,
-                           w_depth, v_image, (float*)nullptr);
-    return launch_status();
-}
-
-int ts_photometric_loss_planes(int32_t height, int32_t width, const float* image, const float* depth,
-                               const float* target, const float* depth_target, float w_l1, float w_ssim,
-                               float w_depth, float* ws, float* v_image, float* v_depth, void* stream) {
-    if (height <= kHalo || width <= kHalo) return TS_E_BADARG;
-    if (!image || !target || !ws || (depth_target && !depth) || (v_depth && (!depth || !v_image))) return TS_E_BADARG;
-    const dim3 grid((width + kTile - 1) / kTile, (height + kTile - 1) / kTile);
-    const size_t plane3 = (size_t)3 * (height - kHalo) * (width - kHalo) * 3;
-    hipStream_t s = (hipStream_t)stream;
-    launch_ssim_fwd(height, width, 3, image, depth, target, depth_target, ws, s);
-    if (v_image)
-        hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(kThreads), 0, s, height, width, 3, image, depth, target,
-                           depth_target, ws, w_l1, w_ssim, w_depth, v_image, v_depth);
-    return launch_status();
-}
-
 int ts_photometric_loss_reduce(int32_t height, int32_t width, float w_l1, float w_ssim, float w_depth,
                                const float* ws, float* out4, void* stream) {
     if (height <= kHalo || width <= kHalo || !ws || !out4) return TS_E_BADARG;
@@ -674,12 +617,6 @@ int ts_photometric_loss_reduce(int32_t height, int32_t width, float w_l1, float 
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, height, width, (int)triples,
                        w_l1, w_ssim, w_depth, ws + maps, out4);
     return launch_status();
-}
-
-int ts_photometric_loss(int32_t height, int32_t width, const float* image, const float* target,
-                        float w_l1, float w_ssim, float* ws, float* v_image, void* stream) {
-    return ts_photometric_loss_rgbd(height, width, 3, image, target, nullptr, w_l1, w_ssim, 0.0f, ws,
-                                    v_image, stream);
 }
 
 int ts_adam_step(int32_t num_tensors, float* const* params, const float* const* grads,

@@ -26,15 +26,6 @@ DEFAULT_LRS = {"means": 0.00016, "colors_dc": 0.0025, "colors_rest": 0.000125, "
 PARAM_ORDER = ("means", "colors_dc", "colors_rest", "scales", "quats", "opacities")
 
 
-def _loss_values(lib, h, w, w_l1, w_ssim, w_depth, ws, dev) -> Tensor:
-    """{loss, l1, ssim, depth l1} as ONE four-float device tensor from the partial sums in ``ws`` (ABI 8: one launch
-    instead of a dozen one-element tensor operations between the loss kernels and the frame's backward pass)."""
-    out = torch.empty((4,), dtype=torch.float32, device=dev)
-    _call("ts_photometric_loss_reduce", lib.ts_photometric_loss_reduce, h, w, w_l1, w_ssim, w_depth, _ptr(ws), _ptr(out),
-          _stream(dev))
-    return out
-
-
 def _mask_arg(mask, h: int, w: int, dev) -> Tensor:
     """A loss function's ``mask`` as the kernels read it: contiguous uint8 [H, W] on ``dev`` (masks.as_mask: bool -> 0 / 255)."""
     from .masks import as_mask
@@ -44,145 +35,87 @@ def _mask_arg(mask, h: int, w: int, dev) -> Tensor:
     return mask
 
 
-class _PhotometricLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, image, target, lambda_dssim, mask=None):
-        dev = _need_hip(image, target)
-        if image.dim() != 3 or image.shape[2] != 3 or image.shape != target.shape:
-            raise ValueError("image and target must both be [H, W, 3]")
-        h, w = image.shape[0], image.shape[1]
-        if h <= 10 or w <= 10:
-            raise ValueError("SSIM with an 11-tap window needs H, W > 10")
-        image, target = _f32c(image), _f32c(target)
-        lib = _lib.load()
-        ws = torch.empty((int(lib.ts_photometric_ws_floats(h, w)),), dtype=torch.float32, device=dev)
-        v_image = torch.empty_like(image) if ctx.needs_input_grad[0] else None
-        ho, wo = h - 10, w - 10
-        lam = float(lambda_dssim)
-        with torch.cuda.device(dev):
-            w_l1, w_ssim = (1.0 - lam) / (3.0 * h * w), -lam / (3.0 * ho * wo)
-            if mask is None:
-                _call("ts_photometric_loss", lib.ts_photometric_loss, h, w, _ptr(image), _ptr(target),
-                      w_l1, w_ssim, _ptr(ws), _ptr(v_image), _stream(dev))
-            else:
-                _call("ts_photometric_loss_masked", lib.ts_photometric_loss_masked, h, w, _ptr(image), _ptr(target),
-                      _ptr(_mask_arg(mask, h, w, dev)), w_l1, w_ssim, _ptr(ws), _ptr(v_image), _stream(dev))
-            loss, l1, ssim, _ = _loss_values(lib, h, w, w_l1, w_ssim, 0.0, ws, dev).unbind(0)
-        ctx.save_for_backward(v_image)
-        ctx.mark_non_differentiable(l1, ssim)
-        return loss, l1, ssim
-
-    @staticmethod
-    def backward(ctx, v_loss, _v_l1, _v_ssim):
-        (v_image,) = ctx.saved_tensors
-        return (None if v_image is None else v_image * v_loss), None, None, None
-
-
-class _FrameLoss(torch.autograd.Function):
-    """train.py:58-69 on the adapter's 4-channel output (RGB + depth) in one pair of launches."""
-
-    @staticmethod
-    def forward(ctx, frame, target, depth_target, lambda_dssim, lambda_depth, mask=None):
-        dev = _need_hip(frame, target)
-        if frame.dim() != 3 or frame.shape[2] != 4 or not frame.is_contiguous():
-            raise ValueError("frame must be a contiguous [H, W, 4] tensor (RGB + depth)")
-        h, w = frame.shape[0], frame.shape[1]
-        if target.shape != (h, w, 3) or (depth_target is not None and depth_target.shape != (h, w)):
-            raise ValueError("target must be [H, W, 3] and depth_target [H, W]")
-        if h <= 10 or w <= 10:
-            raise ValueError("SSIM with an 11-tap window needs H, W > 10")
-        frame, target = _f32c(frame), _f32c(target)
-        dt = None if depth_target is None else _f32c(depth_target)
-        lib = _lib.load()
-        ws = torch.empty((int(lib.ts_photometric_ws_floats(h, w)),), dtype=torch.float32, device=dev)
-        v_frame = torch.empty_like(frame) if ctx.needs_input_grad[0] else None
-        ho, wo = h - 10, w - 10
-        lam, lamd = float(lambda_dssim), float(lambda_depth) if dt is not None else 0.0
-        with torch.cuda.device(dev):
-            w_l1, w_ssim, w_depth = (1.0 - lam) / (3.0 * h * w), -lam / (3.0 * ho * wo), lamd / (h * w)
-            if mask is None:
-                _call("ts_photometric_loss_rgbd", lib.ts_photometric_loss_rgbd, h, w, 4, _ptr(frame),
-                      _ptr(target), _ptr(dt), w_l1, w_ssim, w_depth, _ptr(ws), _ptr(v_frame), _stream(dev))
-            else:
-                _call("ts_photometric_loss_rgbd_masked", lib.ts_photometric_loss_rgbd_masked, h, w, 4, _ptr(frame),
-                      _ptr(target), _ptr(dt), _ptr(_mask_arg(mask, h, w, dev)), w_l1, w_ssim, w_depth, _ptr(ws),
-                      _ptr(v_frame), _stream(dev))
-            loss, l1, ssim, ldepth = _loss_values(lib, h, w, w_l1, w_ssim, w_depth, ws, dev).unbind(0)
-        ctx.save_for_backward(v_frame)
-        ctx.mark_non_differentiable(l1, ssim, ldepth)
-        return loss, l1, ssim, ldepth
-
-    @staticmethod
-    def backward(ctx, v_loss, *_):
-        (v_frame,) = ctx.saved_tensors
-        return (None if v_frame is None else v_frame * v_loss), None, None, None, None, None   # out of place: retain_graph re-runs this (train.py:71)
-
-
-def planes_loss_and_gradient(rgb: Tensor, depth: Tensor, target: Tensor, depth_target: Optional[Tensor],
+def planes_loss_and_gradient(image: Tensor, depth: Optional[Tensor], target: Tensor, depth_target: Optional[Tensor],
                              lambda_dssim: float, lambda_depth: float, want_rgb: bool = True, want_depth: bool = True,
                              mask: Optional[Tensor] = None):
-    """train.py:58-69 on the adapter's two outputs as it hands them out (rgb[H,W,3] and depth[H,W], both contiguous:
-    frame.render_frame_planes) in one pair of launches, WITHOUT autograd: -> (values[4] = {loss, l1, ssim, depth l1},
-    dloss/drgb or None, dloss/ddepth or None).  ``TrainStep`` hands the two gradients straight to
-    ``torch.autograd.backward`` - no loss node, no ``grad * 1.0`` passes over 33 MB.
+    """train.py:58-69 in one pair of launches and the reduce, WITHOUT autograd, on any of the three layouts of a frame:
+    ``image`` [H,W,3] with ``depth`` None (no depth term), the adapter's two planes as it hands them out (image [H,W,3]
+    and depth [H,W], both contiguous: frame.render_frame_planes), or its contiguous [H,W,4] output whose channel 3 is the
+    depth (``depth`` None).  -> (values[4] = {loss, l1, ssim, depth l1}, dloss/dimage in the layout of ``image`` or None,
+    dloss/ddepth as a plane or None).  ``TrainStep`` hands the two gradients straight to ``torch.autograd.backward`` -
+    no loss node, no ``grad * 1.0`` passes over 33 MB.
     ``mask`` (uint8 or bool [H, W]): the masked pair of launches - the loss of the substituted
     image, gradients times the pixel's weight; None: the launches as they always were."""
-    dev = _need_hip(rgb, depth, target)
-    if rgb.dim() != 3 or rgb.shape[2] != 3 or not rgb.is_contiguous() or not depth.is_contiguous():
-        raise ValueError("rgb must be a contiguous [H, W, 3] tensor and depth a contiguous [H, W] one")
-    h, w = rgb.shape[0], rgb.shape[1]
-    if depth.shape != (h, w) or target.shape != (h, w, 3) or (depth_target is not None and depth_target.shape != (h, w)):
-        raise ValueError("depth must be [H, W], target [H, W, 3] and depth_target [H, W]")
+    dev = _need_hip(image, target) if depth is None else _need_hip(image, depth, target)
+    if image.dim() != 3 or image.shape[2] not in (3, 4) or (depth is not None and image.shape[2] != 3):
+        raise ValueError("image must be [H, W, 3], or [H, W, 4] (RGB + depth) without a separate depth plane")
+    h, w, floats = image.shape
+    if (floats == 4 or depth is not None) and not (image.is_contiguous() and (depth is None or depth.is_contiguous())):
+        raise ValueError("an [H, W, 4] frame, and an [H, W, 3] image with its [H, W] depth plane, must be contiguous")
+    if (target.shape != (h, w, 3) or (depth is not None and depth.shape != (h, w))
+            or (depth_target is not None and depth_target.shape != (h, w))):
+        raise ValueError("target must be [H, W, 3], depth and depth_target [H, W]")
     if h <= 10 or w <= 10:
         raise ValueError("SSIM with an 11-tap window needs H, W > 10")
-    rgb, depth, target = _f32c(rgb.detach()), _f32c(depth.detach()), _f32c(target)
+    image, target = _f32c(image.detach()), _f32c(target)
+    depth = None if depth is None else _f32c(depth.detach())
     dt = None if depth_target is None else _f32c(depth_target)
     lib = _lib.load()
     ws = torch.empty((int(lib.ts_photometric_ws_floats(h, w)),), dtype=torch.float32, device=dev)
-    v_rgb = torch.empty_like(rgb) if want_rgb else None
-    v_depth = torch.empty_like(depth) if (v_rgb is not None and want_depth and dt is not None) else None
+    v_image = torch.empty_like(image) if want_rgb else None
+    v_depth = torch.empty_like(depth) if (depth is not None and v_image is not None and want_depth and dt is not None) else None
     ho, wo = h - 10, w - 10
     lam, lamd = float(lambda_dssim), float(lambda_depth) if dt is not None else 0.0
     w_l1, w_ssim, w_depth = (1.0 - lam) / (3.0 * h * w), -lam / (3.0 * ho * wo), lamd / (h * w)
+    values = torch.empty((4,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        if mask is None:
-            _call("ts_photometric_loss_rgbd", lib.ts_photometric_loss_planes, h, w, _ptr(rgb), _ptr(depth),
-                  _ptr(target), _ptr(dt), w_l1, w_ssim, w_depth, _ptr(ws), _ptr(v_rgb), _ptr(v_depth), _stream(dev))
-        else:
-            _call("ts_photometric_loss_planes_masked", lib.ts_photometric_loss_planes_masked, h, w, _ptr(rgb), _ptr(depth),
-                  _ptr(target), _ptr(dt), _ptr(_mask_arg(mask, h, w, dev)), w_l1, w_ssim, w_depth, _ptr(ws), _ptr(v_rgb),
-                  _ptr(v_depth), _stream(dev))
-        values = _loss_values(lib, h, w, w_l1, w_ssim, w_depth, ws, dev)
-    return values, v_rgb, v_depth
+        m = None if mask is None else _mask_arg(mask, h, w, dev)
+        loss = _lib.TsLoss(height=h, width=w, pixel_floats=floats, flags=0 if m is None else _lib.LOSS_MASKED,
+                           image=_ptr(image), depth=_ptr(depth), target=_ptr(target), depth_target=_ptr(dt), mask=_ptr(m),
+                           w_l1=w_l1, w_ssim=w_ssim, w_depth=w_depth, ws=_ptr(ws), v_image=_ptr(v_image),
+                           v_depth=_ptr(v_depth))
+        _call("ts_photometric_loss_rgbd", lib.ts_photometric_loss_rgbd, ctypes.byref(loss), _stream(dev))
+        # {loss, l1, ssim, depth l1} as ONE four-float device tensor from the partial sums in ``ws`` (ABI 8: one launch
+        # instead of a dozen one-element tensor operations between the loss kernels and the frame's backward pass)
+        _call("ts_photometric_loss_reduce", lib.ts_photometric_loss_reduce, h, w, w_l1, w_ssim, w_depth, _ptr(ws),
+              _ptr(values), _stream(dev))
+    return values, v_image, v_depth
 
 
-class _PlanesLoss(torch.autograd.Function):
-    """``planes_loss_and_gradient`` as a differentiable function of rgb and depth."""
+class _Loss(torch.autograd.Function):
+    """``planes_loss_and_gradient`` as a differentiable function of the image and, where there is one, the depth plane."""
 
     @staticmethod
-    def forward(ctx, rgb, depth, target, depth_target, lambda_dssim, lambda_depth, mask=None):
-        values, v_rgb, v_depth = planes_loss_and_gradient(rgb, depth, target, depth_target, lambda_dssim, lambda_depth,
-                                                          ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                                          **({} if mask is None else {"mask": mask}))
+    def forward(ctx, image, depth, target, depth_target, lambda_dssim, lambda_depth, mask):
+        values, v_image, v_depth = planes_loss_and_gradient(image, depth, target, depth_target, lambda_dssim, lambda_depth,
+                                                            ctx.needs_input_grad[0], ctx.needs_input_grad[1], mask)
         loss, l1, ssim, ldepth = values.unbind(0)
         ctx.has_depth = v_depth is not None
-        ctx.save_for_backward(*(t for t in (v_rgb, v_depth) if t is not None))
+        ctx.save_for_backward(*(t for t in (v_image, v_depth) if t is not None))
         ctx.mark_non_differentiable(l1, ssim, ldepth)
         return loss, l1, ssim, ldepth
 
     @staticmethod
     def backward(ctx, v_loss, *_):
         saved = ctx.saved_tensors
-        v_rgb = saved[0] * v_loss if saved else None             # out of place: retain_graph re-runs this (train.py:71)
+        v_image = saved[0] * v_loss if saved else None           # out of place: retain_graph re-runs this (train.py:71)
         v_depth = saved[1] * v_loss if ctx.has_depth else None   # None: no depth target, the kernels take "no gradient"
-        return v_rgb, v_depth, None, None, None, None, None
+        return v_image, v_depth, None, None, None, None, None
+
+
+def _need_floats(image: Tensor, floats: int, what: str) -> None:
+    if image.dim() != 3 or image.shape[2] != floats:
+        raise ValueError(f"{what} must be a [H, W, {floats}] tensor")
 
 
 def planes_loss(rgb: Tensor, depth: Tensor, target: Tensor, depth_target: Optional[Tensor] = None,
                 lambda_dssim: float = 0.2, lambda_depth: float = 0.2, mask: Optional[Tensor] = None):
     """``frame_loss`` on the frame as two planes: ``(loss, l1, ssim, depth_l1)``, differentiable w.r.t. ``rgb`` and
     ``depth``.  ``mask``: as ``photometric_loss``'s."""
-    return _PlanesLoss.apply(rgb, depth, target, depth_target, lambda_dssim, lambda_depth, mask)
+    _need_floats(rgb, 3, "rgb")
+    if depth is None:
+        raise ValueError("planes_loss needs the depth plane; photometric_loss is the loss without one")
+    return _Loss.apply(rgb, depth, target, depth_target, lambda_dssim, lambda_depth, mask)
 
 
 def frame_loss(frame: Tensor, target: Tensor, depth_target: Optional[Tensor] = None,
@@ -191,7 +124,8 @@ def frame_loss(frame: Tensor, target: Tensor, depth_target: Optional[Tensor] = N
     channel 3 = depth): ``(1-l) L1 + l (1 - SSIM) [+ l_depth * mean|depth - depth_target|]``.
     Returns ``(loss, l1, ssim, depth_l1)``; differentiable w.r.t. ``frame``.  ``mask``: as ``photometric_loss``'s; the
     depth term becomes ``mean(m |depth - depth_target|)``."""
-    return _FrameLoss.apply(frame, target, depth_target, lambda_dssim, lambda_depth, mask)
+    _need_floats(frame, 4, "frame")
+    return _Loss.apply(frame, None, target, depth_target, lambda_dssim, lambda_depth, mask)
 
 
 def photometric_loss(image: Tensor, target: Tensor, lambda_dssim: float = 0.2, mask: Optional[Tensor] = None):
@@ -201,7 +135,8 @@ def photometric_loss(image: Tensor, target: Tensor, lambda_dssim: float = 0.2, m
     The loss is then the same loss, with the same weights (not renormalised by the mask's area), of the substituted image
     ``m image + (1 - m) target``, and the gradient is m times that loss's: an ignored pixel (0) gets exactly zero, an
     all-255 mask gives the unmasked bits.  None, the default: the launches as they always were."""
-    return _PhotometricLoss.apply(image, target, lambda_dssim, mask)
+    _need_floats(image, 3, "image")
+    return _Loss.apply(image, None, target, None, lambda_dssim, 0.0, mask)[:3]
 
 
 class Adam:

@@ -6,8 +6,8 @@ Everything runs at BASELINE config 3's size, 1920 x 1080, on the frame as two pl
 mask of about 30 % ignored pixels in blobs.  The variants are timed ALTERNATING inside one process, ``--iters`` calls
 each, and the whole set is repeated ``--rounds`` times so that the spread of each call is visible beside its median:
 
-  * the unmasked loss pair (``ts_photometric_loss_planes``), on this build;
-  * the masked loss pair (``ts_photometric_loss_planes_masked``);
+  * the unmasked loss pair (``ts_photometric_loss_rgbd`` on a ``ts_loss`` with a depth plane), on this build;
+  * the masked loss pair (the same descriptor with ``TS_LOSS_MASKED``);
   * the route a user would otherwise take: the blend as tensor expressions, the unmasked pair, both gradients times m;
   * a streaming read of as many bytes as the masked pair moves (``ts_bench_stream_read``), as the floor;
   * ``image_metrics`` with and without a mask (uint8 target).
@@ -18,6 +18,7 @@ each, and the whole set is repeated ``--rounds`` times so that the spread of eac
 ``--note`` adds a string to the file (the unmasked-path comparison against the parent commit, kernel statistics).
 """
 import argparse
+import ctypes
 import json
 import statistics
 import sys
@@ -82,14 +83,18 @@ def main():
     stream = _stream(dev)
     w_l1, w_ssim, w_depth = 0.8 / (3.0 * h * w), -0.2 / (3.0 * (h - 10) * (w - 10)), 0.2 / (h * w)
 
+    def descriptor(**more):
+        return _lib.TsLoss(height=h, width=w, pixel_floats=3, image=_ptr(rgb), depth=_ptr(depth), target=_ptr(tgt),
+                           depth_target=_ptr(dtgt), w_l1=w_l1, w_ssim=w_ssim, w_depth=w_depth, ws=_ptr(ws),
+                           v_image=_ptr(v_rgb), v_depth=_ptr(v_depth), **more)
+    plain, masked = descriptor(), descriptor(flags=_lib.LOSS_MASKED, mask=_ptr(mask))
+
     def pair(image):
-        _lib.check(lib.ts_photometric_loss_planes(h, w, _ptr(image), _ptr(depth), _ptr(tgt), _ptr(dtgt), w_l1, w_ssim, w_depth,
-                                                  _ptr(ws), _ptr(v_rgb), _ptr(v_depth), stream), "ts_photometric_loss_planes")
+        plain.image = _ptr(image)
+        _lib.check(lib.ts_photometric_loss_rgbd(ctypes.byref(plain), stream), "ts_photometric_loss_rgbd")
 
     def masked_pair():
-        _lib.check(lib.ts_photometric_loss_planes_masked(h, w, _ptr(rgb), _ptr(depth), _ptr(tgt), _ptr(dtgt), _ptr(mask), w_l1,
-                                                         w_ssim, w_depth, _ptr(ws), _ptr(v_rgb), _ptr(v_depth), stream),
-                   "ts_photometric_loss_planes_masked")
+        _lib.check(lib.ts_photometric_loss_rgbd(ctypes.byref(masked), stream), "ts_photometric_loss_rgbd, masked")
 
     def torch_route():
         blended = torch.where(keep, rgb, torch.addcmul(tgt, m3, rgb - tgt))
@@ -108,8 +113,8 @@ def main():
         _lib.check(lib.ts_bench_stream_read(floor.data_ptr(), floor.numel(), sink.data_ptr(), stream), "ts_bench_stream_read")
 
     out_m = torch.empty((4,), dtype=torch.float64, device=dev)
-    variants = {"loss pair, unmasked (ts_photometric_loss_planes)": lambda: pair(rgb),
-                "loss pair, masked (ts_photometric_loss_planes_masked)": masked_pair,
+    variants = {"loss pair, unmasked (ts_photometric_loss_rgbd, two planes)": lambda: pair(rgb),
+                "loss pair, masked (ts_photometric_loss_rgbd, two planes, TS_LOSS_MASKED)": masked_pair,
                 "torch route: blend, unmasked pair, gradients times m": torch_route,
                 f"streaming read of the masked pair's {moved} bytes": stream_read,
                 "image_metrics, uint8 target": lambda: image_metrics(rgb, u8, out=out_m),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Times the evaluation metrics with device events after a warm-up; one JSON line per row.
 
-  * the entry: ``ts_image_metrics`` with a uint8 target against the training loss's forward (``ts_photometric_loss``
+  * the entry: ``ts_image_metrics`` with a uint8 target against the training loss's forward (``ts_photometric_loss_rgbd``
     without a gradient image + ``ts_photometric_loss_reduce``) on the float target, both on preallocated workspaces,
     timed ALTERNATING in ``--rounds`` rounds of ``--iters`` calls each; per side the median and the smallest and largest
     round (the run-to-run spread of this very call), the bytes the algorithm moves computed from the shapes, and their
@@ -12,6 +12,7 @@
     python tools/time_metrics.py [--width 1920 --height 1080] [--iters 2000] [--rounds 7] [--n 1000000] [--out FILE]
 """
 import argparse
+import ctypes
 import json
 import statistics
 import sys
@@ -58,14 +59,16 @@ def entry_rows(h, w, iters, rounds, dev):
     def metrics():
         _lib.check(lib.ts_image_metrics(h, w, 3, _ptr(img), _ptr(u8), 1, _ptr(ws_m), _ptr(out_m), stream), "ts_image_metrics")
 
+    loss = _lib.TsLoss(height=h, width=w, pixel_floats=3, image=_ptr(img), target=_ptr(tgt), w_l1=w_l1, w_ssim=w_ssim,
+                       ws=_ptr(ws_l))
+
     def loss_forward():
-        _lib.check(lib.ts_photometric_loss(h, w, _ptr(img), _ptr(tgt), w_l1, w_ssim, _ptr(ws_l), None, stream),
-                   "ts_photometric_loss")
+        _lib.check(lib.ts_photometric_loss_rgbd(ctypes.byref(loss), stream), "ts_photometric_loss_rgbd")
         _lib.check(lib.ts_photometric_loss_reduce(h, w, w_l1, w_ssim, 0.0, _ptr(ws_l), _ptr(out_l), stream),
                    "ts_photometric_loss_reduce")
 
     sides = {"ts_image_metrics, uint8 target": metrics,
-             "ts_photometric_loss forward + reduce, float target, no gradient": loss_forward}
+             "ts_photometric_loss_rgbd forward + reduce, float target, no gradient": loss_forward}
     for fn in sides.values():
         timed(fn, max(50, iters // 10))
     ms = {k: [] for k in sides}
@@ -74,7 +77,7 @@ def entry_rows(h, w, iters, rounds, dev):
             ms[k].append(timed(fn, iters))
     px, mp = h * w, (h - 10) * (w - 10)
     moved = {"ts_image_metrics, uint8 target": 12 * px + 3 * px,                       # image + bytes, read once
-             "ts_photometric_loss forward + reduce, float target, no gradient": 12 * px + 12 * px + 36 * mp}   # + 9 maps written
+             "ts_photometric_loss_rgbd forward + reduce, float target, no gradient": 12 * px + 12 * px + 36 * mp}   # + 9 maps written
     rows = []
     for k, v in ms.items():
         med = statistics.median(v)
