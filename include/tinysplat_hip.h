@@ -449,6 +449,11 @@ int ts_reduce_partials(int32_t n, int32_t channels, int32_t flags, const int32_t
                                           lists (same rows, same gradients).  Only with the in-kernel sort on 16x16 lists
                                           without TS_FRAME_SPLIT / NARROW_WAVES / SEPARATE_SORT (ignored otherwise), and
                                           `survivors` set; bucket_ids then holds the survivors' ids after the forward pass */
+#define TS_FRAME_LINEAR_OPACITY (8192)   /* `opacities` holds opacities, not logits: the executor drops TS_RASTER_LOGIT_OPACITY
+                                          from the flag words of the colour / pack stage, of ts_reduce_partials (v_opacity
+                                          is then the gradient of the opacity itself) and of the sharded owner stage.  The
+                                          antialiased mode renders with the compensated opacities of ts_antialias_fwd this
+                                          way; the kernels test the bit at run time */
 typedef struct ts_frame {
     int32_t n, num_bases, sh_degree, channels, flags;
     int32_t flag_gen;                         /* row-flag generation of the backward pass (0: zero row_flags) */
@@ -1346,6 +1351,32 @@ int ts_box_mask(int32_t n, const float* box_host, const float* means, uint8_t* i
 int64_t ts_pose_ws_bytes(int32_t n);
 int ts_pose_grad(int32_t n, const float* view34_host, const float* means, const float* quats, const float* v_means,
                  const float* v_quats, void* ws, double* out6, void* stream);
+
+/* ============================ antialiased rendering: opacity compensation ===================== */
+/* DESIGN.md section 6w; the arithmetic is csrc/antialias_math.h's, and every result is the bits of that header's host
+ * build.  With (a_o, b, c_o) a Gaussian's projected covariance before the 0.3 blur of the projection and det_o, det_b
+ * the determinants before and after it, comp = sqrt(max(0, det_o / det_b)); behind the clip plane and where the max
+ * clamps comp = 0 and so is every derivative.  One lane per Gaussian, no atomics, no workspace.
+ * ts_antialias_fwd: from means3d [n, 3], scales [n, 3] and quats [n, 4] under project_flags (TS_PROJECT_*), viewmat (12
+ * floats, device) and the camera -> comp [n], o_eff [n] = opacity * comp with `opacity` [n] a logit (raster_flags =
+ * TS_RASTER_LOGIT_OPACITY) or an opacity (0), and rows [n, 4] = (a_o, b, c_o, comp), 16-byte aligned, for ts_antialias_bwd.
+ * Any of the three outputs may be NULL, not all; opacity may be NULL without o_eff.
+ * ts_antialias_bwd: between ts_frame_bwd_composite and ts_frame_bwd_params[_adam] of a frame rendered with o_eff
+ * (TS_FRAME_LINEAR_OPACITY).  For every Gaussian with radii > 0, in place: v_conic [n, 3] += the compensation's gradient
+ * in v_conic's convention (true partials of the stored entries) for v_comp = v_opacity * opacity, and v_opacity [n] (on
+ * entry dL/do_eff) <- dL/d(opacity argument): times comp, and through the sigmoid for a logit.  Other rows are not touched.
+ * ts_compensation_bwd: v_comp [n] -> v_means3d [n, 3], v_scales [n, 3], v_quats [n, 4] (gradients of the stored tensors
+ * under project_flags) through the projection's own VJP; every row is written.
+ * n == 0: returns 0.  TS_E_BADARG before any launch: n < 0, a NULL camera, unknown flag bits, with n > 0 a NULL or
+ * misaligned pointer. */
+int ts_antialias_fwd(int32_t n, const float* means3d, const float* scales, const float* quats, const float* viewmat,
+                     const ts_camera* cam_host, int32_t project_flags, const float* opacity, int32_t raster_flags,
+                     float* comp, float* o_eff, float* rows, void* stream);
+int ts_antialias_bwd(int32_t n, const int32_t* radii, const float* rows, const float* opacity, int32_t raster_flags,
+                     float* v_opacity, float* v_conic, void* stream);
+int ts_compensation_bwd(int32_t n, const float* means3d, const float* scales, const float* quats, const float* viewmat,
+                        const ts_camera* cam_host, int32_t project_flags, const float* v_comp, float* v_means3d,
+                        float* v_scales, float* v_quats, void* stream);
 
 /* ======================================= measurement utility ================================== */
 /* Streaming read of n_floats float32 (16-byte loads, grid-stride): the read-bandwidth microbenchmark

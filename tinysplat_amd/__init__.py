@@ -3,7 +3,7 @@
 Exports the names tinysplat imports from gsplat (tinysplat/splatting/rasterize.py:3-4,
 model_gaussian.py:14) plus the render adapter.  ``tinysplat_amd.sh`` mirrors ``gsplat.sh``.
 """
-from .ops import (deg_from_sh, num_sh_bases, project_gaussians, rasterize_gaussians,
+from .ops import (deg_from_sh, num_sh_bases, opacity_compensation, project_gaussians, rasterize_gaussians,
                   spherical_harmonics)
 from .extract import ExtractConfig, SurfacePoints, extract_surface_points, level_set_points
 from .mesh import MeshConfig, TriangleMesh, extract_mesh, vertex_colors
@@ -45,4 +45,4 @@ __all__ = ["project_gaussians", "rasterize_gaussians", "spherical_harmonics", "n
            "sh_rotation_matrices", "transform_gaussians", "transform_camera", "transform_cameras", "transform_points",
            "orient_from_cameras", "box_mask", "crop_gaussians", "merge_models", "PoseConfig", "PoseModel", "pose_gradient",
            "refine_pose", "se3_exp", "se3_log", "TrainingMasks", "masks_from_labels", "dilate_ignored", "combine_masks",
-           "mask_coverage"]
+           "mask_coverage", "opacity_compensation"]

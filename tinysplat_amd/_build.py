@@ -83,6 +83,9 @@ SOURCES = [
     # pose.hip: a row's six terms and the sums over the rows are defined as the bits of the host build of pose_math.h,
     # double products and sums each rounded on its own in a fixed order; an fma would make the two builds two functions
     ("pose.hip", ["-ffp-contract=off"]),
+    # antialias.hip: comp, the compensated opacity and the gradient rows are defined as the bits of the host build of
+    # antialias_math.h, float32 products and sums each rounded on its own; its exponential is written out in that header
+    ("antialias.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -34,6 +34,7 @@ FRAME_SURVIVORS = 512
 FRAME_GROUP_COUNTS = 1024
 FRAME_ONE_WALK = 2048
 FRAME_ROW_SPANS = 4096
+FRAME_LINEAR_OPACITY = 8192
 PARTIAL_ROW_FLOATS = 12          # TS_PARTIAL_ROW_FLOATS: floats per (tile, Gaussian) gradient row slot
 
 
@@ -317,6 +318,9 @@ SIGNATURES = {
     "ts_box_mask": (c_int32, [c_int32, POINTER(c_float), _P, _P, _P]),
     "ts_pose_ws_bytes": (c_int64, [c_int32]),
     "ts_pose_grad": (c_int32, [c_int32, POINTER(c_float), _P, _P, _P, _P, _P, _P, _P]),
+    "ts_antialias_fwd": (c_int32, [c_int32, _P, _P, _P, _P, _CAM, c_int32, _P, c_int32, _P, _P, _P, _P]),
+    "ts_antialias_bwd": (c_int32, [c_int32, _P, _P, _P, c_int32, _P, _P, _P]),
+    "ts_compensation_bwd": (c_int32, [c_int32, _P, _P, _P, _P, _CAM, c_int32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

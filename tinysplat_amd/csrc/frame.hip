@@ -148,6 +148,10 @@ inline int32_t* longest_word(const ts_frame* f) {
     }
     return nullptr;
 }
+// the opacity argument's flag word: logits, or (TS_FRAME_LINEAR_OPACITY) opacities as they are
+inline int opacity_flags(const ts_frame* f) {
+    return (f->flags & TS_FRAME_LINEAR_OPACITY) ? 0 : TS_RASTER_LOGIT_OPACITY;
+}
 inline int raster_flags(const ts_frame* f) {
     return TS_RASTER_CLAMP_RGB | ((f->flags & TS_FRAME_SPLIT) ? TS_RASTER_SPLIT_BLOCKS : 0) |
            ((f->flags & TS_FRAME_NARROW_WAVES) ? TS_RASTER_NARROW_WAVES : 0);
@@ -196,7 +200,7 @@ int ts_frame_fwd_prepare(const ts_frame* f, void* stream) {
                     ts_colors_pack_spans_fwd(f->n, f->sh_degree, f->num_bases, f->means, f->origin, f->colors_dc,
                                              f->num_bases > 1 ? f->colors_rest : nullptr, f->sh_mask,
                                              (f->flags & TS_FRAME_STRIPE) ? f->num_tiles_hit : nullptr, f->channels,
-                                             TS_RASTER_LOGIT_OPACITY, f->xys, f->radii, f->conics, f->opacities,
+                                             opacity_flags(f), f->xys, f->radii, f->conics, f->opacities,
                                              f->cum_tiles_hit, &f->cam, f->channels == 4 ? f->depths : nullptr,
                                              f->splats, tight ? 1 : 0, row_spans(f), stream)));
     // (TS_FRAME_LIST_STATS: the longest list goes to the word behind the count word - read a frame later by the caller's
@@ -309,7 +313,7 @@ int ts_frame_bwd_composite(const ts_frame* f, void* stream) {
     const bool stripe = (f->flags & TS_FRAME_STRIPE) != 0;
     return TS_ENTRY("ts_reduce_partials",
                     ts_reduce_partials(f->n, f->channels,
-                                       TS_RASTER_LOGIT_OPACITY | bwd_split(f) | TS_RASTER_FLAG_GEN(f->flag_gen),
+                                       opacity_flags(f) | bwd_split(f) | TS_RASTER_FLAG_GEN(f->flag_gen),
                                        f->num_tiles_hit, f->cum_tiles_hit, f->partials, f->row_flags, f->splats,
                                        f->v_xy, f->v_conic, f->v_colors, f->v_opacity,
                                        f->channels == 4 ? f->v_depth : nullptr, stripe ? f->sh_mask : nullptr, stream));
@@ -364,7 +368,7 @@ int ts_shard_owner_fwd_padded(const ts_frame* fo, const ts_stripes* stripes, con
                         ts_shard_owner_fwd_fused(fo->n, fo->sh_degree, fo->num_bases, fo->means, fo->scales, fo->quats,
                                                  fo->view34, fo->projview, &fo->cam, 3, fo->origin, fo->colors_dc,
                                                  fo->num_bases > 1 ? fo->colors_rest : nullptr, fo->opacities,
-                                                 fo->channels, TS_RASTER_LOGIT_OPACITY, fo->xys, fo->depths, fo->radii,
+                                                 fo->channels, opacity_flags(fo), fo->xys, fo->depths, fo->radii,
                                                  fo->conics, fo->num_tiles_hit, fo->sh_mask, fo->splats, stripes,
                                                  group_base, route_ws, counts, stream));
     TS_TRY(TS_ENTRY("ts_project_fwd",
@@ -375,7 +379,7 @@ int ts_shard_owner_fwd_padded(const ts_frame* fo, const ts_stripes* stripes, con
     TS_TRY(TS_ENTRY("ts_colors_pack_fwd",
                     ts_colors_pack_fwd(fo->n, fo->sh_degree, fo->num_bases, fo->means, fo->origin, fo->colors_dc,
                                        fo->num_bases > 1 ? fo->colors_rest : nullptr, fo->sh_mask, nullptr,
-                                       fo->channels, TS_RASTER_LOGIT_OPACITY, fo->xys, fo->radii, fo->conics,
+                                       fo->channels, opacity_flags(fo), fo->xys, fo->radii, fo->conics,
                                        fo->opacities, fo->num_tiles_hit, &fo->cam,
                                        fo->channels == 4 ? fo->depths : nullptr, fo->splats, stream)));
     return TS_ENTRY("ts_route_count",

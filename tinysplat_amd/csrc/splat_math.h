@@ -113,6 +113,7 @@ struct ProjMid {
     float t00, t01, t02, t10, t11, t12;   // T = J W
     float c00, c01, c02, c11, c12, c22;   // cov3d
     float a, b, c, det;                   // cov2d (+blur), determinant
+    float ao, co;                         // the diagonal of cov2d before the blur (antialias_math.h)
     float m00, m01, m02, m10, m11, m12, m20, m21, m22;  // M = R S
     Rot R;
     float s0, s1, s2;              // glob_scale * scale
@@ -165,9 +166,11 @@ TS_HD bool project_mid(const Cam& C, const float m[3], const float sc[3], const 
     const float w0 = (o.t10 * o.c00 + o.t11 * o.c01) + o.t12 * o.c02;
     const float w1 = (o.t10 * o.c01 + o.t11 * o.c11) + o.t12 * o.c12;
     const float w2 = (o.t10 * o.c02 + o.t11 * o.c12) + o.t12 * o.c22;
-    o.a = ((u0 * o.t00 + u1 * o.t01) + u2 * o.t02) + kBlur;
+    o.ao = (u0 * o.t00 + u1 * o.t01) + u2 * o.t02;
+    o.a = o.ao + kBlur;
     o.b = (u0 * o.t10 + u1 * o.t11) + u2 * o.t12;
-    o.c = ((w0 * o.t10 + w1 * o.t11) + w2 * o.t12) + kBlur;
+    o.co = (w0 * o.t10 + w1 * o.t11) + w2 * o.t12;
+    o.c = o.co + kBlur;
     o.det = o.a * o.c - o.b * o.b;
     return true;
 }

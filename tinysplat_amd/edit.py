@@ -277,7 +277,8 @@ def transform_gaussians(model, sim3: Sim3, mask: Optional[Tensor] = None) -> Spl
               *[_ptr(t) if t.numel() else None for t in (means, scales, quats, rest)],
               *[_ptr(t) if t.numel() else None for t in out], _stream(dev))
     return SplatModel(out[0], model.colors_dc, out[3], out[1], out[2], model.opacities,
-                      active_sh_degree=model.active_sh_degree, background=model.background)
+                      active_sh_degree=model.active_sh_degree, background=model.background,
+                      rasterize_mode=getattr(model, "rasterize_mode", "classic"))
 
 
 def transform_points(points: Tensor, sim3: Sim3) -> Tensor:
@@ -383,10 +384,13 @@ def crop_gaussians(model, center, half_extent, rotation=None) -> SplatModel:
 def merge_models(models: Sequence) -> SplatModel:
     """The models' rows concatenated in order.  ``colors_rest`` is zero-padded to the largest stored degree,
     ``active_sh_degree`` is the maximum, ``background`` the first model's.  Plain torch; raises on an empty list or
-    models on different devices."""
+    models on different devices, or of different rasterize modes (an opacity means something else in each)."""
     models = list(models)
     if not models:
         raise ValueError("merge_models needs at least one model")
+    modes = {getattr(m, "rasterize_mode", "classic") for m in models}
+    if len(modes) > 1:
+        raise ValueError(f"merge_models: the models have different rasterize modes {sorted(modes)}")
     dev = models[0].means.device
     if any(p.device != dev for m in models for p in m.parameters()):
         raise ValueError("merge_models: the models live on different devices")
@@ -401,4 +405,4 @@ def merge_models(models: Sequence) -> SplatModel:
            for f in ("means", "colors_dc", "scales", "quats", "opacities")}
     return SplatModel(cat["means"], cat["colors_dc"], torch.cat(rests, dim=0), cat["scales"], cat["quats"],
                       cat["opacities"], active_sh_degree=max(int(m.active_sh_degree) for m in models),
-                      background=models[0].background)
+                      background=models[0].background, rasterize_mode=modes.pop())

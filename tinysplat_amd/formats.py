@@ -19,7 +19,7 @@ contiguous buffer and writes / parses the header.  No CPU fallback: tensors must
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -41,8 +41,9 @@ def save_checkpoint(model, path) -> None:
     torch.save(state_dict(model), path)
 
 
-def load_checkpoint(path, device) -> SplatModel:
-    """train.py:267-270 + model_gaussian.py:92-110."""
+def load_checkpoint(path, device, rasterize_mode: str = "classic") -> SplatModel:
+    """train.py:267-270 + model_gaussian.py:92-110.  The file holds the six tensors and nothing else (the reference loads
+    it): the rasterize mode of the model is the caller's to give."""
     sd = torch.load(path, map_location="cpu")
     missing = [f for f in FIELDS if f not in sd]
     if missing:
@@ -59,7 +60,7 @@ def load_checkpoint(path, device) -> SplatModel:
     dev = torch.device(device)
     ps = [sd[f].to(device=dev, dtype=torch.float32).contiguous() for f in
           ("means", "colors_dc", "colors_rest", "scales", "quats", "opacities")]
-    return SplatModel(*ps, active_sh_degree=degree, background=torch.zeros(3, device=dev))
+    return SplatModel(*ps, active_sh_degree=degree, background=torch.zeros(3, device=dev), rasterize_mode=rasterize_mode)
 
 
 def ply_attribute_names(k_rest: int) -> List[str]:
@@ -84,19 +85,26 @@ def ply_records(model) -> Tensor:
     return rows
 
 
+PLY_MODE_COMMENT = "comment rasterize_mode "      # header line of an antialiased model's file; load_ply honours it
+
+
 def export_ply(model, path) -> None:
     rows = ply_records(model).cpu().numpy()
     k_rest = getattr(model, "colors_rest").shape[1]
-    head = ["ply", "format binary_little_endian 1.0", f"element vertex {rows.shape[0]}"]
+    head = ["ply", "format binary_little_endian 1.0"]
+    if getattr(model, "rasterize_mode", "classic") == "antialiased":     # (a classic model's file is what it always was)
+        head += [PLY_MODE_COMMENT + "antialiased"]
+    head += [f"element vertex {rows.shape[0]}"]
     head += [f"property float {a}" for a in ply_attribute_names(k_rest)] + ["end_header"]
     with open(path, "wb") as f:
         f.write(("\n".join(head) + "\n").encode("ascii"))
         f.write(rows.astype("<f4", copy=False).tobytes())
 
 
-def load_ply(path, device) -> SplatModel:
+def load_ply(path, device, rasterize_mode: Optional[str] = None) -> SplatModel:
     """Reads a binary little-endian 3DGS PLY whose vertex element holds only float32 properties
-    (what export_ply and the INRIA tool-chain write)."""
+    (what export_ply and the INRIA tool-chain write).  The model's rasterize mode is ``rasterize_mode`` if given, else
+    the one a ``comment rasterize_mode ...`` header line names, else "classic"."""
     with open(path, "rb") as f:
         blob = f.read()
     marker = b"end_header\n"
@@ -106,10 +114,12 @@ def load_ply(path, device) -> SplatModel:
     lines = blob[:at].decode("ascii").split("\n")
     if "format binary_little_endian 1.0" not in lines:
         raise ValueError("only binary_little_endian PLY is supported")
-    n, names = None, []
+    n, names, mode = None, [], "classic"
     for ln in lines:
         tok = ln.split()
-        if tok[:2] == ["element", "vertex"]:
+        if ln.startswith(PLY_MODE_COMMENT):
+            mode = ln[len(PLY_MODE_COMMENT):].strip()
+        elif tok[:2] == ["element", "vertex"]:
             n = int(tok[2])
         elif tok[:1] == ["element"]:
             raise ValueError("unexpected extra PLY element")
@@ -141,7 +151,8 @@ def load_ply(path, device) -> SplatModel:
                 ("means", "colors_dc", "colors_rest", "opacities", "scales", "quats")], _stream(dev))
     return SplatModel(out["means"], out["colors_dc"], out["colors_rest"], out["scales"], out["quats"],
                       out["opacities"], active_sh_degree=deg_from_sh(k_rest + 1),
-                      background=torch.zeros(3, device=dev))
+                      background=torch.zeros(3, device=dev),
+                      rasterize_mode=mode if rasterize_mode is None else rasterize_mode)
 
 
 _POINT_FIELDS = ("x", "y", "z", "nx", "ny", "nz")
@@ -332,9 +343,10 @@ def export_splat(model, path, order="importance", limit=None) -> None:
         f.write(blob)
 
 
-def load_splat(path, device) -> SplatModel:
+def load_splat(path, device, rasterize_mode: str = "classic") -> SplatModel:
     """Reads a .splat file as a degree-0 model: colors_rest is [n, 0, 3], quats are not renormalised (projection does),
-    opacities are finite (the alpha byte is clamped to 1..254 before the logit)."""
+    opacities are finite (the alpha byte is clamped to 1..254 before the logit).  The format has no place for the
+    rasterize mode: it is the caller's to give."""
     with open(path, "rb") as f:
         blob = f.read()
     if len(blob) % SPLAT_RECORD_BYTES:
@@ -352,4 +364,5 @@ def load_splat(path, device) -> SplatModel:
         _call("ts_splat_unpack", lib.ts_splat_unpack, n, _ptr(records) if n else None,
               *[_ptr(t) if n else None for t in out.values()], _stream(dev))
     return SplatModel(out["means"], out["colors_dc"], torch.empty((n, 0, 3), **f32), out["scales"], out["quats"],
-                      out["opacities"], active_sh_degree=0, background=torch.zeros(3, device=dev))
+                      out["opacities"], active_sh_degree=0, background=torch.zeros(3, device=dev),
+                      rasterize_mode=rasterize_mode)

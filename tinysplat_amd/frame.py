@@ -31,7 +31,8 @@ from torch import Tensor
 from ._comm import collective_timer
 from . import _lib
 from ._lib import TsFrame
-from .ops import TileBinning, _camera, _f32c, _need_hip, _stream, _stripe_rows, _tile_bounds, deg_from_sh
+from .ops import (TileBinning, _call, _camera, _f32c, _need_hip, _stream, _stripe_rows, _tile_bounds, deg_from_sh,
+                  rasterize_mode)
 
 # Tight tile lists (see ts_bin_count): (Gaussian, tile) pairs that provably cannot reach alpha >= 1/255
 # anywhere in the tile are dropped at binning time.  Results are bit-identical either way
@@ -362,13 +363,15 @@ class _Frame:
     """Buffers of one frame plus the ``ts_frame`` struct that points at them."""
     __slots__ = ("fr", "cam", "n", "nb", "ch", "w", "h", "num_tiles", "total", "split", "segs", "keep",
                  "wf", "tile_bins", "ids", "bucket_ids", "out_img", "out_depth", "planes", "xys", "radii", "nth", "cum",
-                 "inputs", "bg")
+                 "inputs", "bg", "aa")
 
 
 def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, projview, origin, background,
-             fx, fy, width, height, sh_degree, with_depth, tile_rows, keep: bool, planes: bool = False) -> _Frame:
+             fx, fy, width, height, sh_degree, with_depth, tile_rows, keep: bool, planes: bool = False,
+             antialiased: bool = False) -> _Frame:
     """Enqueues the forward frame; ``keep`` = also produce what the backward pass needs; ``planes`` (with
-    ``with_depth``) = RGB and depth as two contiguous images instead of one 4-channel image."""
+    ``with_depth``) = RGB and depth as two contiguous images instead of one 4-channel image; ``antialiased``: the frame
+    is rendered with the compensated opacities of ts_antialias_fwd in place of the logits."""
     _mark("fwd:enter")
     dev = _need_hip(means, scales, quats, opacities, colors_dc, colors_rest, view34, projview, origin, background)
     n = means.shape[0]
@@ -409,6 +412,7 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
     F.cam, F.n, F.nb, F.ch, F.w, F.h, F.keep = cam, n, nb, ch, w, h, keep
     F.inputs = (means, scales, quats, opacities, colors_dc, colors_rest, view34, projview, origin)
     F.bg = bg
+    F.aa = None
     num_tiles = int(lib.ts_num_tiles(ctypes.byref(cam)))            # lists of this launch (wide or 16x16 tiles)
     F.num_tiles = num_tiles
     F.split = 0 < cam.tile_rows * cam.tile_bounds_x <= SPLIT_BLOCKS_BELOW
@@ -502,6 +506,18 @@ def _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, pr
         if keep:
             fr.sh_mask, fr.final_Ts, fr.final_index, fr.clamp_mask = ptr[11], ptr[12], ptr[13], ptr[14]
         F.fr = fr
+        if antialiased:
+            # ANTIALIASED MODE: one streaming launch in front of the frame leaves o_eff = sigmoid(logit) * comp [n] and,
+            # for a backward pass, the 16-byte records (a_o, b, c_o, comp) [n, 4] in a scratch of the frame's own; the
+            # executor then packs, bins and composites with those plain opacities (TS_FRAME_LINEAR_OPACITY).  F.inputs
+            # keeps the logits: the backward pass points fr.opacities back at them for the fused Adam.
+            F.aa = torch.empty((5 * m,), **f32)           # rows[4 n] | o_eff[n]
+            o_eff = F.aa.data_ptr() + 16 * m
+            _call("ts_antialias_fwd", lib.ts_antialias_fwd, n, means.data_ptr(), scales.data_ptr(), quats.data_ptr(),
+                  view34.data_ptr(), ctypes.byref(cam), 3, opacities.data_ptr(), _lib.RASTER_LOGIT_OPACITY, None, o_eff,
+                  F.aa.data_ptr() if keep else None, s)
+            fr.opacities = o_eff
+            fr.flags |= _lib.FRAME_LINEAR_OPACITY
         _mark("fwd:allocated + struct")
         spin = COUNT_WAIT == "spin" and n > 0
         cap_key = (dev.index, n, w, h, cam.tile_row0, cam.tile_rows)
@@ -631,9 +647,14 @@ class fused_adam:
 class _RenderFrame(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, scales, quats, opacities, colors_dc, colors_rest, view34, projview,
-                origin, background, fx, fy, width, height, sh_degree, with_depth, tile_rows, group, planes=False):
+                origin, background, fx, fy, width, height, sh_degree, with_depth, tile_rows, group, planes=False,
+                antialiased=False):
+        if antialiased and group is not None:
+            raise NotImplementedError("rasterize_mode 'antialiased' is not built for a frame rendered with a process "
+                                      "group (tile-stripe sharding): render it on one GPU, or use the classic mode")
         F = _forward(means, scales, quats, opacities, colors_dc, colors_rest, view34, projview, origin,
-                     background, fx, fy, width, height, sh_degree, with_depth, tile_rows, keep=True, planes=planes)
+                     background, fx, fy, width, height, sh_degree, with_depth, tile_rows, keep=True, planes=planes,
+                     antialiased=antialiased)
         ctx.frame, ctx.group = F, group
         ctx.opacity_shape = opacities.shape
         ctx.rest_shape = colors_rest.shape
@@ -706,6 +727,13 @@ class _RenderFrame(torch.autograd.Function):
                 fr.v_colors_dc, fr.v_colors_rest = v_dc.data_ptr(), v_rest.data_ptr()
             _mark("bwd:allocated")
             _lib.check(lib.ts_frame_bwd_composite(ctypes.byref(fr), s), "ts_frame_bwd_composite")
+            if F.aa is not None:
+                # antialiased mode: v_opacity holds dL/do_eff (the frame ran on plain opacities).  In place, for the
+                # visible Gaussians: v_conic += the compensation's gradient, v_opacity <- dL/dlogit; then the logits
+                # take their place back, so that the fused Adam updates them
+                _call("ts_antialias_bwd", lib.ts_antialias_bwd, n, fr.radii, F.aa.data_ptr(), F.inputs[3].data_ptr(),
+                      _lib.RASTER_LOGIT_OPACITY, fr.v_opacity, fr.v_conic, s)
+                fr.opacities = F.inputs[3].data_ptr()
             if ctx.group is not None:                          # tile-stripe sharding: sum over ranks
                 with collective_timer.span(on_device=flat.is_cuda and dist.get_backend(ctx.group) != "gloo",
                                            label="all_reduce(2-D gradients)", nbytes=flat.numel() * flat.element_size()):
@@ -715,6 +743,8 @@ class _RenderFrame(torch.autograd.Function):
                            "ts_frame_bwd_params_adam")
             else:
                 _lib.check(lib.ts_frame_bwd_params(ctypes.byref(fr), s), "ts_frame_bwd_params")
+            if F.aa is not None:            # the struct describes the frame as it was rendered again (TS_FRAME_LINEAR_OPACITY
+                fr.opacities = F.aa.data_ptr() + 16 * max(n, 1)      # goes with o_eff): a second backward pass finds it so
         _mark("bwd:calls")
         if not single:      # compact copies: views would pin the n * (6 + ch) buffer
             v_xy = flat[:2 * n].view(n, 2).clone()
@@ -727,8 +757,8 @@ class _RenderFrame(torch.autograd.Function):
         xo.grad = v_xy if xo.grad is None else xo.grad + v_xy
         _mark("bwd:exit")
         if adam is not None:          # the parameters were updated in place: no gradients to hand out
-            return (None,) * 19
-        return (v_means, v_scales, v_quats, v_opac, v_dc, v_rest) + (None,) * 13
+            return (None,) * 20
+        return (v_means, v_scales, v_quats, v_opac, v_dc, v_rest) + (None,) * 14
 
 
 @torch.no_grad()
@@ -743,7 +773,7 @@ def render_view(model, view34: Tensor, projview: Tensor, origin: Tensor, fx: flo
     F = _forward(model.means.detach(), model.scales.detach(), model.quats.detach(), model.opacities.detach(),
                  model.colors_dc.detach(), model.colors_rest.detach(), view34, projview, origin,
                  model.background, fx, fy, width, height, int(model.active_sh_degree), with_depth, tile_rows,
-                 keep=False, planes=planes)
+                 keep=False, planes=planes, antialiased=rasterize_mode(model) == "antialiased")
     if F.planes:
         return F.out_img, F.out_depth, F.xys, F.radii
     return F.out_img, F.xys, F.radii
@@ -758,11 +788,15 @@ def render_frame(model, view34: Tensor, projview: Tensor, origin: Tensor, fx: fl
 
     ``group`` (a process group, or ``dist.group.WORLD``) makes backward sum the 2-D gradients over
     the ranks rendering the other stripes; ``None`` = single GPU, no collective.
+
+    A model with ``rasterize_mode = "antialiased"`` is rendered with every opacity scaled by the compensation factor of
+    the 2D low-pass, here and in ``render_frame_planes`` and ``render_view``; not with ``group``.
     """
     out, _, xys, radii = _RenderFrame.apply(model.means, model.scales, model.quats, model.opacities,
                                             model.colors_dc, model.colors_rest, view34, projview, origin,
                                             model.background, fx, fy, width, height, model.active_sh_degree,
-                                            with_depth, tile_rows, group, False)
+                                            with_depth, tile_rows, group, False,
+                                            rasterize_mode(model) == "antialiased")
     return out, xys, radii
 
 
@@ -776,4 +810,4 @@ def render_frame_planes(model, view34: Tensor, projview: Tensor, origin: Tensor,
     return _RenderFrame.apply(model.means, model.scales, model.quats, model.opacities,
                               model.colors_dc, model.colors_rest, view34, projview, origin,
                               model.background, fx, fy, width, height, model.active_sh_degree,
-                              True, tile_rows, None, True)
+                              True, tile_rows, None, True, rasterize_mode(model) == "antialiased")

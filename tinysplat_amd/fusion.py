@@ -293,8 +293,10 @@ def render_depth_alpha(model, camera, device=None):
         model.means, model.scales, 1., model.quats, view[:3, :], pv, camera.f_x, camera.f_y, w / 2, h / 2, h, w,
         tile_bounds((w, h)), log_scales=True, raw_quats=True)
     colors = torch.stack((z, torch.ones_like(z), torch.zeros_like(z)), dim=1)
-    out, _ = ops.rasterize_gaussians(xys, z, radii, conics, num_tiles, colors, model.opacities, h, w,
-                                     torch.zeros(3, dtype=torch.float32, device=dev), logit_opacity=True)
+    antialiased = ops.rasterize_mode(model) == "antialiased"        # compensated plain opacities
+    opacity = ops.compensated_opacity(model, view[:3, :], camera.f_x, camera.f_y, w, h) if antialiased else model.opacities
+    out, _ = ops.rasterize_gaussians(xys, z, radii, conics, num_tiles, colors, opacity, h, w,
+                                     torch.zeros(3, dtype=torch.float32, device=dev), logit_opacity=not antialiased)
     alpha = out[:, :, 1].contiguous()
     depth = torch.where(alpha > 0, out[:, :, 0] / alpha, torch.zeros_like(alpha))
     return depth, alpha

@@ -258,6 +258,83 @@ def project_gaussians(means3d: Tensor, scales: Tensor, glob_scale: float, quats:
 
 
 # --------------------------------------------------------------------------------------------------
+# opacity compensation of the antialiased mode (csrc/antialias.hip)
+# --------------------------------------------------------------------------------------------------
+RASTERIZE_MODES = ("classic", "antialiased")
+
+
+def rasterize_mode(model) -> str:
+    """``model.rasterize_mode``, "classic" for a model without the attribute; anything else raises."""
+    mode = getattr(model, "rasterize_mode", "classic")
+    if mode not in RASTERIZE_MODES:
+        raise ValueError(f"rasterize_mode {mode!r}: expected one of {RASTERIZE_MODES}")
+    return mode
+
+
+def refuse_antialiased(model, what: str) -> None:
+    """Raises for an antialiased model on a path the mode is not built for (the sharded trainers)."""
+    if rasterize_mode(model) == "antialiased":
+        raise NotImplementedError(f"{what} does not render rasterize_mode 'antialiased' (DESIGN.md section 6w: the sharded "
+                                  "paths are out of scope): render on one GPU, or use the classic mode")
+
+
+class _OpacityCompensation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means3d, scales, glob_scale, quats, viewmat, fx, fy, cx, cy, img_height, img_width, clip_thresh,
+                flags):
+        dev = _need_hip(means3d, scales, quats, viewmat)
+        n = means3d.shape[0]
+        if means3d.shape != (n, 3) or scales.shape != (n, 3) or quats.shape != (n, 4):
+            raise ValueError("means3d [N,3], scales [N,3], quats [N,4] expected")
+        if viewmat.numel() < 12:
+            raise ValueError("viewmat must hold the 3x4 view rows")
+        means3d, scales, quats, viewmat = _f32c(means3d), _f32c(scales), _f32c(quats), _f32c(viewmat)
+        cam = _camera(fx, fy, cx, cy, img_height, img_width, _tile_bounds(img_height, img_width), glob_scale, clip_thresh)
+        comp = torch.empty((n,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _call("ts_antialias_fwd", _lib.load().ts_antialias_fwd, n, _ptr(means3d), _ptr(scales), _ptr(quats),
+                  _ptr(viewmat), cam, int(flags), None, 0, _ptr(comp), None, None, _stream(dev))
+        ctx.cam, ctx.flags = cam, int(flags)
+        ctx.save_for_backward(means3d, scales, quats, viewmat)
+        return comp
+
+    @staticmethod
+    def backward(ctx, v_comp):
+        means3d, scales, quats, viewmat = ctx.saved_tensors
+        dev = means3d.device
+        n = means3d.shape[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        v_comp = _f32c(v_comp)
+        v_means, v_scales, v_quats = torch.empty((n, 3), **f32), torch.empty((n, 3), **f32), torch.empty((n, 4), **f32)
+        with torch.cuda.device(dev):
+            _call("ts_compensation_bwd", _lib.load().ts_compensation_bwd, n, _ptr(means3d), _ptr(scales), _ptr(quats),
+                  _ptr(viewmat), ctx.cam, ctx.flags, _ptr(v_comp), _ptr(v_means), _ptr(v_scales), _ptr(v_quats),
+                  _stream(dev))
+        return (v_means, v_scales, None, v_quats) + (None,) * 9
+
+
+def opacity_compensation(means3d: Tensor, scales: Tensor, glob_scale: float, quats: Tensor, viewmat: Tensor,
+                         fx: float, fy: float, cx: float, cy: float, img_height: int, img_width: int,
+                         clip_thresh: float = CLIP_THRESH, log_scales: bool = False, raw_quats: bool = False) -> Tensor:
+    """``comp[N] = sqrt(max(0, det(cov2d) / det(cov2d + 0.3 I)))`` of the covariance ``project_gaussians`` projects, before
+    its blur: the factor the antialiased mode scales an opacity by (0 behind the clip plane and where the max clamps,
+    with a zero gradient there).  Differentiable w.r.t. ``means3d``, ``scales``, ``quats``; ``log_scales`` /
+    ``raw_quats`` as in ``project_gaussians``."""
+    flags = (1 if log_scales else 0) | (2 if raw_quats else 0)
+    return _OpacityCompensation.apply(means3d, scales, glob_scale, quats, viewmat, fx, fy, cx, cy, img_height, img_width,
+                                      clip_thresh, flags)
+
+
+def compensated_opacity(model, viewmat: Tensor, fx: float, fy: float, width: int, height: int, op=None) -> Tensor:
+    """``sigmoid(model.opacities) * comp`` in the shape of ``model.opacities``: the plain opacity an op-by-op consumer of
+    an antialiased model hands to ``rasterize_gaussians`` (without ``logit_opacity``) in place of the logits.  ``op``: the
+    compensation op of a pluggable ops namespace (``GaussianRasterizer.ops``); None: ``opacity_compensation``."""
+    comp = (op or opacity_compensation)(model.means, model.scales, 1., model.quats, viewmat, fx, fy, width / 2, height / 2,
+                                        height, width, log_scales=True, raw_quats=True)
+    return torch.sigmoid(model.opacities) * comp.view(model.opacities.shape)
+
+
+# --------------------------------------------------------------------------------------------------
 # spherical_harmonics
 # --------------------------------------------------------------------------------------------------
 class _SphericalHarmonics(torch.autograd.Function):

@@ -121,7 +121,8 @@ class GaussianRasterizer:
                                    sh_colors=_hip_ops.sh_colors, fused_prep=True,
                                    four_channels=True, render_frame=_hip_frame.render_frame,
                                    render_view=_hip_frame.render_view,
-                                   render_frame_planes=_hip_frame.render_frame_planes)
+                                   render_frame_planes=_hip_frame.render_frame_planes,
+                                   opacity_compensation=_hip_ops.opacity_compensation)
 
     def __call__(self, camera, dims=None, sh_degree: Optional[int] = None):
         if dims is None:
@@ -172,36 +173,53 @@ class GaussianRasterizer:
             xys.retain_grad()          # model_gaussian.py:130-132 reads extras['xys'].grad
 
         colors = self.colors(camera)
+        o_eff = self._compensated_opacity(camera, dims)
+        if o_eff is not None:              # antialiased model: a plain opacity takes the place of the logits / the sigmoid
+            rkw = {}
 
         if self.fused_depth and getattr(ops, "four_channels", False):
             # one 4-channel compositing pass instead of the reference's two 3-channel ones
             # (rasterize.py:44 and :50): channel 3 carries the depth, its background is
             # background[0] exactly as in the reference's depth pass (rasterize.py:86)
             ra = self._raster_inputs(xys, depths, radii, conics, num_tiles,
-                                     torch.cat([colors, depths[:, None]], dim=1), dims, prep)
+                                     torch.cat([colors, depths[:, None]], dim=1), dims, prep, o_eff)
             ra[9] = torch.cat([ra[9], ra[9][:1]])
             out, _ = ops.rasterize_gaussians(*ra, **rkw)
             rgb = torch.clamp(out[:, :, :3], max=1.0)
             depth_map = out[:, :, 3]
         else:
             rgb, _ = ops.rasterize_gaussians(*self._raster_inputs(
-                xys, depths, radii, conics, num_tiles, colors, dims, prep), **rkw)
+                xys, depths, radii, conics, num_tiles, colors, dims, prep, o_eff), **rkw)
             rgb = torch.clamp(rgb, max=1.0)
             depth_as_color = depths[:, None].repeat(1, 3)
             depth_img, _ = ops.rasterize_gaussians(*self._raster_inputs(
-                xys, depths, radii, conics, num_tiles, depth_as_color, dims, prep), **rkw)
+                xys, depths, radii, conics, num_tiles, depth_as_color, dims, prep, o_eff), **rkw)
             depth_map = depth_img[:, :, 0]
 
         extras = {"depth": depth_map, "radii": radii, "xys": xys,
                   "camera": {"height": camera.height, "width": camera.width}}
         return rgb, extras
 
-    def _raster_inputs(self, xys, depths, radii, conics, num_tiles, colors, dims, prep):
+    def _raster_inputs(self, xys, depths, radii, conics, num_tiles, colors, dims, prep, o_eff=None):
+        w, h = dims
+        if o_eff is not None:
+            return [xys, depths, radii, conics, num_tiles, colors, o_eff, h, w, self.model.background]
         if not prep:
             return self.rasterize_forward_inputs(xys, depths, radii, conics, num_tiles, colors, dims)
-        w, h = dims
         return [xys, depths, radii, conics, num_tiles, colors, self.model.opacities, h, w,
                 self.model.background]
+
+    def _compensated_opacity(self, camera, dims):
+        """The op-by-op paths of an antialiased model: ``sigmoid(opacities) * comp`` from the
+        compensation op of the ops namespace, handed to rasterize_gaussians as a plain opacity; None for a classic model."""
+        if _hip_ops.rasterize_mode(self.model) != "antialiased":
+            return None
+        op = getattr(self.ops, "opacity_compensation", None)
+        if op is None:
+            raise RuntimeError("rasterize_mode 'antialiased' needs an ops namespace with opacity_compensation")
+        w, h = dims
+        view = camera_on_device(camera, self.device)[0]
+        return _hip_ops.compensated_opacity(self.model, view[:3, :], camera.f_x, camera.f_y, w, h, op=op)
 
     def colors(self, camera):
         """Per-Gaussian RGB handed to the rasterizer: clamp(SH(...) + 0.5, min=0)."""

@@ -114,6 +114,17 @@ class LiftResult:
     class_ids: List[int]
 
 
+def _view_opacity(model, camera, dev):
+    """(opacity tensor, TS_RASTER_* flag word) a view of ``model`` composites with: the logits, or for an antialiased model
+     the compensated plain opacities of this camera."""
+    if _ops.rasterize_mode(model) != "antialiased":
+        return model.opacities.detach().contiguous(), _lib.RASTER_LOGIT_OPACITY
+    view = camera.view_matrix.to(dev)
+    with torch.no_grad():
+        o_eff = _ops.compensated_opacity(model, view[:3, :], camera.f_x, camera.f_y, int(camera.width), int(camera.height))
+    return o_eff.contiguous(), 0
+
+
 def _vote_view(model, camera, label_map: Optional[Tensor], class_map: Optional[Tensor], votes: Tensor,
                dummy_colors: Tensor) -> None:
     """Adds one view's votes: project -> bin -> pack -> ts_label_votes, the forward launch's own lists and records."""
@@ -124,6 +135,7 @@ def _vote_view(model, camera, label_map: Optional[Tensor], class_map: Optional[T
     b = _ops.bin_gaussians(xys, depths, radii, nth, h, w, use_cache=False)
     if b.num_intersects == 0:
         return
+    opacity, opacity_flags = _view_opacity(model, camera, dev)
     if label_map is not None and (label_map.dtype != torch.uint8 or tuple(label_map.shape) != (h, w)
                                   or label_map.device != dev):
         raise ValueError(f"a label map must be a uint8 [{h}, {w}] tensor on {dev}")
@@ -131,8 +143,8 @@ def _vote_view(model, camera, label_map: Optional[Tensor], class_map: Optional[T
     lib = _lib.load()
     s = _stream(dev)
     with torch.cuda.device(dev):
-        _call("ts_pack_splats", lib.ts_pack_splats, n, 3, _lib.RASTER_LOGIT_OPACITY, _ptr(xys.contiguous()),
-              _ptr(b._keep[2]), _ptr(conics.contiguous()), _ptr(dummy_colors), _ptr(model.opacities.detach().contiguous()),
+        _call("ts_pack_splats", lib.ts_pack_splats, n, 3, opacity_flags, _ptr(xys.contiguous()),
+              _ptr(b._keep[2]), _ptr(conics.contiguous()), _ptr(dummy_colors), _ptr(opacity),
               _ptr(b.cum_tiles_hit), b.cam, None, _ptr(splats), s)
         _call("ts_label_votes", lib.ts_label_votes, 0, b.cam, _ptr(b.tile_bins), _ptr(b.gaussian_ids_sorted),
               _ptr(splats), _ptr(None if label_map is None else label_map.contiguous()), _ptr(class_map),
@@ -224,7 +236,8 @@ def select_gaussians(model, mask: Tensor) -> SplatModel:
     if mask.dtype != torch.bool or mask.shape != (model.means.shape[0],):
         raise ValueError("mask must be a bool [N] tensor")
     rows = [p.detach()[mask] for p in model.parameters()]
-    return SplatModel(*rows, active_sh_degree=model.active_sh_degree, background=model.background)
+    return SplatModel(*rows, active_sh_degree=model.active_sh_degree, background=model.background,
+                      rasterize_mode=_ops.rasterize_mode(model))
 
 
 @torch.no_grad()
@@ -244,13 +257,14 @@ def render_labels(model, camera, labels: Tensor, num_classes: int) -> Tensor:
     xys, depths, radii, conics, nth, _ = _ops.project_gaussians(*project_args(model, camera, (w, h), dev))
     best = torch.zeros((h, w), dtype=torch.float32, device=dev)
     background = torch.zeros(4, dtype=torch.float32, device=dev)
+    opacity, opacity_flags = _view_opacity(model, camera, dev)
     for at in range(0, len(present), 4):                   # ascending classes and a strict `>`: ties to the smaller
         group = present[at:at + 4]
         one_hot = torch.zeros((n, 4), dtype=torch.float32, device=dev)
         for j, c in enumerate(group):
             one_hot[:, j] = (labels == c).to(torch.float32)
-        img, _ = _ops.rasterize_gaussians(xys, depths, radii, conics, nth, one_hot, model.opacities.detach(), h, w,
-                                          background, logit_opacity=True)
+        img, _ = _ops.rasterize_gaussians(xys, depths, radii, conics, nth, one_hot, opacity, h, w,
+                                          background, logit_opacity=bool(opacity_flags))
         for j, c in enumerate(group):
             better = img[:, :, j] > best
             best = torch.where(better, img[:, :, j], best)

@@ -46,7 +46,8 @@ from ._comm import collective_timer
 from . import _lib
 from . import frame as _frame
 from ._lib import TsFrame, TsStripes
-from .ops import _call, _camera, kernel_timer, _f32c, _need_hip, _stream, _stripe_rows, _tile_bounds, deg_from_sh
+from .ops import (_call, _camera, kernel_timer, _f32c, _need_hip, _stream, _stripe_rows, _tile_bounds, deg_from_sh,
+                  refuse_antialiased)
 from .rasterizer import camera_on_device
 from .sharding import stripe_rows
 from .synthetic import SplatModel
@@ -236,7 +237,8 @@ def shard_model(model, world: int, rank: int) -> SplatModel:
     """Rank's rows of the six parameter tensors as a model of its own (fresh leaf tensors)."""
     i0, i1 = shard_range(model.means.shape[0], world, rank)
     ps = [p.detach()[i0:i1].clone() for p in model.parameters()]
-    return SplatModel(*ps, active_sh_degree=model.active_sh_degree, background=model.background)
+    return SplatModel(*ps, active_sh_degree=model.active_sh_degree, background=model.background,
+                      rasterize_mode=getattr(model, "rasterize_mode", "classic"))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1102,6 +1104,7 @@ def render_sharded(model_shard, camera, device, layout: ShardLayout, exchange: E
         raise ValueError("the sharded trainer does not take masks: a rank's loss runs on its stripe of the frame, and the "
                          "masked loss (DESIGN.md section 6v) is built for whole images only - train masked scenes on "
                          "one GPU (training.fit(..., masks=))")
+    refuse_antialiased(model_shard, "render_sharded")
     view, projview, origin = camera_on_device(camera, device)
     out, xys, _ = _ShardedFrame.apply(model_shard.means, model_shard.scales, model_shard.quats,
                                       model_shard.opacities, model_shard.colors_dc, model_shard.colors_rest,
@@ -1124,6 +1127,7 @@ class _LocalCounts(Exchange):
 def export_records(model_shard, camera, device, layout: ShardLayout, with_depth: bool = False):
     """Owner stage only: the records this rank would send, grouped by destination -> (records, send_counts).
     (bench.py's --emulate-ranks records the other ranks' traffic with it.)"""
+    refuse_antialiased(model_shard, "export_records")
     dev = torch.device(device)
     view, projview, origin = camera_on_device(camera, dev)
     lib = _lib.load()
@@ -1143,6 +1147,7 @@ def simulate_frame(model, camera, dims, device, world: int, v_img_of, with_depth
     on 1-GPU boxes.  ``model``: the WHOLE model; ``v_img_of(rank, image, (y0, y1))`` -> upstream gradient of that
     rank's stripe image.  -> (list of stripe images, list of (y0, y1), gradients of the six whole parameter
     tensors in ``model.parameters()`` order, v_xy[N, 2], per-rank record counts)."""
+    refuse_antialiased(model, "simulate_frame")
     dev = torch.device(device)
     n_total = model.means.shape[0]
     view, projview, origin = camera_on_device(camera, dev)

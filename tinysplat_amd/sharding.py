@@ -103,6 +103,8 @@ def render_stripe(model, camera, dims, device, rank: int = 0, world_size: int = 
     whole frame without a collective; ``collective`` overrides whether the all-reduce runs.
     """
     from . import frame as _frame
+    from .ops import refuse_antialiased
+    refuse_antialiased(model, "render_stripe")
     w, h = dims
     tby = tile_bounds(dims)[1]
     if tile_rows is None:
@@ -125,6 +127,8 @@ def render_rgb_stripe(model, camera, dims, ops, device, rank: int = 0, world_siz
 
     world_size == 1 renders the whole frame and involves no collective.
     """
+    from .ops import refuse_antialiased
+    refuse_antialiased(model, "render_rgb_stripe")
     w, h = dims
     tby = tile_bounds(dims)[1]
     if tile_rows is None:

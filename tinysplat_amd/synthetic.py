@@ -185,7 +185,12 @@ class SplatModel:
     """Holder of the six learnable tensors in the reference's layout (model_gaussian.py:84-89)."""
 
     def __init__(self, means, colors_dc, colors_rest, scales, quats, opacities,
-                 active_sh_degree: int, background=None):
+                 active_sh_degree: int, background=None, rasterize_mode: str = "classic"):
+        if rasterize_mode not in ("classic", "antialiased"):
+            raise ValueError(f"rasterize_mode {rasterize_mode!r}: expected 'classic' or 'antialiased'")
+        # "antialiased": every render of the model scales each opacity by sqrt(det(cov2d) / det(cov2d + 0.3 I)), so that
+        # the projection's low-pass spreads a Gaussian's energy instead of adding to it (DESIGN.md section 6w)
+        self.rasterize_mode = rasterize_mode
         self.means = means
         self.colors_dc = colors_dc
         self.colors_rest = colors_rest
@@ -199,7 +204,8 @@ class SplatModel:
         return [self.means, self.colors_dc, self.colors_rest, self.scales, self.quats, self.opacities]
 
     def to(self, device):
-        kw = dict(active_sh_degree=self.active_sh_degree, background=self.background.to(device))
+        kw = dict(active_sh_degree=self.active_sh_degree, background=self.background.to(device),
+                  rasterize_mode=getattr(self, "rasterize_mode", "classic"))
         ps = [p.detach().to(device) for p in self.parameters()]
         return SplatModel(*ps, **kw)
 

@@ -55,6 +55,8 @@ def parse(argv=None):
                     help="label maps <image name>.npy: also print the mIoU of the rendered labels on the evaluated views")
     ap.add_argument("--semantic-classes", type=int, default=150, help="labels of the maps: 0 .. this - 1, 255 ignored")
     ap.add_argument("--min-share", type=float, default=0.0, help="least share of a Gaussian's votes its class must have")
+    ap.add_argument("--antialiased", action="store_true",
+                    help="render in the antialiased mode (opacity compensation for the 2D low-pass), whatever the file says")
     from train import add_mask_arguments, mask_classes
     add_mask_arguments(ap, semantic=False)
     args = ap.parse_args(argv)
@@ -122,6 +124,8 @@ def main(argv=None):
     dataset = Dataset(base / args.colmap_path, base / args.images_path, max_image_dimension=args.max_image_dimension,
                       device=args.device, principal_point=args.principal_point)
     model = getattr(formats, READERS[Path(args.scene).suffix.lower()])(args.scene, args.device)
+    if args.antialiased:                 # overrides what the file says (a .pth or .splat says nothing)
+        model.rasterize_mode = "antialiased"
     train, test = holdout_split([c.name for c in dataset.cameras], args.holdout)
     views = test if args.holdout else train
     if args.poses:

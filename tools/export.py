@@ -69,6 +69,10 @@ def parse(argv=None):
                     help="z up, centred and unit-sized by the cameras of --dataset-dir, before the manual transform")
     ap.add_argument("--crop-box", type=float_list(6), default=None,
                     help="cx,cy,cz,hx,hy,hz: keep the Gaussians inside this axis-aligned box of the new frame")
+    ap.add_argument("--antialiased", action="store_true",
+                    help="treat the input as a model of the antialiased mode (opacity compensation for the 2D low-pass), "
+                         "whatever the file says: the depth renders of --mesher tsdf and the votes of --semantic-dir "
+                         "follow it, and a PLY output records it")
     args = ap.parse_args(argv)
     mesh = args.filetype in ("OBJ", "MESH_PLY")
     if args.limit is not None and args.filetype != "SPLAT":
@@ -189,6 +193,8 @@ def main(argv=None):
         raise SystemExit("no GPU: tinysplat_amd has no CPU path")
     from tinysplat_amd import MeshConfig, extract_mesh, formats
     model = load_model(args.input_file, args.device)
+    if args.antialiased:
+        model.rasterize_mode = "antialiased"
     cameras = dataset_cameras(args.dataset_dir, args.colmap_path) if args.dataset_dir is not None else None
     if args.semantic_dir is not None:
         model = cut_by_class(model, cameras, args)

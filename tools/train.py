@@ -220,6 +220,21 @@ def parse_frame(argv=None):
     return _frame_parser().parse_known_args(argv)[0]
 
 
+def _render_parser():
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    g = ap.add_argument_group("rendering")
+    g.add_argument("--antialiased", action="store_true",
+                   help="train and evaluate in the antialiased mode: every opacity is scaled by sqrt(det(cov2d) / "
+                        "det(cov2d + 0.3 I)), so that the 2D low-pass spreads a Gaussian's energy and adds none; a .ply "
+                        "output records the mode")
+    return ap
+
+
+def parse_render(argv=None):
+    """The rasterize mode's option, a namespace of its own like the depth prior's."""
+    return _render_parser().parse_known_args(argv)[0]
+
+
 def parse(argv=None):
     depth_ap, strategy_ap, appearance_ap = _depth_parser(), _strategy_parser(), _appearance_parser()
     parse_depth(argv)                                          # checks the depth prior's options
@@ -229,6 +244,7 @@ def parse(argv=None):
     _strategy, argv = strategy_ap.parse_known_args(argv)
     _appearance, argv = appearance_ap.parse_known_args(argv)
     _frame, argv = _frame_parser().parse_known_args(argv)
+    _render, argv = _render_parser().parse_known_args(argv)
     parse_masks(argv)
     _masks, argv = _mask_parser().parse_known_args(argv)
     parse_pose(argv)
@@ -239,6 +255,7 @@ def parse(argv=None):
                                  strategy_ap.format_help().split("\n\n", 1)[-1] + "\n" +
                                  appearance_ap.format_help().split("\n\n", 1)[-1] + "\n" +
                                  _frame_parser().format_help().split("\n\n", 1)[-1] + "\n" +
+                                 _render_parser().format_help().split("\n\n", 1)[-1] + "\n" +
                                  _mask_parser().format_help().split("\n\n", 1)[-1] + "\n" +
                                  pose_ap.format_help().split("\n\n", 1)[-1])
     ap.add_argument("--device", type=str, default="cuda:0")
@@ -300,6 +317,8 @@ def main(argv=None):
     if parse_frame(argv).normalize_scene:
         normalize_scene(dataset)
     model = from_pcd(dataset.pcd, sh_degree=args.sh_degree, device=args.device)
+    if parse_render(argv).antialiased:
+        model.rasterize_mode = "antialiased"
     cameras, targets, evaluator, corrected = dataset.cameras, dataset.targets, None, None
     masks = held_masks = None
     if masking.masks_dir is not None or masking.classes:

@@ -33,6 +33,8 @@ def parse(argv=None):
     ap.add_argument("--subsampling", choices=("420", "444"), default="420")
     ap.add_argument("--viewer-ip", type=str, default="127.0.0.1")
     ap.add_argument("--viewer-port", type=int, default=8765)
+    ap.add_argument("--antialiased", action="store_true",
+                    help="render in the antialiased mode (opacity compensation for the 2D low-pass), whatever the file says")
     args = ap.parse_args(argv)
     if Path(args.scene).suffix.lower() not in READERS:
         ap.error(f"the scene must end in one of {', '.join(READERS)}")
@@ -49,6 +51,8 @@ def main(argv=None):
     from tinysplat_amd import Viewer, formats
     from tinysplat_amd.viewer import ViewRenderer
     model = getattr(formats, READERS[Path(args.scene).suffix.lower()])(args.scene, args.device)
+    if args.antialiased:                 # overrides what the file says (a .pth or .splat says nothing)
+        model.rasterize_mode = "antialiased"
     if args.dataset_dir is not None:
         from tinysplat_amd.colmap import read_reconstruction
         from tinysplat_amd.dataset import camera_from_colmap
