@@ -171,8 +171,11 @@ __device__ __forceinline__ void dma_record(const float4* __restrict__ splats, in
 #define TS_DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #define TS_LDS_WAIT() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
-#ifndef TS_REDUCE_AHEAD
-#define TS_REDUCE_AHEAD 4                // rows of a Gaussian requested together by reduce_partials
+#ifndef TS_REDUCE_ROWS
+#define TS_REDUCE_ROWS 4                 // FLAGGED rows of a Gaussian requested together by reduce_partials
+#endif
+#ifndef TS_REDUCE_BLOCK
+#define TS_REDUCE_BLOCK 256              // threads (= Gaussians) per workgroup of reduce_partials
 #endif
 
 constexpr int kWaves = 4;                 // tiles (= waves) per workgroup; waves never synchronise (COOPERATIVE TILES: the four
@@ -1893,20 +1896,68 @@ __global__ __launch_bounds__(64 * kBwdWaves, TS_BWD_MIN_WAVES_16) void raster_bw
 // with d = xy - pixel.  The conic / opacity factors are applied once per Gaussian here.
 // color_mask (may be NULL): clamp mask of the colour stage, applied here (bit c clear -> v_colors[c] = 0)
 // when the gradients are summed over ranks before the colour stage's backward runs.
-// One lane per Gaussian walks all its slots in ascending order - a fixed order, so the gradients stay bit-reproducible
-// run to run.  (Several lanes per Gaussian did not pay: the walk is bound by its row gathers, not by its longest lane -
-// profiles/HISTORY.md, "build-time variants retired from the tree".)
-template <int CH>
-__global__ __launch_bounds__(256) void reduce_partials_kernel(
+// One lane per Gaussian adds its FLAGGED rows in ascending slot order - a fixed order, so the gradients stay
+// bit-reproducible run to run.  The lane walks the flagged rows, not the slots: the flags of up to 32 slots arrive as one
+// window (FlagWindow) and become a bit mask, whose set bits are taken TS_REDUCE_ROWS at a time.  A wave's chain of
+// dependent round trips is then counts + records | flags | rows (| more rows), and its trip count the largest number of
+// flagged rows among its lanes instead of the largest slot count (profiles/reduce_rows_walk.txt).  (Several lanes per
+// Gaussian did not pay, 59 / 56 / 58 / 87 / 183 us for 1 ... 16 lanes on the slot walk: a wave did fewer steps, but there
+// were as many more waves - profiles/HISTORY.md, "build-time variants retired from the tree".)
+
+// The flag bytes of the slots [s0, s0 + len), 1 <= len <= 32, fetched as the naturally aligned 16-byte pieces that
+// overlap them: every piece holds a byte of the Gaussian's own range, so it lies in that byte's page, wherever the array
+// starts and ends.  Bytes of other Gaussians (or of whatever surrounds the array) are shifted and masked out in bits().
+struct FlagWindow {
+    uint4 c0, c1, c2;
+    int sh, len;
+
+    __device__ __forceinline__ void request(const unsigned char* __restrict__ row_flags, int s0, int end) {
+        sh = (int)((unsigned long long)(row_flags + s0) & 15ull);
+        len = min(32, end - s0);
+        const unsigned char* p = row_flags + ((long long)s0 - sh);
+        // a piece that holds none of the slots is not fetched: the first one, which holds slot s0, is fetched in its
+        // place, and what it puts into the mask lies at or above bit len
+        c0 = *reinterpret_cast<const uint4*>(p);
+        c1 = *reinterpret_cast<const uint4*>(p + (sh + len > 16 ? 16 : 0));   // byte 16 is slot s0 + 16 - sh < s0 + len
+        c2 = *reinterpret_cast<const uint4*>(p + (sh + len > 32 ? 32 : 0));   // byte 32 likewise
+    }
+    // bit k: byte k of the piece equals the generation (gen4 = the generation in all four bytes of a word)
+    static __device__ __forceinline__ unsigned int piece_bits(const uint4& c, unsigned int gen4) {
+        auto nibble = [gen4](unsigned int w) {
+            w ^= gen4;                                // a matching byte is now zero
+            const unsigned int nz = ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w;         // bit 7 of every non-zero byte
+            // bits 0, 8, 16, 24 (byte k is zero) -> bits 24 .. 27: the products land on distinct bits, nothing carries
+            return (((~nz & 0x80808080u) >> 7) * 0x01020408u) >> 24;
+        };
+        return nibble(c.x) | (nibble(c.y) << 4) | (nibble(c.z) << 8) | (nibble(c.w) << 12);
+    }
+    // bit u set iff row_flags[s0 + u] == generation, u < len
+    __device__ __forceinline__ unsigned int bits(unsigned int gen4) const {
+        const unsigned long long b = (unsigned long long)piece_bits(c0, gen4) |
+                                     ((unsigned long long)piece_bits(c1, gen4) << 16) |
+                                     ((unsigned long long)piece_bits(c2, gen4) << 32);
+        return (unsigned int)(b >> sh) & (0xffffffffu >> (32 - len));
+    }
+};
+
+constexpr int kReduceBlock = TS_REDUCE_BLOCK;
+
+// SPLIT (TS_RASTER_SPLIT_BLOCKS, the same for every lane) is a launch of its own: its four-row slots and the row walk
+// would otherwise share one register budget.
+template <int CH, bool SPLIT>
+__global__ __launch_bounds__(kReduceBlock) void reduce_partials_kernel(
     int n, int flags, const int* __restrict__ num_tiles_hit, const int* __restrict__ cum_tiles_hit,
     const float4* __restrict__ partials, const unsigned char* __restrict__ row_flags,
     const float4* __restrict__ splats, float* __restrict__ v_xy, float* __restrict__ v_conic,
     float* __restrict__ v_colors, float* __restrict__ v_opacity, float* __restrict__ v_depth,
     const unsigned char* __restrict__ color_mask, float4* __restrict__ grad_rows) {
-    const int i = (int)((long long)blockIdx.x * 256 + threadIdx.x);
+    const int i = (int)((long long)blockIdx.x * kReduceBlock + threadIdx.x);
     if (i >= n) return;
-    const int cnt = num_tiles_hit[i];
-    const long long end = cum_tiles_hit[i];
+    // everything that depends on i alone is requested here: the record too (a Gaussian without slots ignores it)
+    int cnt = num_tiles_hit[i], end32 = cum_tiles_hit[i];
+    const float4 q0 = splats[3 * (size_t)i], q1 = splats[3 * (size_t)i + 1];
+    asm volatile("" : "+v"(cnt), "+v"(end32));     // or the loads sink to where a branch on cnt has already waited
+    const long long end = end32;
     // a row holds data of THIS pass iff its flag equals the pass's value (legacy value 1 on a zeroed array, or
     // the caller's generation on a persistent one: TS_RASTER_FLAG_GEN)
     const unsigned int gen = ((unsigned int)flags >> 8) & 0xffu ? ((unsigned int)flags >> 8) & 0xffu : 1u;
@@ -1923,7 +1974,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
         s[4] += (double)p1.x; s[5] += (double)p1.y; s[6] += (double)p1.z; s[7] += (double)p1.w;
         s[8] += (double)p2.x; s[9] += (double)p2.y;
     };
-    if (flags & TS_RASTER_SPLIT_BLOCKS) {         // four rows per (tile, Gaussian): one flag word per pair
+    if (SPLIT) {                                  // four rows per (tile, Gaussian): one flag word per pair
         const unsigned int* flags4 = reinterpret_cast<const unsigned int*>(row_flags);
         for (long long sl = end - cnt; sl < end; ++sl) {
             const unsigned int fw = flags4[sl];
@@ -1945,26 +1996,45 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
             }
         }
     } else {
-        // kAhead slots per step: their flags, then the rows of the flagged ones, are all requested before the
-        // first addition, which happens in slot order - a lane's walk is otherwise a chain of dependent
-        // flag -> row -> flag loads
-        constexpr int kAhead = TS_REDUCE_AHEAD;
-        for (long long s0 = end - cnt; s0 < end; s0 += kAhead) {
-            bool f[kAhead];
-            float4 p0[kAhead], p1[kAhead], p2[kAhead];
+        // Windows of 32 slots.  The set bits of a window's mask are taken kRows at a time, lowest first: their rows are
+        // all requested before the first addition, which happens in slot order.  No row is addressed unless its flag
+        // matched (an unflagged slot's row may never have been written, a masked-off byte is not this Gaussian's).
+        // A Gaussian with more than 32 slots asks for its next window together with the last rows of this one.
+        constexpr int kRows = TS_REDUCE_ROWS;
+        const unsigned int gen4 = gen * 0x01010101u;
+        const int last = (int)end;
+        int s0 = last - cnt;
+        FlagWindow win;
+        unsigned int m = 0u;
+        bool more = cnt > 0;
+        if (more) { win.request(row_flags, s0, last); m = win.bits(gen4); }
+        while (more) {
+            more = s0 + 32 < last;
+            do {
+                bool f[kRows];
+                long long row[kRows];
+                float4 p0[kRows], p1[kRows], p2[kRows];
 #pragma unroll
-            for (int u = 0; u < kAhead; ++u) f[u] = (s0 + u < end) && row_flags[s0 + u] == gen;   // else: not written in this pass (stale)
-#pragma unroll
-            for (int u = 0; u < kAhead; ++u) {
-                if (f[u]) {
-                    p0[u] = partials[kRowF4 * (s0 + u)]; p1[u] = partials[kRowF4 * (s0 + u) + 1];
-                    p2[u] = partials[kRowF4 * (s0 + u) + 2];
+                for (int r = 0; r < kRows; ++r) {
+                    f[r] = m != 0u;
+                    row[r] = (long long)kRowF4 * (s0 + (__ffs(m) - 1));
+                    m &= m - 1u;
                 }
-            }
+                // every address of the step exists before its first row is requested: an address worked out between
+                // two requests may land in registers that an earlier request still writes, and waits for it
 #pragma unroll
-            for (int u = 0; u < kAhead; ++u) {
-                if (f[u]) add_row(p0[u], p1[u], p2[u]);
-            }
+                for (int r = 0; r < kRows; ++r) asm volatile("" : "+v"(row[r]));
+#pragma unroll
+                for (int r = 0; r < kRows; ++r) {
+                    if (f[r]) { p0[r] = partials[row[r]]; p1[r] = partials[row[r] + 1]; p2[r] = partials[row[r] + 2]; }
+                }
+                if (m == 0u && more) win.request(row_flags, s0 + 32, last);
+#pragma unroll
+                for (int r = 0; r < kRows; ++r) {
+                    if (f[r]) add_row(p0[r], p1[r], p2[r]);
+                }
+            } while (m);
+            if (more) { s0 += 32; m = win.bits(gen4); }
         }
     }
     float4 a0 = make_float4((float)s[0], (float)s[1], (float)s[2], (float)s[3]);
@@ -1972,7 +2042,6 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
     float4 a2 = make_float4((float)s[8], (float)s[9], 0.f, 0.f);
     float vx = 0.f, vy = 0.f, vop = 0.f;
     if (cnt > 0) {
-        const float4 q0 = splats[3 * (size_t)i], q1 = splats[3 * (size_t)i + 1];
         const float A = q0.w, B = q1.x, C = q1.y, op = q0.z;
         vx = A * a0.y + B * a0.z;
         vy = B * a0.y + C * a0.z;
@@ -2246,6 +2315,27 @@ int raster_bwd(int32_t channels, int32_t flags, int64_t num_intersects, const ts
 
 }  // namespace ts_surv
 
+namespace {
+
+// the one launch behind ts_reduce_partials (grad_rows NULL) and ts_reduce_partials_rows (the five arrays NULL)
+void launch_reduce_partials(int32_t n, int32_t channels, int32_t flags, const int32_t* num_tiles_hit,
+                            const int32_t* cum_tiles_hit, const float* partials, const uint8_t* row_flags,
+                            const float* splats, float* v_xy, float* v_conic, float* v_colors, float* v_opacity,
+                            float* v_depth, const uint8_t* color_mask, float* grad_rows, void* stream) {
+    const int grid = (int)(((long long)n + kReduceBlock - 1) / kReduceBlock);
+#define TS_LAUNCH_REDUCE(CH, SPLIT)                                                                                     \
+    hipLaunchKernelGGL((reduce_partials_kernel<CH, SPLIT>), dim3(grid), dim3(kReduceBlock), 0, (hipStream_t)stream, n,  \
+                       (int)flags, num_tiles_hit, cum_tiles_hit, reinterpret_cast<const float4*>(partials), row_flags,  \
+                       reinterpret_cast<const float4*>(splats), v_xy, v_conic, v_colors, v_opacity, v_depth, color_mask, \
+                       reinterpret_cast<float4*>(grad_rows))
+    const bool split = (flags & TS_RASTER_SPLIT_BLOCKS) != 0;
+    if (channels == 3) { if (split) TS_LAUNCH_REDUCE(3, true); else TS_LAUNCH_REDUCE(3, false); }
+    else { if (split) TS_LAUNCH_REDUCE(4, true); else TS_LAUNCH_REDUCE(4, false); }
+#undef TS_LAUNCH_REDUCE
+}
+
+}  // namespace
+
 extern "C" {
 
 int ts_reduce_partials(int32_t n, int32_t channels, int32_t flags, const int32_t* num_tiles_hit,
@@ -2257,18 +2347,8 @@ int ts_reduce_partials(int32_t n, int32_t channels, int32_t flags, const int32_t
     if (n == 0) return 0;
     if (!num_tiles_hit || !cum_tiles_hit || !row_flags || !splats || !v_xy || !v_conic || !v_colors || !v_opacity)
         return TS_E_BADARG;
-    hipStream_t s = (hipStream_t)stream;
-    const float4* pr = reinterpret_cast<const float4*>(partials);
-    const float4* sp = reinterpret_cast<const float4*>(splats);
-    const int grid = (int)(((long long)n + 255) / 256);
-    if (channels == 3)
-        hipLaunchKernelGGL(reduce_partials_kernel<3>, dim3(grid), dim3(256), 0, s, n, (int)flags, num_tiles_hit,
-                           cum_tiles_hit, pr, row_flags, sp, v_xy, v_conic, v_colors, v_opacity, v_depth, color_mask,
-                           (float4*)nullptr);
-    else
-        hipLaunchKernelGGL(reduce_partials_kernel<4>, dim3(grid), dim3(256), 0, s, n, (int)flags, num_tiles_hit,
-                           cum_tiles_hit, pr, row_flags, sp, v_xy, v_conic, v_colors, v_opacity, v_depth, color_mask,
-                           (float4*)nullptr);
+    launch_reduce_partials(n, channels, flags, num_tiles_hit, cum_tiles_hit, partials, row_flags, splats, v_xy, v_conic,
+                           v_colors, v_opacity, v_depth, color_mask, nullptr, stream);
     return launch_status();
 }
 
@@ -2278,19 +2358,8 @@ int ts_reduce_partials_rows(int32_t n, int32_t channels, int32_t flags, const in
     if (n < 0 || (channels != 3 && channels != 4)) return TS_E_BADARG;
     if (n == 0) return 0;
     if (!num_tiles_hit || !cum_tiles_hit || !row_flags || !splats || !grad_rows) return TS_E_BADARG;
-    hipStream_t s = (hipStream_t)stream;
-    const float4* pr = reinterpret_cast<const float4*>(partials);
-    const float4* sp = reinterpret_cast<const float4*>(splats);
-    float4* gr = reinterpret_cast<float4*>(grad_rows);
-    const int grid = (int)(((long long)n + 255) / 256);
-    if (channels == 3)
-        hipLaunchKernelGGL(reduce_partials_kernel<3>, dim3(grid), dim3(256), 0, s, n, (int)flags, num_tiles_hit,
-                           cum_tiles_hit, pr, row_flags, sp, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                           (float*)nullptr, (float*)nullptr, (const unsigned char*)nullptr, gr);
-    else
-        hipLaunchKernelGGL(reduce_partials_kernel<4>, dim3(grid), dim3(256), 0, s, n, (int)flags, num_tiles_hit,
-                           cum_tiles_hit, pr, row_flags, sp, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                           (float*)nullptr, (float*)nullptr, (const unsigned char*)nullptr, gr);
+    launch_reduce_partials(n, channels, flags, num_tiles_hit, cum_tiles_hit, partials, row_flags, splats, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, grad_rows, stream);
     return launch_status();
 }
 
